@@ -16,7 +16,14 @@ cases; the default cfg2 is the metric's):
         one training step on them; every step is the whole chain
   cfg5  B=8/GPU 512x512, CE + 0.1 * NCut + 0.1 * ConstrainToBoundaryLoss(sigma_c 0.1, sigma_s 5)
 
-Prints ONE JSON line (rank 0).  Besides the contract keys:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the contract keys (metric,
+value, unit, higher_is_better, dtype, ms_per_step) with the configuration and the host time of the timed region.
+``--dump-outputs DIR`` writes what the last timed step computed (the loss and the model it leaves behind) as DIR/<name>.npy.
+``--full`` adds every other measurement, each in passes of its own after the timed region:
+  host         - issue_ms_per_step (one step call into an empty queue) and the optimiser tail.
+  range, streams - the range sentinel of the fp16x2 arithmetic and the stream census.
+  full_width   - the same step in bf16x3 and on the exact-fp32 MFMA kernels (cfg2, one GPU).
+  dp           - data-parallel runs: the N = 1 reference, per-bucket all-reduce times, what RCCL reported.
   roofline     - the dominant kernel class (by summed device time): algorithmic FLOPs of its launches
                  divided by their summed HIP-event durations.  Taken in a second, instrumented pass of the same K
                  steps (event records around every launch would perturb `value`); `kernels` lists every class.
@@ -713,6 +720,39 @@ def build_workload(cfg, B, S, device, rank, graph=False):
     return model, opt, step, step
 
 
+DUMP_SAMPLE = 1 << 22          # parameters / gradients: 4 Mi values each of the ~42 M (16 MB apiece as float32)
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, model, loss, cfg):
+    """What a caller of the timed step holds after its last call, as float32 / float64 .npy files in ``out_dir``: the loss
+    (float64), the parameters and their gradients (one fixed, seeded sample of positions in the concatenation of all parameters
+    in ``named_parameters`` order, the same positions for both), every floating-point buffer (BatchNorm running statistics,
+    whole) and, for cfg4, the pseudo masks the step trained on.  Inputs, weights and dropout seeds are fixed by the arguments,
+    so two builds run with the same arguments can be compared file for file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    params = [p for _, p in model.named_parameters()]
+    flat = torch.cat([p.detach().reshape(-1) for p in params])
+    grad = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])
+    n = flat.numel()
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=min(n, DUMP_SAMPLE)))
+    idx_dev = torch.from_numpy(idx).to(flat.device)
+    arrays = {"loss": np.asarray(float(loss.item()), dtype=np.float64),
+              "params_sample": flat[idx_dev].float().cpu().numpy(),
+              "grads_sample": grad[idx_dev].float().cpu().numpy(),
+              "buffers": torch.cat([b.detach().reshape(-1).float() for _, b in model.named_buffers()
+                                    if b.is_floating_point()]).cpu().numpy()}
+    if cfg == "cfg4":
+        from weaklysuperviseddl_amd.TraditionalModel import generate_pseudo_masks
+        arrays["pseudo_masks"] = np.stack([m.cpu().numpy() if torch.is_tensor(m) else np.asarray(m)
+                                           for m in generate_pseudo_masks.last_masks]).astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"outputs of the last timed step -> {out_dir}: " + ", ".join(f"{k} {tuple(a.shape)}" for k, a in arrays.items()))
+
+
 def _plan_pending(opt):
     """Is the training step still going to record a launch plan (plan.PlannedTrainStep: neither recorded nor refused yet)?"""
     from weaklysuperviseddl_amd import plan as _plan
@@ -752,6 +792,13 @@ def main():
                          "roofline pass always runs like this)")
     ap.add_argument("--graph", type=int, default=None, help="1/0: force hipGraph replay of the training step on/off")
     ap.add_argument("--plan", type=int, default=None, help="0: every step eager (no launch-plan replay; the A/B partner)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every secondary measurement (host issue time, optimiser tail, range / stream census, full-width "
+                         "legs, data-parallel self-description, roofline pass, CAM / NCut legs, CPU baselines); the --no-* "
+                         "switches thin it out.  Off: set-up, warm-up, the timed steps and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, a seeded sample of "
+                         "the parameters and gradients, < 64 MB in all)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -800,7 +847,7 @@ def main():
     # single rank as well: the one-GPU rehearsal of the code path the 8-GPU run takes
     dp_on = world > 1 or (dist.is_available() and dist.is_initialized())
     n1_reference = None
-    if dp_on and cfg != "cfg4":
+    if args.full and dp_on and cfg != "cfg4":
         # the same process layout WITHOUT data parallelism: every rank steps its own replica on its own GPU, no collective
         # (the reducer, built right after, broadcasts rank 0's state over whatever these steps did) - the N = 1 figure this
         # run's scaling should be read against, measured on this node, in these processes
@@ -854,6 +901,9 @@ def main():
     if rank == 0:
         log(f"{ms_per_step:.2f} ms/step, {value:.1f} img/s")
     loss_val = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        # before anything else steps the model: the outputs are the timed path's own
+        dump_outputs(args.dump_outputs, model, loss, cfg)
 
     metric = ("SegmentationModel train img/s at B=16 256x256" if cfg == "cfg2"
               else f"SegmentationModel train img/s, {cfg} (B={B} {S}x{S})")
@@ -884,19 +934,20 @@ def main():
     # The wall time until K back-to-back steps are enqueued (enqueue_wall_ms_per_step, the figure of earlier rounds) also
     # contains the runtime's back-pressure: once the host is a few steps ahead, launches block until the GPU has drained
     # the queue, so a host that issues a step in 2.5 ms reads ~9 ms there (tools/plan_probe.py).
-    singles = []
-    for _ in range(7):
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        step()
-        singles.append(time.perf_counter() - t1)
-    sync_all(world)
-    singles.sort()
-    result["host"]["issue_ms_per_step"] = round(singles[len(singles) // 2] * 1e3, 3)
-    result["host"]["note"] = ("issue_ms_per_step: host time of one step call issued into an empty queue (median of 7, after the timed "
-                              "region); enqueue_wall_ms_per_step: wall time until the K timed steps were enqueued / K - includes the "
-                              "runtime's back-pressure once the host runs ahead of the GPU; cpu_s_per_step: process CPU time of all "
-                              "threads (the runtime's helper threads included)")
+    if args.full:
+        singles = []
+        for _ in range(7):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            step()
+            singles.append(time.perf_counter() - t1)
+        sync_all(world)
+        singles.sort()
+        result["host"]["issue_ms_per_step"] = round(singles[len(singles) // 2] * 1e3, 3)
+        result["host"]["note"] = ("issue_ms_per_step: host time of one step call issued into an empty queue (median of 7, after the timed "
+                                  "region); enqueue_wall_ms_per_step: wall time until the K timed steps were enqueued / K - includes the "
+                                  "runtime's back-pressure once the host runs ahead of the GPU; cpu_s_per_step: process CPU time of all "
+                                  "threads (the runtime's helper threads included)")
     from weaklysuperviseddl_amd import plan as _plan
     pst = next(iter(opt.__dict__.get("_wsdl_planned", {}).values()), None) if not use_graph else None
     result["host"]["launch_plan"] = (None if pst is None else
@@ -906,35 +957,36 @@ def main():
                                       "what": "steps after the second are ONE host call: the launches of an eager step recorded behind "
                                               "the C ABI (wsdl_plan_*), verified bit for bit against an eager step on a probe batch, "
                                               "then replayed from a C loop (weaklysuperviseddl_amd/plan.py)"})
-    # optimiser tail on the main stream (join with the weight-gradient / collective stream + Adam), in a short pass of its
-    # own: two event records per step are kept out of the timed region
-    opt.time_tail = True
-    for _ in range(5):
-        step()
-    opt.time_tail = False
-    tail = opt.tail_ms()
-    issue_by_rank = [result["host"]["issue_ms_per_step"]]
-    if dp_on and world > 1:
-        gathered = [None] * world
-        dist.all_gather_object(gathered, issue_by_rank[0])
-        issue_by_rank = gathered
-    result["host"]["issue_ms_per_step_by_rank"] = issue_by_rank
-    result["optimizer_tail_ms"] = None if tail is None else round(tail, 4)
-    torch.cuda.synchronize()
-    result["range"] = dict(ops.range_status(device),
-                           note="range sentinel of the fp16x2 arithmetic (one power-of-two scale per tensor): the BatchNorm kernels publish "
-                                "max|tensor| and the smallest non-zero channel maximum; worst_log2 = the largest log2 of "
-                                "their ratio over the last step's tensors, exceeded = some tensor beyond 2^25 (there conv_arith = 2, the "
-                                "range guard of the forward / input gradient, is the arithmetic to use: WSDL_RANGE_GUARD=auto, the default, "
-                                "switches it on for the steps that follow; the weight gradients scale every channel by its own power of two "
-                                "from step 0 - the maxima come from the BatchNorm kernels)",
-                           guard=__import__("weaklysuperviseddl_amd.optim", fromlist=["x"]).RANGE_GUARD[0],
-                           guard_active=bool(__import__("weaklysuperviseddl_amd.optim", fromlist=["x"]).RANGE_GUARD_ACTIVE[0]))
-    result["streams"] = ops.stream_census(device)
     if dp_on and dist.get_backend() != "nccl":
         result["config"]["rehearsal"] = ("ranks share the GPU(s) and the gradients travel over gloo through host memory: a rehearsal "
                                          "of the data-parallel code path, not a performance figure")
-    if dp_on:
+    if args.full:
+        # optimiser tail on the main stream (join with the weight-gradient / collective stream + Adam), in a short pass of its
+        # own: two event records per step are kept out of the timed region
+        opt.time_tail = True
+        for _ in range(5):
+            step()
+        opt.time_tail = False
+        tail = opt.tail_ms()
+        issue_by_rank = [result["host"]["issue_ms_per_step"]]
+        if dp_on and world > 1:
+            gathered = [None] * world
+            dist.all_gather_object(gathered, issue_by_rank[0])
+            issue_by_rank = gathered
+        result["host"]["issue_ms_per_step_by_rank"] = issue_by_rank
+        result["optimizer_tail_ms"] = None if tail is None else round(tail, 4)
+        torch.cuda.synchronize()
+        result["range"] = dict(ops.range_status(device),
+                               note="range sentinel of the fp16x2 arithmetic (one power-of-two scale per tensor): the BatchNorm kernels publish "
+                                    "max|tensor| and the smallest non-zero channel maximum; worst_log2 = the largest log2 of "
+                                    "their ratio over the last step's tensors, exceeded = some tensor beyond 2^25 (there conv_arith = 2, the "
+                                    "range guard of the forward / input gradient, is the arithmetic to use: WSDL_RANGE_GUARD=auto, the default, "
+                                    "switches it on for the steps that follow; the weight gradients scale every channel by its own power of two "
+                                    "from step 0 - the maxima come from the BatchNorm kernels)",
+                               guard=__import__("weaklysuperviseddl_amd.optim", fromlist=["x"]).RANGE_GUARD[0],
+                               guard_active=bool(__import__("weaklysuperviseddl_amd.optim", fromlist=["x"]).RANGE_GUARD_ACTIVE[0]))
+        result["streams"] = ops.stream_census(device)
+    if args.full and dp_on:
         per_rank = [dt_local / args.steps * 1e3]
         if world > 1:
             per_rank = [None] * world
@@ -974,7 +1026,7 @@ def main():
                                 "layer1, the last gradients of backward) cannot overlap backward: its time is the expected "
                                 "exposed communication per step; the others have the rest of backward (>= 1 ms each) to hide in"}
 
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # instrumented pass: same steps on every rank (the collectives must match), HIP events around every
         # conv / loss launch on the launch stream on rank 0 only
         # The timed region overlaps weight-gradient kernels (side stream) with the main chain; a kernel's own
@@ -990,7 +1042,7 @@ def main():
         torch.cuda.synchronize()
         ops.prof_enable(False)
         ops.OVERLAP_WGRAD[0] = not args.serial
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         kernels = []
         for c in range(ops.PROF_NCLASSES):
             n, ms, work, exe, byt = ops.prof_collect(c)
@@ -1084,7 +1136,7 @@ def main():
                                   "tflops_nominal": round(kk["work"] / (kk["total_ms"] * 1e-3) / 1e12, 3)} for kk in per_class]
             result["model_tflops_nominal"] = round(value * GFLOP_PER_IMG_256 * (S / 256) ** 2 / 1e3, 3)
 
-    if world == 1 and cfg == "cfg2" and not args.no_full_width and not args.opt and not use_graph:
+    if args.full and world == 1 and cfg == "cfg2" and not args.no_full_width and not args.opt and not use_graph:
         # the same step at full operand width, timed here (not only in builder runs under profiles/): bf16x3 = all 24 bits
         # of both operands on the 16-bit matrix core (six MFMAs per product), fp32 = the exact-fp32 MFMA kernels everywhere
         fw = {}
@@ -1109,12 +1161,12 @@ def main():
     if world > 1:
         dist.barrier()
     if rank == 0:
-        secondary = world == 1 and cfg == "cfg2"
+        secondary = args.full and world == 1 and cfg == "cfg2"
         if secondary and not args.no_cam:
             log("cam bench")
             result["cam"] = cam_bench(device, roofline=not args.no_roofline)
             result["ncut"] = ncut_bench(device)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # oracle twin of the extra loss terms of cfg3 / cfg5 (cfg4's CPU leg is the cfg2 step + the CAM legs)
             cpu_extra = None
             if cfg in ("cfg3", "cfg5"):

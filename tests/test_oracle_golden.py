@@ -68,20 +68,47 @@ def test_boundary_loss_and_grad(golden):
 
 def test_layercam_epilogue_both_variants(golden):
     """The epilogue is where an INTEGER output (the pseudo mask) is decided: the oracle equals the reference's bodies bit
-    for bit on identical activations / gradients (same torch ops in the same order), not merely within a tolerance."""
+    for bit on identical activations / gradients (same torch ops in the same order), not merely within a tolerance.
+
+    Two properties of the host enter those bits.  The thread count decides ATen's channel-sum order (16 threads split the
+    wide fixture's 14 x 14 maps differently, test_channel_sum_order_the_hip_epilogue_reproduces): pinned to 4, an order of
+    the fixtures.  alpha = 0.5 is `x ** 0.5` = MKL's vsSqrt, not correctly rounded, whose last bit depends on the CPU it runs
+    on (an AMD EPYC host gives 1 ulp off the fixtures in ~13 % of the values).  The modular epilogue raises its alpha = 1 CAM
+    to alpha as its last op, so its alpha = 0.5 CAM is checked bit for bit against the fixture's alpha = 1 CAM raised to 0.5
+    on this host, on every host.  Where this host's `** 0.5` is the fixtures' (that same pair says so), the alpha = 0.5
+    fixtures are matched bit for bit as well; elsewhere the notebook's `** 0.5`, which sits before a min-max and the
+    upsampling, may move its CAM by a few ulps of 1."""
+    from conftest import cpu_threads
+
+    def ulp_diff(a, b):
+        return int((a.contiguous().view(torch.int32).long() - b.contiguous().view(torch.int32).long()).abs().max())
+
+    def notebook_sqrt_case(got, want, host_is_fixtures):
+        if host_is_fixtures:
+            assert torch.equal(got, want)
+        else:
+            assert (got - want).abs().max().item() <= 2.0 ** -21, ((got - want).abs().max().item(), ulp_diff(got, want))
+
     g = golden("layercam")
-    for i in range(2):
-        acts = [T(g[f"act_layer3_{i}"]), T(g[f"act_layer4_{i}"])]
-        grads = [T(g[f"grad_layer3_{i}"]), T(g[f"grad_layer4_{i}"])]
-        for a in (0.5, 1.0, 2.0):
-            assert torch.equal(oracle.layercam_epilogue(acts, grads, (224, 224), a, "modular"), T(g[f"modular_cam_{i}_a{a}"]))
-        for a in (0.5, 2.0):
-            assert torch.equal(oracle.layercam_epilogue(acts, grads, (224, 224), a, "notebook"), T(g[f"notebook_cam_{i}_a{a}"]))
-    g = golden("layercam_wide")        # 300 / 600 channels: every level of torch's cascade summation
-    acts, grads = [T(g["act_layer3"]), T(g["act_layer4"])], [T(g["grad_layer3"]), T(g["grad_layer4"])]
-    assert torch.equal(oracle.layercam_epilogue(acts, grads, (224, 224), 1.0, "modular"), T(g["modular_cam_a1.0"]))
-    assert torch.equal(oracle.layercam_epilogue(acts, grads, (224, 224), 3.0, "modular"), T(g["modular_cam_a3.0"]))
-    assert torch.equal(oracle.layercam_epilogue(acts, grads, (224, 224), 0.5, "notebook"), T(g["notebook_cam_a0.5"]))
+    with cpu_threads(4):
+        sqrt_of_a1 = [T(g[f"modular_cam_{i}_a1.0"]).clamp(min=0.0) ** 0.5 for i in range(2)]
+        host_is_fixtures = all(torch.equal(s, T(g[f"modular_cam_{i}_a0.5"])) for i, s in enumerate(sqrt_of_a1))
+        for i in range(2):
+            acts = [T(g[f"act_layer3_{i}"]), T(g[f"act_layer4_{i}"])]
+            grads = [T(g[f"grad_layer3_{i}"]), T(g[f"grad_layer4_{i}"])]
+            for a in (1.0, 2.0):
+                assert torch.equal(oracle.layercam_epilogue(acts, grads, (224, 224), a, "modular"), T(g[f"modular_cam_{i}_a{a}"]))
+            assert torch.equal(oracle.layercam_epilogue(acts, grads, (224, 224), 0.5, "modular"), sqrt_of_a1[i])
+            assert ulp_diff(sqrt_of_a1[i], T(g[f"modular_cam_{i}_a0.5"])) <= (0 if host_is_fixtures else 1)
+            assert torch.equal(oracle.layercam_epilogue(acts, grads, (224, 224), 2.0, "notebook"), T(g[f"notebook_cam_{i}_a2.0"]))
+            notebook_sqrt_case(oracle.layercam_epilogue(acts, grads, (224, 224), 0.5, "notebook"), T(g[f"notebook_cam_{i}_a0.5"]),
+                               host_is_fixtures)
+        g = golden("layercam_wide")        # 300 / 600 channels: every level of torch's cascade summation
+        acts, grads = [T(g["act_layer3"]), T(g["act_layer4"])], [T(g["grad_layer3"]), T(g["grad_layer4"])]
+        assert torch.equal(oracle.layercam_epilogue(acts, grads, (224, 224), 1.0, "modular"), T(g["modular_cam_a1.0"]))
+        assert torch.equal(oracle.layercam_epilogue(acts, grads, (224, 224), 3.0, "modular"), T(g["modular_cam_a3.0"]))
+        notebook_sqrt_case(oracle.layercam_epilogue(acts, grads, (224, 224), 0.5, "notebook"), T(g["notebook_cam_a0.5"]),
+                           host_is_fixtures)
 
 
 def _cascade_rows(x):

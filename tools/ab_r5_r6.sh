@@ -22,5 +22,5 @@ for c in cfg3 cfg5; do
   run r6 . --no-cam --config $c --steps 10 --warmup 3
 done
 run r5 _r5tree --steps 10
-run r6 . --steps 10
+run r6 . --full --steps 10
 } 2>&1 | tee gpurun_out/r6/ab_r5_r6.txt
