@@ -435,6 +435,37 @@ int wsdl_lovasz_softmax_fwd_bwd(const float* probas, const int64_t* labels, floa
                                 int H, int W, int classes_all, long long ignore_label, void* ws, size_t ws_bytes,
                                 wsdl_stream_t stream);
 
+/* ---- dense-CRF refinement of pseudo masks (csrc/crf.hip) -------------------------------------------------------
+ * apply_dense_crf(img_np, cam_np) of the notebook pipeline (TraditionalModel/AlternatingDirectionCutLoss.py:183-204, called
+ * at :558 on the LayerCAM thresholded at :527-530): pydensecrf DenseCRF2D(W, H, 2) with
+ *   unary      -log(clip(clip([1 - cam, cam], 1e-8, 1), 1e-5, 1))       (np.clip + unary_from_softmax),
+ *   Gaussian   features (x/sxy, y/sxy), sxy = 1, PottsCompatibility(2)                     (addPairwiseGaussian defaults),
+ *   bilateral  features (x/sxy, y/sxy, r/srgb, g/srgb, b/srgb), sxy = 50, srgb = 5, Potts(10),
+ *   both DIAG_KERNEL, NORMALIZE_SYMMETRIC, inference(5), argmax over the labels (ties -> label 0).
+ * The filter is the permutohedral lattice (Adams et al. 2010) as densecrf builds it; the oracle is tests/crf_oracle.py
+ * (parity with pydensecrf itself is not verified).  rgb: (B,H,W,3) uint8 (the notebook's
+ * (img*255).astype(uint8)); cam (B,H,W) fp32 with values below cam_thresh set to 0 (pass -INFINITY for none), or an
+ * explicit unary (B,2,H,W) fp32 instead (cam = NULL).  mask (B,H,W) uint8 {0,1}; q (optional, (B,2,H,W)) the final Q.
+ * n_labels must be 2 (WSDL_EINVAL otherwise).  All images of the batch go through every launch: (lattice build + normaliser)
+ * x 2 terms + n_iter x 2 x (splat + d+1 blurs + slice); no float atomics - bitwise reproducible and independent of B.
+ * Coordinates of lattice keys are 16-bit fields: images up to ~4700 pixels on a side at sxy = 1 (WSDL_EINVAL beyond).
+ * The workspace (wsdl_dense_crf_workspace) also serves the two diagnostic entry points below. */
+size_t wsdl_dense_crf_workspace(int B, int H, int W, int n_labels);
+int wsdl_dense_crf(const uint8_t* rgb, const float* cam, const float* unary, float cam_thresh, int B, int H, int W,
+                   int n_labels, int n_iter, float gauss_sxy, float gauss_compat, float bil_sxy, float bil_srgb,
+                   float bil_compat, uint8_t* mask, float* q, void* ws, size_t ws_bytes, wsdl_stream_t stream);
+/* (B,3,H,W) fp32 image in [0,1] -> (B,H,W,3) uint8 by truncating x*255 (the notebook's astype(np.uint8), :551-556),
+ * clamped to [0, 255]. */
+int wsdl_dense_crf_quantize(const float* img, uint8_t* out, int B, int H, int W, wsdl_stream_t stream);
+/* Diagnostics of one feature set (bilateral = 0: Gaussian d = 2, 1: bilateral d = 5):
+ * lattice: per (pixel, vertex) the d integer key coordinates (keys, (B*H*W, d+1, d) int32) and the barycentric weight
+ * (bary, (B*H*W, d+1)); points (B) the number of lattice points of each image.
+ * filter: out = K~ in = n * Lattice(n * in), n = 1/sqrt(Lattice(1) + 1e-20), on (B,2,H,W) fp32. */
+int wsdl_dense_crf_lattice(const uint8_t* rgb, int B, int H, int W, int bilateral, float sxy, float srgb, int* keys,
+                           float* bary, int* points, void* ws, size_t ws_bytes, wsdl_stream_t stream);
+int wsdl_dense_crf_filter(const uint8_t* rgb, const float* in, float* out, int B, int H, int W, int n_labels, int bilateral,
+                          float sxy, float srgb, void* ws, size_t ws_bytes, wsdl_stream_t stream);
+
 /* nn.CrossEntropyLoss() on (B,C,H,W) logits and int64 (B,H,W) labels
  * (TraditionalModel/SegmentationModel.py:90,107; AlternatingDirectionCutLoss.py:789,699): mean over the pixels whose
  * label != ignore_index (PyTorch's default is -100; such pixels get zero loss and zero gradient).  Any other label

@@ -9,8 +9,15 @@ Mirrors reference TraditionalModel/AlternatingDirectionCutLoss.py:
     with the dynamic weight kept ON DEVICE (the reference does two ``.item()`` syncs per step);
     softmax is applied twice to X on the NCut branch, as the reference does (SURVEY.md D8);
   * ``train_model``             :684-707 - CE-only training epochs;
-  * ``run_alternating_training`` :791-818 - the outer loop: train <-> five chained refinement passes, in memory.
+  * ``run_alternating_training`` :791-818 - the outer loop: train <-> five chained refinement passes, in memory;
+  * ``apply_dense_crf``         :183-204 - pydensecrf's dense CRF with the notebook's parameters, on the device
+    (``ops.dense_crf``: permutohedral-lattice mean field, csrc/crf.hip); numpy in, numpy out;
+  * ``generate_crf_pseudo_masks`` :510-560 - the notebook's pseudo-mask loop batched: notebook LayerCAM, threshold,
+    8-bit quantisation and CRF on the device, ``{id}.png`` masks and min-max-normalised images as ``save_image`` writes them.
 """
+import os
+
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -221,3 +228,69 @@ def run_alternating_training(model, optimizer, dataset, num_alternations=10, epo
     if log and rank == 0:
         log("Alternating training and pseudo mask updates completed.")
     return history
+
+
+def apply_dense_crf(img_np, cam_np):
+    """Reference ``apply_dense_crf(img_np, cam_np)`` (AlternatingDirectionCutLoss.py:183-204): img_np (H,W,3) uint8 (any
+    strides), cam_np (H,W) float (taken as float32) -> refined mask (H,W) uint8 {0,1}.  Runs on the device
+    (``ops.dense_crf`` with the defaults the reference passes to pydensecrf); there is no CPU path."""
+    img_np = np.ascontiguousarray(img_np)
+    if img_np.dtype != np.uint8 or img_np.ndim != 3 or img_np.shape[2] != 3:
+        raise ops.WsdlError(f"apply_dense_crf: img_np must be (H,W,3) uint8, got {img_np.dtype} {img_np.shape}")
+    h, w = cam_np.shape
+    if img_np.shape[:2] != (h, w):
+        raise ops.WsdlError(f"apply_dense_crf: image {img_np.shape[:2]} and cam {(h, w)} differ in size")
+    dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    rgb = torch.from_numpy(img_np).to(dev).unsqueeze(0)
+    cam = torch.from_numpy(np.ascontiguousarray(cam_np, dtype=np.float32)).to(dev).unsqueeze(0)
+    return ops.dense_crf(rgb, cam)[0].cpu().numpy()
+
+
+def generate_crf_pseudo_masks(loader, layercam_gen, alpha=0.5, cam_thresh=0.2, out_root=".", max_images=None, write_png=True,
+                              device="cuda", keep_on_device=False):
+    """The notebook's pseudo-mask loop (AlternatingDirectionCutLoss.py:510-560), batched: per loader batch
+    ``(images, (labels, _))`` the LayerCAM of each image's label (``layercam_gen``; the notebook uses ``variant="notebook"``,
+    alpha 0.5), values below ``cam_thresh`` set to 0, the image quantised to 8 bits by truncation, the dense CRF
+    (``ops.dense_crf``) - all on the device.  ``write_png``: ``{id}.png`` masks under ``out_root/pseudo_masks`` and the
+    min-max-normalised images under ``out_root/images``, quantised as ``save_image`` does - what
+    ``PseudoSegmentationDataset`` reads.  ``max_images``: the notebook stops after 200 (None: the whole loader).
+    Returns (image_dir, mask_dir); ``.last_masks`` / ``.last_ids`` / ``.last_cams`` hold the masks (host uint8 arrays, device
+    tensors with ``keep_on_device`` and no PNGs), their ids and the unthresholded CAMs (device) - ``.last_images`` the device
+    images when no PNGs are written (``stage_handoff(torch.stack(last_images), last_masks)``)."""
+    from .PsuedoMasks import _to_device_async, _to_png_u8
+    mask_dir = os.path.join(out_root, "pseudo_masks")
+    image_dir = os.path.join(out_root, "images")
+    if write_png:
+        from PIL import Image
+        for d in (mask_dir, image_dir):
+            os.makedirs(d, exist_ok=True)
+    masks, ids, cams, images, img_id = [], [], [], [], 0
+    for imgs, (labels, _) in loader:
+        if max_images is not None and img_id >= max_images:
+            break
+        take = imgs.size(0) if max_images is None else min(imgs.size(0), max_images - img_id)
+        imgs_d = _to_device_async(imgs[:take], device).float()
+        labels_d = _to_device_async(torch.as_tensor(labels[:take]), device)
+        out = layercam_gen.generate_batch(imgs_d, alpha=alpha, class_idx=labels_d)
+        cam = (out[0] if isinstance(out, tuple) else out).contiguous()
+        m = ops.dense_crf(imgs_d, cam, cam_thresh=cam_thresh)
+        m_host = m if keep_on_device and not write_png else m.cpu().numpy()
+        for i in range(take):
+            gid = img_id + i
+            masks.append(m_host[i])
+            ids.append(gid)
+            cams.append(cam[i])
+            if not write_png:
+                images.append(imgs_d[i])
+            else:
+                mt = torch.from_numpy(m_host[i]).float().unsqueeze(0).expand(3, -1, -1)
+                Image.fromarray(_to_png_u8(mt)).save(os.path.join(mask_dir, f"{gid}.png"))
+                im = imgs_d[i].detach().cpu().clone()
+                im = (im - im.min()) / (im.max() - im.min())
+                Image.fromarray(_to_png_u8(im)).save(os.path.join(image_dir, f"{gid}.png"))
+        img_id += take
+    generate_crf_pseudo_masks.last_masks = masks
+    generate_crf_pseudo_masks.last_ids = ids
+    generate_crf_pseudo_masks.last_cams = cams
+    generate_crf_pseudo_masks.last_images = images
+    return image_dir, mask_dir

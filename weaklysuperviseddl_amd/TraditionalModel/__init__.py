@@ -6,7 +6,8 @@ from .SegmentationModel import (SegmentationModel, build_segmentation_model, tra
                                 train_segmentation_model)
 from .AlternatingDirectionCutLoss import (  # noqa: F401
     LocalNormalizedCutLoss, compute_affinities, refine_pseudo_mask, refine_pseudo_masks_batched, train_model,
-    refine_dataset, run_alternating_training, network_soft_prediction)
+    refine_dataset, run_alternating_training, network_soft_prediction, apply_dense_crf,
+    generate_crf_pseudo_masks)
 from .AlternatingDirectionBoundaryLoss import ConstrainToBoundaryLossSingle  # noqa: F401
 from .ExtraUtilities import compute_iou_and_acc  # noqa: F401
 from .SegmentationDataset import PseudoSegmentationDataset, InMemoryPseudoDataset  # noqa: F401

@@ -1964,6 +1964,87 @@ def lovasz_softmax(probas, labels, classes="present", per_image=False, ignore=No
     return _LovaszSoftmax.apply(probas, labels, classes == "all", ign)
 
 
+def _crf_rgb(images):
+    """(B,H,W,3) uint8 as it is, or (B,3,H,W) float in [0,1] quantised on the device (truncation of x*255)."""
+    if not images.is_cuda:
+        raise WsdlError(f"dense_crf: the HIP path needs a device tensor (got {images.device}); there is no CPU fallback")
+    if images.dtype == torch.uint8:
+        if images.dim() != 4 or images.shape[-1] != 3:
+            raise WsdlError(f"dense_crf: uint8 images must be (B,H,W,3), got {tuple(images.shape)}")
+        return images.contiguous()
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise WsdlError(f"dense_crf: float images must be (B,3,H,W), got {tuple(images.shape)}")
+    images = _dense(images, "images")
+    B, _, H, W = images.shape
+    out = torch.empty(B, H, W, 3, device=images.device, dtype=torch.uint8)
+    check(lib().wsdl_dense_crf_quantize(_p(images), _p(out), B, H, W, _stream()))
+    return out
+
+
+def _crf_ws(B, H, W, n_labels, device):
+    n = lib().wsdl_dense_crf_workspace(B, H, W, int(n_labels))
+    if n == 0:
+        raise WsdlError(f"dense_crf: unsupported geometry B={B} H={H} W={W} n_labels={n_labels} (n_labels must be 2)")
+    return workspace(n, device)
+
+
+def dense_crf(images, cam=None, cam_thresh=None, n_iter=5, gauss=(1, 2), bilateral=(50, 5, 10), return_q=False,
+              unary=None, n_labels=2):
+    """Dense-CRF refinement (reference AlternatingDirectionCutLoss.py:183-204, pydensecrf defaults): masks (B,H,W) uint8
+    [, Q (B,2,H,W) fp32].  images: (B,H,W,3) uint8 or (B,3,H,W) float in [0,1]; cam (B,H,W) fp32, values below
+    ``cam_thresh`` set to 0; or ``unary`` (B,2,H,W) fp32 instead of the cam.  gauss = (sxy, compat),
+    bilateral = (sxy, srgb, compat)."""
+    rgb = _crf_rgb(images)
+    B, H, W, _ = rgb.shape
+    if (cam is None) == (unary is None):
+        raise WsdlError("dense_crf: pass exactly one of cam and unary")
+    if cam is not None:
+        cam = _dense(cam, "cam")
+        if tuple(cam.shape) != (B, H, W):
+            raise WsdlError(f"dense_crf: cam {tuple(cam.shape)} does not match images (B,H,W) = {(B, H, W)}")
+    else:
+        unary = _dense(unary, "unary")
+        if tuple(unary.shape) != (B, int(n_labels), H, W):
+            raise WsdlError(f"dense_crf: unary {tuple(unary.shape)} is not (B,{n_labels},H,W) = {(B, n_labels, H, W)}")
+    ws = _crf_ws(B, H, W, n_labels, rgb.device)
+    mask = torch.empty(B, H, W, device=rgb.device, dtype=torch.uint8)
+    q = torch.empty(B, 2, H, W, device=rgb.device, dtype=torch.float32) if return_q else None
+    thr = float("-inf") if cam_thresh is None else float(cam_thresh)
+    check(lib().wsdl_dense_crf(_p(rgb), _p(cam), _p(unary), thr, B, H, W, int(n_labels), int(n_iter), float(gauss[0]),
+                               float(gauss[1]), float(bilateral[0]), float(bilateral[1]), float(bilateral[2]), _p(mask),
+                               _p(q), _p(ws), ws.numel(), _stream()))
+    return (mask, q) if return_q else mask
+
+
+def dense_crf_lattice(images, bilateral, sxy, srgb=1.0):
+    """Diagnostic: per-pixel lattice keys (B*H*W, d+1, d) int32, barycentric weights (B*H*W, d+1) and the number of
+    lattice points per image (B) of one feature set (bilateral=False: (x, y)/sxy; True: also rgb/srgb)."""
+    rgb = _crf_rgb(images)
+    B, H, W, _ = rgb.shape
+    d = 5 if bilateral else 2
+    keys = torch.empty(B * H * W, d + 1, d, device=rgb.device, dtype=torch.int32)
+    bary = torch.empty(B * H * W, d + 1, device=rgb.device, dtype=torch.float32)
+    points = torch.empty(B, device=rgb.device, dtype=torch.int32)
+    ws = _crf_ws(B, H, W, 2, rgb.device)
+    check(lib().wsdl_dense_crf_lattice(_p(rgb), B, H, W, int(bool(bilateral)), float(sxy), float(srgb), _p(keys), _p(bary),
+                                       _p(points), _p(ws), ws.numel(), _stream()))
+    return keys, bary, points
+
+
+def dense_crf_filter(images, values, bilateral, sxy, srgb=1.0, n_labels=2):
+    """Diagnostic: one normalised filter application K~ values, values (B,2,H,W) fp32."""
+    rgb = _crf_rgb(images)
+    B, H, W, _ = rgb.shape
+    values = _dense(values, "values")
+    if tuple(values.shape) != (B, int(n_labels), H, W):
+        raise WsdlError(f"dense_crf_filter: values {tuple(values.shape)} is not (B,{n_labels},H,W)")
+    out = torch.empty_like(values)
+    ws = _crf_ws(B, H, W, 2, rgb.device)
+    check(lib().wsdl_dense_crf_filter(_p(rgb), _p(values), _p(out), B, H, W, int(n_labels), int(bool(bilateral)), float(sxy),
+                                      float(srgb), _p(ws), ws.numel(), _stream()))
+    return out
+
+
 def pairwise_affinity_loss(preds, image, window=5, sigma_color=0.1, sigma_space=0.0, apply_softmax=True,
                            normalise=0, cache=None):
     """``cache``: ``pairwise_cache(image, window, sigma_color)`` when the image stays fixed over many evaluations."""
