@@ -420,6 +420,32 @@ int wsdl_scale_by_device_scalar(const float* x, const float* s, float* y, size_t
 int wsdl_copy_planes(const float* src, float* dst, int B, int C, int HW, long long src_bs,
                      long long dst_bs, wsdl_stream_t stream);
 
+/* ---- BASNet saliency inference (csrc/basnet.hip; reference PretrainedBasnetModel/model/BASNet.py, RunInference.py) ----
+ * The network's convolutions are wsdl_conv2d_fwd with BatchNorm folded into scale / shift.  Its bridge and decoder
+ * convolutions carry a bias in front of their BatchNorm (nn.Conv2d default bias=True, BASNet.py:144-234):
+ * shift = beta + (bias - rm) * scale, scale = gamma / sqrt(rv + eps) (wsdl_bn_fold without the bias otherwise). */
+int wsdl_bn_fold_bias(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                      const float* bias, float eps, float* scale, float* shift, int C, wsdl_stream_t stream);
+/* nn.MaxPool2d(2, 2, ceil_mode=True) (BASNet.py:124,130; RefUnet pool1..4, :19-37): (B,C,H,W) -> (B,C,ceil(H/2),ceil(W/2)),
+ * the last window of an odd side clipped; NaN propagates as in ATen.  x_bs / y_bs: batch strides (channel slices of a wider
+ * tensor; 0 = dense). */
+int wsdl_maxpool2x2_ceil_fwd(const float* x, float* y, int B, int C, int H, int W, long long x_bs, long long y_bs,
+                             wsdl_stream_t stream);
+/* A side output: logits = Conv2d(Cin, 1, 3, padding=1)(x) + bias (+ residual), then (y non-NULL) y = sigmoid(bilinear
+ * up-sample by s of the logits) - outconv{b,6,5,4,3,2,1} + upscore{6,5,4,3,2} + F.sigmoid (BASNet.py:245-251,323-344);
+ * with residual = outconv1's logits and s = 1 it is RefUnet's tail, conv_d0(d1) + x (:96-100).  x (B,Cin,h,wd) with batch
+ * stride x_bs (0 = dense); w (1,Cin,3,3) and bias (1) as the module holds them; residual optional (B,1,h,wd); logits
+ * (B,1,h,wd) REQUIRED (outconv1's are RefUnet's input); y optional (B,1,h*s,wd*s), batch stride y_bs (0 = dense).  The
+ * up-sample is wsdl_bilinear_fwd's arithmetic (identical bits); sigmoid = 0 writes the up-sampled logits instead.  Each
+ * pixel's dot product is summed in a fixed order: bitwise reproducible and independent of B.  Two launches. */
+int wsdl_side_output(const float* x, long long x_bs, const float* w, const float* bias, const float* residual, int B,
+                     int Cin, int h, int wd, int s, float* logits, float* y, long long y_bs, int sigmoid,
+                     wsdl_stream_t stream);
+/* RunInference.py's norm_pred (:36-40) per image, then (pred * 255).astype(np.uint8) (:77-83): out[b] = trunc(255 *
+ * (d - min_b) / (max_b - min_b + 1e-8)) in float32 with contraction off, in ATen's order.  d (B,HW) fp32 with batch stride
+ * d_bs (0 = dense; e.g. output #1 of a (B,1,H,W) tensor), out (B,HW) uint8.  One workgroup per image, two passes. */
+int wsdl_saliency_u8(const float* d, long long d_bs, uint8_t* out, int B, int HW, wsdl_stream_t stream);
+
 /* ---- losses --------------------------------------------------------------------------------- */
 size_t wsdl_reduce_workspace(void);
 /* lovasz_softmax(probas, labels, classes, per_image=False, ignore) - the optional loss of train_segmentation_model

@@ -18,6 +18,14 @@ _MEAN = torch.tensor([0.485, 0.456, 0.406]).view(3, 1, 1)
 _STD = torch.tensor([0.229, 0.224, 0.225]).view(3, 1, 1)
 
 
+def image_to_tensor(image, size=(256, 256)):
+    """PIL RGB image -> (3,H,W) float32: resize(BILINEAR), ToTensor, ImageNet normalise (transforms.Resize on a PIL image,
+    ToTensor, Normalize of the reference's pipelines)."""
+    image = image.resize((size[1], size[0]), Image.BILINEAR)
+    img = torch.from_numpy(np.asarray(image, dtype=np.uint8).copy()).permute(2, 0, 1).float().div(255.0)
+    return (img - _MEAN) / _STD
+
+
 class PseudoSegmentationDataset(Dataset):
     def __init__(self, img_dir, mask_dir, transform=False, return_name=False, size=(256, 256)):
         self.img_dir, self.mask_dir = img_dir, mask_dir
@@ -29,12 +37,8 @@ class PseudoSegmentationDataset(Dataset):
         return len(self.image_list)
 
     def joint_transform(self, image, mask):
-        w_h = (self.size[1], self.size[0])
-        image = image.resize(w_h, Image.BILINEAR)
-        mask = mask.resize(w_h, Image.NEAREST)
-        img = torch.from_numpy(np.asarray(image, dtype=np.uint8).copy()).permute(2, 0, 1).float().div(255.0)
-        img = (img - _MEAN) / _STD
-        return img, torch.as_tensor(np.array(mask), dtype=torch.long)
+        mask = mask.resize((self.size[1], self.size[0]), Image.NEAREST)
+        return image_to_tensor(image, self.size), torch.as_tensor(np.array(mask), dtype=torch.long)
 
     def __getitem__(self, idx):
         image = Image.open(os.path.join(self.img_dir, self.image_list[idx])).convert("RGB")

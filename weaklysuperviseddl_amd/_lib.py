@@ -80,6 +80,10 @@ SIGNATURES = {
     "wsdl_dense_crf_quantize": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "wsdl_dense_crf_lattice": (_i, [_vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wsdl_dense_crf_filter": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _sz, _vp]),
+    "wsdl_bn_fold_bias": (_i, [_vp] * 5 + [_f, _vp, _vp, _i, _vp]),
+    "wsdl_maxpool2x2_ceil_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _ll, _ll, _vp]),
+    "wsdl_side_output": (_i, [_vp, _ll, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _ll, _i, _vp]),
+    "wsdl_saliency_u8": (_i, [_vp, _ll, _vp, _i, _i, _vp]),
     "wsdl_pairwise_affinity_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _sz, _vp]),
     "wsdl_pairwise_cache_bytes": (_sz, [_i, _i, _i, _i]),
     "wsdl_pairwise_cache": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),

@@ -11,27 +11,15 @@
 // so forward and backward are ONE sweep over the in-bounds window: image and (softmaxed) predictions
 // are staged once per 32x8 tile (+halo) in LDS, 20 B/px of HBM reads + 8 B/px of gradient writes.
 #include "common.h"
+#include "bilinear.h"
 
 #include <algorithm>
 
 namespace {
 
 // ------------------------------------------------------------------------------- bilinear
-struct Lerp {
-    int i0, i1;
-    float l0, l1;
-};
-__device__ __forceinline__ Lerp src_index(int o, float scale, int in) {
-    float s = scale * ((float)o + 0.5f) - 0.5f;
-    if (s < 0.f) s = 0.f;
-    Lerp r;
-    r.i0 = (int)s;
-    if (r.i0 > in - 1) r.i0 = in - 1;
-    r.i1 = r.i0 + (r.i0 < in - 1 ? 1 : 0);
-    r.l1 = s - (float)r.i0;
-    r.l0 = 1.f - r.l1;
-    return r;
-}
+using wsdl::Lerp;
+using wsdl::src_index;
 
 __global__ void bilinear_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int C, int h, int w,
                                     int H, int W, long long y_bs, int planes) {
@@ -42,10 +30,7 @@ __global__ void bilinear_fwd_kernel(const float* __restrict__ x, float* __restri
         float* yp = y + (long long)b * y_bs + (long long)c * H * W;
         for (int o = blockIdx.x * blockDim.x + threadIdx.x; o < H * W; o += gridDim.x * blockDim.x) {
             const int oh = o / W, ow = o - oh * W;
-            const Lerp a = src_index(oh, sh, h), bb = src_index(ow, sw, w);
-            const float top = bb.l0 * xp[a.i0 * w + bb.i0] + bb.l1 * xp[a.i0 * w + bb.i1];
-            const float bot = bb.l0 * xp[a.i1 * w + bb.i0] + bb.l1 * xp[a.i1 * w + bb.i1];
-            yp[o] = a.l0 * top + a.l1 * bot;
+            yp[o] = wsdl::bilinear_at(xp, oh, ow, sh, sw, h, w);
         }
     }
 }

@@ -703,9 +703,10 @@ def prep_weights_multi(entries, lookup_only=False):
 
 
 def conv2d_fwd(x, wt_fwd, wshape, stride, pad, dil, scale=None, shift=None, residual=None, relu=False, out=None,
-               x_amax=None, want_amax=False):
+               x_amax=None, want_amax=False, y_amax=None):
     """``x_amax``: the input's amax scalar (looked up / computed when None and the split kernels may run);
-    ``want_amax``: publish max|out| as ``out._wsdl_amax`` (the output feeds another convolution directly)."""
+    ``want_amax``: publish max|out| as ``out._wsdl_amax`` (the output feeds another convolution directly);
+    ``y_amax``: an existing slot to publish into instead of a fresh one (producers of the slices of one buffer share it)."""
     if x_amax is None:
         x_amax = amax_of(x, _split_kc(x.shape[1], wshape[2] * wshape[3]))
     x, x_bs = _planes(x, "x")
@@ -730,7 +731,8 @@ def conv2d_fwd(x, wt_fwd, wshape, stride, pad, dil, scale=None, shift=None, resi
             raise WsdlError("conv2d: residual shape mismatch")
     nws = _ws_bytes("wsdl_conv2d_igemm_workspace", B, Cin, H, W, Cout, kh, kw, stride, pad, dil, 0)
     ws = workspace(nws, x.device) if nws else None
-    y_amax = amax_slot(x.device) if (want_amax and CONV_ARITH[0] == 1) else None
+    if y_amax is None:
+        y_amax = amax_slot(x.device) if (want_amax and CONV_ARITH[0] == 1) else None
     check(lib().wsdl_conv2d_fwd(_p(x), _p(wt_fwd), _p(out), B, Cin, H, W, Cout, kh, kw, stride, pad, dil,
                                 _p(scale), _p(shift), _p(residual), int(relu), x_bs, y_bs, res_bs, _p(x_amax), _p(y_amax),
                                 _p(ws), ws.numel() if ws is not None else 0, _stream()))
@@ -1010,6 +1012,17 @@ def bn_fold(bn_weight, bn_bias, running_mean, running_var, eps):
     shift = torch.empty_like(scale)
     check(lib().wsdl_bn_fold(_p(_dense(bn_weight)), _p(_dense(bn_bias)), _p(_dense(running_mean)),
                              _p(_dense(running_var)), float(eps), _p(scale), _p(shift), Cc, _stream()))
+    return scale, shift
+
+
+def bn_fold_bias(bn_weight, bn_bias, running_mean, running_var, conv_bias, eps):
+    """bn_fold for a convolution that carries a bias in front of its BatchNorm: shift = beta + (bias - rm) * scale."""
+    Cc = bn_weight.numel()
+    scale = torch.empty(Cc, device=bn_weight.device, dtype=torch.float32)
+    shift = torch.empty_like(scale)
+    check(lib().wsdl_bn_fold_bias(_p(_dense(bn_weight)), _p(_dense(bn_bias)), _p(_dense(running_mean)),
+                                  _p(_dense(running_var)), _p(_dense(conv_bias)), float(eps), _p(scale), _p(shift), Cc,
+                                  _stream()))
     return scale, shift
 
 
@@ -1898,6 +1911,76 @@ def class_logit_head(h, weight, bias=None, class_idx=None):
 
 def bilinear_resize(x, size):
     return _Bilinear.apply(x, int(size[0]), int(size[1]))
+
+
+def _out_planes(out):
+    """(out, batch stride) of an output whose images are dense planes (a channel slice): written in place, never copied."""
+    t, bs = _planes(out, "out")
+    if t.data_ptr() != out.data_ptr():
+        raise WsdlError("output tensor: images must be dense channel planes (a channel slice of an NCHW tensor)")
+    return t, bs
+
+
+def bilinear_into(x, out):
+    """bilinear_resize of dense x written into ``out`` (B,C,H,W), which may be a channel slice of a wider tensor."""
+    x = _dense(x, "x")
+    B, Cc, h, w = x.shape
+    out, y_bs = _out_planes(out)
+    if out.shape[0] != B or out.shape[1] != Cc:
+        raise WsdlError("bilinear_into: output does not match the input's batch / channels")
+    check(lib().wsdl_bilinear_fwd(_p(x), _p(out), B, Cc, h, w, int(out.shape[2]), int(out.shape[3]), y_bs, _stream()))
+    return out
+
+
+def max_pool_2x2_ceil(x, out=None):
+    """nn.MaxPool2d(2, 2, ceil_mode=True); x and ``out`` may be channel slices of wider tensors."""
+    x, x_bs = _planes(x, "x")
+    B, Cc, H, W = x.shape
+    shape = (B, Cc, (H + 1) // 2, (W + 1) // 2)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    if tuple(out.shape) != shape:
+        raise WsdlError(f"max_pool_2x2_ceil: output {tuple(out.shape)} is not {shape}")
+    out, y_bs = _out_planes(out)
+    check(lib().wsdl_maxpool2x2_ceil_fwd(_p(x), _p(out), B, Cc, H, W, x_bs, y_bs, _stream()))
+    return out
+
+
+def side_output(x, weight, bias, s, residual=None, sigmoid=True, out=None, logits=None):
+    """A 3x3 Cin -> 1 convolution with bias (+ residual (B,1,h,w)), then sigmoid(bilinear up-sample by s): BASNet's side outputs
+    and RefUnet's tail (wsdl_side_output).  Returns (y (B,1,h*s,w*s), logits (B,1,h,w)); sigmoid=False: y holds the up-sampled
+    logits."""
+    x, x_bs = _planes(x, "x")
+    B, Cin, h, w = x.shape
+    if tuple(weight.shape) != (1, Cin, 3, 3) or bias is None or bias.numel() != 1:
+        raise WsdlError(f"side_output: weight {tuple(weight.shape)} / bias is not a (1,{Cin},3,3) conv with a bias")
+    if residual is not None:
+        residual = _dense(residual, "residual")
+        if tuple(residual.shape) != (B, 1, h, w):
+            raise WsdlError("side_output: residual must be (B,1,h,w)")
+    if logits is None:
+        logits = torch.empty(B, 1, h, w, device=x.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(B, 1, h * s, w * s, device=x.device, dtype=torch.float32)
+    if tuple(out.shape) != (B, 1, h * s, w * s):
+        raise WsdlError("side_output: bad output shape")
+    out, y_bs = _out_planes(out)
+    check(lib().wsdl_side_output(_p(x), x_bs, _p(_dense(weight, "weight")), _p(_dense(bias, "bias")), _p(residual), B, Cin, h, w,
+                                 int(s), _p(logits), _p(out), y_bs, int(bool(sigmoid)), _stream()))
+    return out, logits
+
+
+def saliency_u8(d):
+    """(B,1,H,W) or (B,H,W) fp32 -> (B,H,W) uint8: norm_pred per image, then (p * 255).astype(uint8) (wsdl_saliency_u8)."""
+    if d.dim() == 4:
+        if d.shape[1] != 1:
+            raise WsdlError("saliency_u8: one channel expected")
+        d = d[:, 0]
+    d = _dense(d, "d")
+    B, H, W = d.shape
+    out = torch.empty(B, H, W, device=d.device, dtype=torch.uint8)
+    check(lib().wsdl_saliency_u8(_p(d), H * W, _p(out), B, H * W, _stream()))
+    return out
 
 
 DROPOUT_SEED_OFFSET = [0]      # dp.init_distributed: a different offset on every rank, so replicas draw different masks
