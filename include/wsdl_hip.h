@@ -446,6 +446,21 @@ int wsdl_side_output(const float* x, long long x_bs, const float* w, const float
  * d_bs (0 = dense; e.g. output #1 of a (B,1,H,W) tensor), out (B,HW) uint8.  One workgroup per image, two passes. */
 int wsdl_saliency_u8(const float* d, long long d_bs, uint8_t* out, int B, int HW, wsdl_stream_t stream);
 
+/* ---- fully-supervised baseline: segmentation metrics (csrc/seg_metrics.hip) ----
+ * The per-batch counts of evaluate_model (reference FullySupervisedModel/SupervisedModel.py:44-83): preds = argmax over C
+ * of logits (B,C,H,W) fp32 with torch.argmax's ties (the first maximum wins; NaN is the maximum, the first NaN wins),
+ * compared with labels (B,H,W) int64.  counts: one row of 3C+1 int64 on the device,
+ *   [0,C)   inter[c]  = #(pred = c and label = c)
+ *   [C,2C)  npred[c]  = #(pred = c)
+ *   [2C,3C) nlabel[c] = #(label = c)
+ *   [3C]    correct   = #(pred = label)
+ * A label outside [0,C) matches no class: it counts in npred of the predicted class and as a wrong pixel, as the
+ * reference's boolean masks do.  union[c] = npred[c] + nlabel[c] - inter[c].  accumulate = 0 zeroes the row first (a
+ * memset), 1 adds to it (one launch).  Integer counts only (block-local LDS histograms, one atomic per bin per block):
+ * exact and independent of the schedule.  2 <= C <= 64 and B * HW < 2^32, other values are refused. */
+int wsdl_seg_counts(const float* logits, const int64_t* labels, long long* counts, int B, int C, int HW, int accumulate,
+                    wsdl_stream_t stream);
+
 /* ---- losses --------------------------------------------------------------------------------- */
 size_t wsdl_reduce_workspace(void);
 /* lovasz_softmax(probas, labels, classes, per_image=False, ignore) - the optional loss of train_segmentation_model

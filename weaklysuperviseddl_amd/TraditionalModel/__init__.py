@@ -9,5 +9,5 @@ from .AlternatingDirectionCutLoss import (  # noqa: F401
     refine_dataset, run_alternating_training, network_soft_prediction, apply_dense_crf,
     generate_crf_pseudo_masks)
 from .AlternatingDirectionBoundaryLoss import ConstrainToBoundaryLossSingle  # noqa: F401
-from .ExtraUtilities import compute_iou_and_acc  # noqa: F401
+from .ExtraUtilities import compute_iou_and_acc, download_data, load_split_data  # noqa: F401
 from .SegmentationDataset import PseudoSegmentationDataset, InMemoryPseudoDataset  # noqa: F401

@@ -1983,6 +1983,27 @@ def saliency_u8(d):
     return out
 
 
+def seg_counts(logits, labels, out=None, accumulate=False):
+    """argmax over C of (B,C,H,W) fp32 logits vs (B,H,W) int64 labels -> int64 (3C+1,) on the device:
+    [inter[C] | npred[C] | nlabel[C] | correct] (wsdl_seg_counts; 2 <= C <= 64).  ``out``: a dense int64 (3C+1,) row to
+    write (``accumulate``: add to it instead of overwriting).  No host synchronisation."""
+    if logits.dim() != 4 or logits.dtype != torch.float32:
+        raise WsdlError("seg_counts: logits must be (B,C,H,W) float32")
+    B, Cc, H, W = logits.shape
+    if tuple(labels.shape) != (B, H, W) or labels.dtype != torch.int64:
+        raise WsdlError(f"seg_counts: labels must be int64 {(B, H, W)}, got {labels.dtype} {tuple(labels.shape)}")
+    logits = _dense(logits, "logits")
+    _req(labels, "labels", torch.int64)
+    labels = labels if labels.is_contiguous() else labels.contiguous()
+    if out is None:
+        out = torch.empty(3 * Cc + 1, device=logits.device, dtype=torch.int64)
+        accumulate = False
+    elif out.dtype != torch.int64 or out.numel() != 3 * Cc + 1 or not out.is_contiguous() or out.device != logits.device:
+        raise WsdlError("seg_counts: out must be a dense int64 row of 3C+1 on the logits' device")
+    check(lib().wsdl_seg_counts(_p(logits), _p(labels), _p(out), B, Cc, H * W, int(bool(accumulate)), _stream()))
+    return out
+
+
 DROPOUT_SEED_OFFSET = [0]      # dp.init_distributed: a different offset on every rank, so replicas draw different masks
 
 
