@@ -461,6 +461,36 @@ int wsdl_saliency_u8(const float* d, long long d_bs, uint8_t* out, int B, int HW
 int wsdl_seg_counts(const float* logits, const int64_t* labels, long long* counts, int B, int C, int HW, int accumulate,
                     wsdl_stream_t stream);
 
+/* ---- Pillow's 8-bit resampling on the device (csrc/pil_resize.hip) ----
+ * Image.resize(size, BILINEAR | BICUBIC) on 8-bit "RGB" / "L" images (box=None, reducing_gap=None), bit for bit: the
+ * Resize((224, 224), BICUBIC) of the Oxford-IIIT Pet reader (reference TraditionalModel/ExtraUtilities.py:24-41) and the
+ * Resize((256, 256)) (BILINEAR) of the stage-2 transforms (TraditionalModel/SegmentationDataset.py:19-28).  Pillow works in
+ * integer fixed point (22 fractional bits, int32 sums, the horizontal pass first and rounded to uint8), so equality is exact.
+ * The filter values are Pillow's Image.BILINEAR / Image.BICUBIC. */
+#define WSDL_PIL_BILINEAR 2
+#define WSDL_PIL_BICUBIC 3
+/* HOST ONLY (no device is touched): the resampling table of one axis, computed in double the way Pillow computes it.
+ * *ksize = (int)ceil(support * max(in / out, 1)) * 2 + 1 is always written.  bounds / kk may both be NULL (a size query);
+ * else bounds[2 * i] = xmin, bounds[2 * i + 1] = xmax of output index i (out pairs) and kk[i * ksize + x] the int32
+ * coefficient of source index xmin + x (zero for x >= xmax).  1 <= in, out <= 16384 and the two filters above; other
+ * values are refused. */
+int wsdl_pil_coeffs(int in, int out, int filter, int* ksize, int* bounds, int* kk);
+/* One image of a batched resize: h x w x C interleaved uint8 (np.asarray of a PIL image) at src + src_off; htab / vtab:
+ * offsets in int32 units into `tables` of the tables (w -> out_w) and (h -> out_h), each laid out as
+ * [ksize | bounds (2 * out) | kk (out * ksize)]. */
+typedef struct {
+    long long src_off;
+    int h, w;
+    int htab, vtab;
+} wsdl_pil_image_t;
+/* N images of different sizes -> planar (N, C, out_h, out_w): uint8 in dst_u8 and / or float32 lut[c * 256 + u8] in dst_f32
+ * (lut: C x 256 floats, e.g. ToTensor's u8 / 255 or ToTensor + Normalize; required with dst_f32).  src, images, tables and
+ * the outputs are device memory.  One launch, no workspace, no atomics; results do not depend on N.  C in {1, 3} and
+ * 1 <= out_h, out_w <= 16384, other values are refused; the images' own sides are checked by wsdl_pil_coeffs when their
+ * tables are made. */
+int wsdl_pil_resize_u8(const uint8_t* src, const wsdl_pil_image_t* images, const int* tables, int N, int C, int out_h,
+                       int out_w, uint8_t* dst_u8, float* dst_f32, const float* lut, wsdl_stream_t stream);
+
 /* ---- losses --------------------------------------------------------------------------------- */
 size_t wsdl_reduce_workspace(void);
 /* lovasz_softmax(probas, labels, classes, per_image=False, ignore) - the optional loss of train_segmentation_model

@@ -34,7 +34,7 @@ def compute_iou_and_acc(pred_mask, true_mask):
 class OxfordIIITPetLocal(Dataset):
     """torchvision ``OxfordIIITPet(root, split, target_types=("category", "segmentation"))`` over an existing tree, with
     the reference's transforms.  ``load_u8(i)`` is the same item before the float conversion: (image (224,224,3) uint8,
-    category, trimap (224,224) uint8) - what the device-resident dataset keeps."""
+    category, trimap (224,224) uint8) - what the device-resident dataset keeps; ``load_raw(i)`` is it before the resize."""
 
     def __init__(self, root, split="test"):
         if split not in ("trainval", "test"):
@@ -67,6 +67,20 @@ class OxfordIIITPetLocal(Dataset):
         img = np.array(image, dtype=np.uint8)
         tri = np.array(mask, copy=True)
         if img.shape != (SIZE[0], SIZE[1], 3) or tri.shape != SIZE or tri.dtype != np.uint8:
+            raise ValueError(f"{self._segs[idx]}: an 8-bit single-channel trimap expected (mode {mask.mode})")
+        return img, self._labels[idx], tri
+
+    def load_raw(self, idx):
+        """The item before any resize: (image H x W x 3 uint8 after ``convert("RGB")``, category, trimap h x w uint8) - what
+        the device resize (``ops.pil_resize``, BICUBIC to 224x224) turns into ``load_u8``'s item.  A trimap that is not mode
+        "L" (Pillow forces NEAREST for "P" and "1") is resized on the host as ``load_u8`` does and handed on at 224x224,
+        which the device resize passes through unchanged."""
+        img = np.array(Image.open(self._images[idx]).convert("RGB"), dtype=np.uint8)
+        mask = Image.open(self._segs[idx])
+        if mask.mode != "L":
+            mask = mask.resize((SIZE[1], SIZE[0]), Image.BICUBIC)
+        tri = np.array(mask, copy=True)
+        if img.ndim != 3 or img.shape[2] != 3 or tri.ndim != 2 or tri.dtype != np.uint8:
             raise ValueError(f"{self._segs[idx]}: an 8-bit single-channel trimap expected (mode {mask.mode})")
         return img, self._labels[idx], tri
 

@@ -157,7 +157,7 @@ def nearest_resize_index(n_out, n_in, device):
 
 
 @torch.no_grad()
-def stage_handoff(images, masks, size=(256, 256), device="cuda"):
+def stage_handoff(images, masks, size=(256, 256), device="cuda", *, exact=False):
     """In-memory stage-1 -> stage-2 hand-off: what ``PseudoSegmentationDataset`` (SegmentationDataset.py:19-38) would
     read back from the PNGs ``generate_pseudo_masks`` writes (PsuedoMasks.py:68-74), without the file system.
 
@@ -165,12 +165,25 @@ def stage_handoff(images, masks, size=(256, 256), device="cuda"):
       images256 (N,3,H,W) float32 on ``device``: min-max rescale per image, 8-bit quantisation (save_image),
                 bilinear resize (PIL BILINEAR up-sampling == align_corners=False; HIP kernel), /255, ImageNet normalise;
       masks256  (N,H,W) uint8 {0,255}: x255 (save_image of a 0/1 tensor), NEAREST resize.
+    ``exact=True``: the 8-bit image goes through ``ops.pil_resize`` (Pillow's integer BILINEAR) instead of the float
+    up-sampler: images256 then EQUALS the PNG round trip (the default is equal to one 8-bit level).
     """
     x = torch.as_tensor(images).to(device=device, dtype=torch.float32)
     lo = x.amin(dim=(1, 2, 3), keepdim=True)
     hi = x.amax(dim=(1, 2, 3), keepdim=True)
     q = ((x - lo) / (hi - lo)).mul(255).add(0.5).clamp(0, 255).floor()          # uint8 values, kept as float
     H, W = size
+    if exact:
+        # the 8-bit planes through Pillow's own fixed-point BILINEAR (ops.pil_resize: planar input = N * 3 one-channel
+        # images), ToTensor + Normalize from a table: equal to the PNG round trip, not only to one 8-bit level
+        from .SegmentationDataset import _normalize_table
+        N, _, h, w = q.shape
+        planes = q.to(torch.uint8).contiguous()
+        desc = ops.pil_describe([(h, w)] * (3 * N), [i * h * w for i in range(3 * N)], (H, W), ops.PIL_BILINEAR, planes.device)
+        u8, _ = ops.pil_resize(planes.view(-1), desc, 1, (H, W))
+        table = _normalize_table().to(planes.device)
+        img = torch.stack([table[c][u8.view(N, 3, H, W)[:, c].to(torch.int32)] for c in range(3)], dim=1)
+        return img.contiguous(), _handoff_masks(masks, H, W, device)
     # PIL resamples 8-bit images in two passes - columns first, then rows - and rounds to 8 bits after each
     if q.shape[-1] != W:
         q = ops.bilinear_resize(q.contiguous(), (q.shape[-2], W)).add(0.5).floor().clamp(0, 255)
@@ -178,6 +191,10 @@ def stage_handoff(images, masks, size=(256, 256), device="cuda"):
         q = ops.bilinear_resize(q.contiguous(), (H, W)).add(0.5).floor().clamp(0, 255)
     mean, std = _norm_constants(device)
     img = (q / 255.0 - mean) / std
+    return img.contiguous(), _handoff_masks(masks, H, W, device)
+
+
+def _handoff_masks(masks, H, W, device):
     if isinstance(masks, (list, tuple)) and len(masks) and torch.is_tensor(masks[0]):
         m = torch.stack(list(masks)).to(device)                        # device masks (keep_on_device): no host round trip
     else:
@@ -187,4 +204,4 @@ def stage_handoff(images, masks, size=(256, 256), device="cuda"):
         ih = nearest_resize_index(H, m.shape[-2], device)
         iw = nearest_resize_index(W, m.shape[-1], device)
         m = m[:, ih][:, :, iw]
-    return img.contiguous(), m.contiguous()
+    return m.contiguous()

@@ -26,6 +26,25 @@ def image_to_tensor(image, size=(256, 256)):
     return (img - _MEAN) / _STD
 
 
+def _normalize_table():
+    """ToTensor + Normalize per 8-bit value and channel, (3, 256) float32, computed with torch on the CPU exactly as
+    ``image_to_tensor`` computes a pixel - so the device resize's float epilogue writes the reference's floats."""
+    v = torch.arange(256, dtype=torch.uint8).float().div(255.0)
+    return ((v.view(1, 256) - _MEAN.view(3, 1)) / _STD.view(3, 1)).contiguous()
+
+
+def images_to_tensor_device(images, size=(256, 256), device="cuda"):
+    """A list of PIL RGB images or H x W x 3 uint8 arrays -> (N,3,H,W) float32 on ``device``, equal to
+    ``torch.stack([image_to_tensor(i, size) for i in images])``: BILINEAR resize (Pillow's, bit for bit), ToTensor and
+    Normalize in one launch (``ops.pil_resize``) - the ``inference_transform`` of the notebook."""
+    from .. import ops
+    arrays = [np.asarray(i.convert("RGB") if isinstance(i, Image.Image) else i, dtype=np.uint8) for i in images]
+    out = torch.empty(len(arrays), 3, size[0], size[1], dtype=torch.float32, device=device)
+    ops.pil_resize_arrays(arrays, size, ops.PIL_BILINEAR, channels=3, device=device, out_f32=out,
+                          lut=_normalize_table().to(device))
+    return out
+
+
 class PseudoSegmentationDataset(Dataset):
     def __init__(self, img_dir, mask_dir, transform=False, return_name=False, size=(256, 256)):
         self.img_dir, self.mask_dir = img_dir, mask_dir
@@ -59,6 +78,24 @@ class InMemoryPseudoDataset(Dataset):
         assert images.shape[0] == masks.shape[0] and images.shape[-2:] == masks.shape[-2:]
         self.images, self.masks = images, masks.to(torch.uint8)
         self.names = list(names) if names is not None else [f"{i}.png" for i in range(images.shape[0])]
+
+    @classmethod
+    def from_dirs(cls, img_dir, mask_dir, size=(256, 256), device="cuda", chunk=64):
+        """The items of ``PseudoSegmentationDataset(img_dir, mask_dir, transform=True, return_name=True)`` read once: the
+        images are decoded on the host and resized + normalised on the device (``images_to_tensor_device``, ``chunk``
+        images per launch); the masks go through PIL's NEAREST on the host, which is cheap and exact."""
+        files = PseudoSegmentationDataset(img_dir, mask_dir, transform=False, return_name=True, size=size)
+        n = len(files)
+        images = torch.empty(n, 3, size[0], size[1], dtype=torch.float32, device=device)
+        masks = torch.empty(n, size[0], size[1], dtype=torch.uint8)
+        names = []
+        for s in range(0, n, chunk):
+            items = [files[i] for i in range(s, min(n, s + chunk))]
+            images[s:s + len(items)] = images_to_tensor_device([it[0] for it in items], size, device)
+            for j, (_, mask, name) in enumerate(items):
+                masks[s + j] = torch.from_numpy(np.array(mask.resize((size[1], size[0]), Image.NEAREST), dtype=np.uint8))
+                names.append(name)
+        return cls(images, masks.to(device), names)
 
     def __len__(self):
         return self.images.shape[0]

@@ -8,6 +8,7 @@ import os
 
 import threading
 
+import numpy as np
 import torch
 
 from ._lib import lib, check, WsdlError
@@ -2002,6 +2003,175 @@ def seg_counts(logits, labels, out=None, accumulate=False):
         raise WsdlError("seg_counts: out must be a dense int64 row of 3C+1 on the logits' device")
     check(lib().wsdl_seg_counts(_p(logits), _p(labels), _p(out), B, Cc, H * W, int(bool(accumulate)), _stream()))
     return out
+
+
+# ---- Pillow's 8-bit resampling (csrc/pil_resize.hip) -------------------------------------------------------------------
+PIL_BILINEAR, PIL_BICUBIC = 2, 3            # Pillow's Image.BILINEAR / Image.BICUBIC
+PIL_MAX_SIDE = 16384
+# one image of a batch: wsdl_pil_image_t
+PIL_IMAGE_DTYPE = np.dtype([("src_off", np.int64), ("h", np.int32), ("w", np.int32), ("htab", np.int32), ("vtab", np.int32)])
+
+
+def _pil_filter(filter):
+    """'bilinear' / 'bicubic' or Pillow's enum value; any other value is refused by the library (wsdl_pil_coeffs)."""
+    f = {"bilinear": PIL_BILINEAR, "bicubic": PIL_BICUBIC}.get(filter, filter)
+    if isinstance(f, bool) or not isinstance(f, (int, np.integer)):
+        raise WsdlError(f"pil_resize: filter {filter!r}: 'bilinear' (2) or 'bicubic' (3)")
+    return int(f)
+
+
+def pil_coeffs(n_in, n_out, filter):
+    """Pillow's resampling table of one axis (wsdl_pil_coeffs; host only): (ksize, bounds (n_out, 2) int32 = (xmin, xmax),
+    coefficients (n_out, ksize) int32 with 22 fractional bits)."""
+    f = _pil_filter(filter)
+    ksize = C.c_int(0)
+    check(lib().wsdl_pil_coeffs(int(n_in), int(n_out), f, C.byref(ksize), None, None))
+    bounds = np.empty((int(n_out), 2), dtype=np.int32)
+    kk = np.empty((int(n_out), ksize.value), dtype=np.int32)
+    ip = C.POINTER(C.c_int)
+    check(lib().wsdl_pil_coeffs(int(n_in), int(n_out), f, C.byref(ksize), bounds.ctypes.data_as(ip), kk.ctypes.data_as(ip)))
+    return ksize.value, bounds, kk
+
+
+class PilTables:
+    """The resampling tables of one device in one int32 arena, uploaded once per (in, out, filter) (Pet has a few hundred
+    distinct side lengths, a table is ~10-50 KB).  ``offset`` returns a table's place in ``arena`` in int32 units.  When the
+    arena grows the old contents are copied on the current stream, so offsets handed out earlier stay valid."""
+
+    def __init__(self, device, capacity=1 << 20):
+        self.device = torch.device(device)
+        self.arena = torch.empty(capacity, dtype=torch.int32, device=self.device)
+        self.used = 0
+        self._offsets = {}
+        self._lock = threading.Lock()
+
+    def offset(self, n_in, n_out, filter):
+        key = (int(n_in), int(n_out), int(filter))
+        off = self._offsets.get(key)
+        if off is not None:
+            return off
+        ksize, bounds, kk = pil_coeffs(*key)
+        table = np.concatenate([np.array([ksize], dtype=np.int32), bounds.ravel(), kk.ravel()])
+        with self._lock:
+            off = self._offsets.get(key)
+            if off is not None:
+                return off
+            if self.used + table.size > self.arena.numel():
+                grown = torch.empty(max(2 * self.arena.numel(), self.used + table.size), dtype=torch.int32, device=self.device)
+                grown[:self.used].copy_(self.arena[:self.used])
+                self.arena = grown
+            off = self.used
+            self.arena[off:off + table.size].copy_(torch.from_numpy(table))
+            self.used += table.size
+            self._offsets[key] = off
+        return off
+
+
+_PIL_TABLES = {}
+
+
+def pil_tables(device):
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise WsdlError(f"pil_resize: the HIP path needs a device (got {device}); there is no CPU fallback")
+    key = device.index if device.index is not None else _cur_device()
+    if key not in _PIL_TABLES:
+        _PIL_TABLES[key] = PilTables(torch.device("cuda", key))
+    return _PIL_TABLES[key]
+
+
+def pil_describe(shapes, offsets, size, filter, device):
+    """The descriptor rows (PIL_IMAGE_DTYPE) of images of ``shapes`` [(h, w), ...] at byte ``offsets`` of the source buffer,
+    for a resize to ``size`` = (out_h, out_w); their tables are made and uploaded on first use."""
+    f = _pil_filter(filter)
+    out_h, out_w = (int(v) for v in size)
+    tables = pil_tables(device)
+    desc = np.empty(len(shapes), dtype=PIL_IMAGE_DTYPE)
+    for i, ((h, w), off) in enumerate(zip(shapes, offsets)):
+        desc[i] = (off, h, w, tables.offset(w, out_w, f), tables.offset(h, out_h, f))
+    return desc
+
+
+def pil_resize(src, desc, channels, size, *, out=None, out_f32=None, lut=None):
+    """Pillow's ``Image.resize(size, BILINEAR | BICUBIC)`` of N 8-bit images of different sizes in one launch
+    (wsdl_pil_resize_u8), bit for bit.
+
+    src       1-D uint8 device buffer: the images as ``np.asarray(pil_image)`` yields them (h x w x C interleaved), each at
+              the byte offset its descriptor names;
+    desc      the descriptors of ``pil_describe`` (which also fixes the filter): a numpy array (checked against ``src``
+              and uploaded) or a device uint8 tensor that holds N of them (8-byte aligned);
+    channels  1 or 3; size = (out_h, out_w).
+    Returns the planar (N, C, out_h, out_w) uint8 (``out``, allocated when neither output is given) and / or writes
+    ``out_f32`` = ``lut[c, u8]`` (float32, same shape; ``lut`` (C, 256) float32 on the device).  Returns ``(out, out_f32)``.
+    Current stream, no host synchronisation on results, no CPU fallback."""
+    _req(src, "pil_resize: src", torch.uint8)
+    if src.dim() != 1 or not src.is_contiguous():
+        raise WsdlError("pil_resize: src must be a dense 1-D uint8 buffer")
+    Cc = int(channels)
+    if Cc not in (1, 3):
+        raise WsdlError(f"pil_resize: channels = {channels}, supported 1 and 3")
+    out_h, out_w = (int(v) for v in size)
+    if not (1 <= out_h <= PIL_MAX_SIDE and 1 <= out_w <= PIL_MAX_SIDE):
+        raise WsdlError(f"pil_resize: size {tuple(size)}: side lengths 1..{PIL_MAX_SIDE}")
+    itemsize = PIL_IMAGE_DTYPE.itemsize
+    if isinstance(desc, np.ndarray):
+        if desc.dtype != PIL_IMAGE_DTYPE or desc.ndim != 1 or len(desc) == 0:
+            raise WsdlError("pil_resize: desc must be a non-empty 1-D array of PIL_IMAGE_DTYPE")
+        end = desc["src_off"] + desc["h"].astype(np.int64) * desc["w"] * Cc
+        if (desc["src_off"] < 0).any() or (desc["h"] < 1).any() or (desc["w"] < 1).any() or end.max() > src.numel():
+            raise WsdlError("pil_resize: a descriptor points outside src")
+        n = len(desc)
+        desc = torch.from_numpy(np.ascontiguousarray(desc).view(np.uint8)).to(src.device)
+    else:
+        _req(desc, "pil_resize: desc", torch.uint8)
+        if desc.dim() != 1 or not desc.is_contiguous() or desc.numel() == 0 or desc.numel() % itemsize or desc.data_ptr() % 8:
+            raise WsdlError("pil_resize: a device desc must be dense uint8, 8-byte aligned, a multiple of %d bytes" % itemsize)
+        n = desc.numel() // itemsize
+    shape = (n, Cc, out_h, out_w)
+    if out is None and out_f32 is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=src.device)
+    for t, name, dt in ((out, "out", torch.uint8), (out_f32, "out_f32", torch.float32)):
+        if t is not None:
+            _req(t, "pil_resize: " + name, dt)
+            if t.numel() != n * Cc * out_h * out_w or not t.is_contiguous() or t.device != src.device:
+                raise WsdlError(f"pil_resize: {name} must be a dense {dt} tensor of {shape} on src's device")
+    if out_f32 is not None:
+        if lut is None:
+            raise WsdlError("pil_resize: out_f32 needs lut, the (C, 256) float32 table")
+        _req(lut, "pil_resize: lut")
+        if tuple(lut.shape) != (Cc, 256) or not lut.is_contiguous() or lut.device != src.device:
+            raise WsdlError(f"pil_resize: lut must be a dense float32 {(Cc, 256)} on src's device")
+    tables = pil_tables(src.device)
+    check(lib().wsdl_pil_resize_u8(_p(src), _p(desc), _p(tables.arena), n, Cc, out_h, out_w, _p(out), _p(out_f32),
+                                   _p(lut) if out_f32 is not None else None, _stream()))
+    return out, out_f32
+
+
+def pil_pack(arrays, channels):
+    """[H x W x C (or H x W for C = 1) uint8 arrays] -> (one flat uint8 array, shapes, byte offsets): the source layout of
+    ``pil_resize``."""
+    Cc = int(channels)
+    shapes, offsets, total = [], [], 0
+    flat = []
+    for a in arrays:
+        a = np.asarray(a)
+        ok = a.dtype == np.uint8 and (a.ndim == 3 and a.shape[2] == Cc or a.ndim == 2 and Cc == 1)
+        if not ok:
+            raise WsdlError(f"pil_resize: an H x W x {Cc} uint8 array expected, got {a.dtype} {a.shape}")
+        shapes.append((a.shape[0], a.shape[1]))
+        offsets.append(total)
+        flat.append(np.ascontiguousarray(a).reshape(-1))
+        total += flat[-1].size
+    return (np.concatenate(flat) if flat else np.empty(0, np.uint8)), shapes, offsets
+
+
+def pil_resize_arrays(arrays, size, filter, channels=3, device="cuda", *, out=None, out_f32=None, lut=None):
+    """``pil_resize`` of a list of host arrays: packed, copied and resized in one launch."""
+    flat, shapes, offsets = pil_pack(arrays, channels)
+    if not shapes:
+        raise WsdlError("pil_resize: no images")
+    desc = pil_describe(shapes, offsets, size, filter, device)
+    return pil_resize(torch.from_numpy(flat).to(device), desc, channels, size, out=out, out_f32=out_f32, lut=lut)
 
 
 DROPOUT_SEED_OFFSET = [0]      # dp.init_distributed: a different offset on every rank, so replicas draw different masks
