@@ -506,6 +506,50 @@ int wsdl_lovasz_softmax_fwd_bwd(const float* probas, const int64_t* labels, floa
                                 int H, int W, int classes_all, long long ignore_label, void* ws, size_t ws_bytes,
                                 wsdl_stream_t stream);
 
+/* ---- the rest of LossFunctions/Lovasz-Softmax_Loss.py (csrc/lovasz_seg.hip) ----
+ * One segmented pipeline for the hinge and for Lovasz-softmax over a class list: ONE device-wide stable radix sort
+ * (rocPRIM) of 64-bit keys (segment id above the order-preserving bits of the error), ONE scan of the packed counts, one
+ * pass with the Jaccard differences in the fp32 arithmetic of wsdl_lovasz_softmax_fwd_bwd.  Bitwise reproducible; ties
+ * are ranked by pixel index.  Refused on the host: a segment (image, or batch) of 2^24 pixels or more, 2^30 pixels or
+ * 2^32 sorted elements or more in all, a null pointer.
+ *
+ * lovasz_hinge(logits, labels, per_image=True, ignore=None) - LossFunctions/Lovasz-Softmax_Loss.py:71-119 (lovasz_hinge
+ * :71-84, lovasz_hinge_flat :87-104, flatten_binary_scores :107-119; lovasz_grad :11-23).  logits (B,H,W) fp32
+ * (channels = 1) or (B,2,H,W) (channels = 2: the binary logit is plane 1 - plane 0), labels int64 (B,H,W) in {0, 1,
+ * ignore_label}.  e = 1 - logit * (2 label - 1); *loss = mean over the segments (per_image: the images; else the one
+ * batch) of <relu(e) sorted descending, Jaccard gradient of the sorted labels>; an image without a valid pixel is a zero
+ * term that counts in the mean.  dlogits (optional, the logits' shape) = d loss / d logits: -sign g_k / #segments where
+ * e > 0, exactly 0 elsewhere and on ignored pixels; with two planes +d on plane 1 and -d on plane 0. */
+size_t wsdl_lovasz_hinge_workspace(int B, int H, int W, int per_image);
+int wsdl_lovasz_hinge_fwd_bwd(const float* logits, const int64_t* labels, float* loss, float* dlogits, int B, int channels,
+                              int H, int W, int per_image, long long ignore_label, void* ws, size_t ws_bytes,
+                              wsdl_stream_t stream);
+/* lovasz_softmax(probas, labels, classes=[...], per_image, ignore) - LossFunctions/Lovasz-Softmax_Loss.py:146-211
+ * (lovasz_softmax :146-161, lovasz_softmax_flat :164-192, flatten_probas :195-211) for an explicit class list: classes is
+ * a HOST array of n_classes (1..1024) channel numbers; every entry is a term whether or not the class occurs; *loss = mean
+ * over the entries, per_image: the mean over the images of that (an image without a valid pixel is a zero term - the
+ * reference returns an empty tensor there).  C = 1 (one sigmoid map) takes exactly one entry c and compares channel 0 with
+ * labels == c.  dprobas optional, (B,C,H,W); channels that are not listed get zeros. */
+size_t wsdl_lovasz_softmax_classes_workspace(int B, int C, int H, int W, int n_classes, int per_image);
+int wsdl_lovasz_softmax_classes_fwd_bwd(const float* probas, const int64_t* labels, float* loss, float* dprobas, int B, int C,
+                                        int H, int W, const int* classes, int n_classes, int per_image, long long ignore_label,
+                                        void* ws, size_t ws_bytes, wsdl_stream_t stream);
+/* The counts of iou_binary / iou - LossFunctions/Lovasz-Softmax_Loss.py:26-65: preds, labels int64 (B,HW); per image
+ * (per_image = 1; else one row for the batch) and class c < C, counts[(img * C + c) * 2 + 0] = #(label = c and pred = c),
+ * [.. + 1] = #(label = c or (pred = c and label != ignore_label)); int64 on the device, overwritten.  The divisions, EMPTY,
+ * the mean and the x 100 are the host's (Python floats in the reference). */
+int wsdl_iou_counts(const int64_t* preds, const int64_t* labels, long long* counts, int B, int HW, int C, int per_image,
+                    long long ignore_label, wsdl_stream_t stream);
+/* binary_xloss / StableBCELoss - LossFunctions/Lovasz-Softmax_Loss.py:122-140: logits fp32 and EITHER labels int64 (t = the
+ * label, pixels with label == ignore_label left out: binary_xloss) OR targets fp32 (every element counts: StableBCELoss), n
+ * each; *loss = mean over those pixels of max(x,0) - x t + log(1 + exp(-|x|)) (NaN without one);
+ * dlogits (optional) = its derivative, NOT yet divided by the count; *inv_count = 1 / count (0 without a valid pixel).
+ * xloss :213-217 is wsdl_softmax_ce_fwd_bwd with ignore_index 255; isnan / mean :221-243 are host helpers.
+ * ws: wsdl_reduce_workspace() bytes. */
+int wsdl_binary_xloss_fwd_bwd(const float* logits, const int64_t* labels, const float* targets, float* loss, float* dlogits,
+                              float* inv_count, long long n, long long ignore_label, void* ws, size_t ws_bytes,
+                              wsdl_stream_t stream);
+
 /* ---- dense-CRF refinement of pseudo masks (csrc/crf.hip) -------------------------------------------------------
  * apply_dense_crf(img_np, cam_np) of the notebook pipeline (TraditionalModel/AlternatingDirectionCutLoss.py:183-204, called
  * at :558 on the LayerCAM thresholded at :527-530): pydensecrf DenseCRF2D(W, H, 2) with
@@ -653,7 +697,8 @@ int wsdl_softmax_bwd(const float* y, const float* dy, float* dx, int B, int C, i
  *     their own; wsdl_set_option is refused while any thread records;
  *   - the caller keeps every buffer the sequence touched alive and at its address for the plan's lifetime, and anything
  *     that varies from replay to replay on the device (wsdl_adam_step's step_dev, wsdl_dropout_fwd's counter);
- *   - wsdl_lovasz_softmax_fwd_bwd (rocPRIM launches kernels of its own) poisons a recording: wsdl_plan_end fails;
+ *   - wsdl_lovasz_softmax_fwd_bwd, wsdl_lovasz_hinge_fwd_bwd and wsdl_lovasz_softmax_classes_fwd_bwd (rocPRIM launches
+ *     kernels of its own) poison a recording: wsdl_plan_end fails;
  *   - wsdl_plan_mark(tag) cuts the plan into segments: wsdl_plan_replay_segment(plan, k) replays segment k (0 .. marks),
  *     so the host can do its own work (a gradient collective) at the places it did while recording. */
 int wsdl_plan_begin(void);

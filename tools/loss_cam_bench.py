@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Timing of the HBM-bound hot-path kernels at BASELINE config sizes: pairwise-affinity loss (cfg3 / cfg5),
-LayerCAM epilogue (cfg1), cross-entropy, Adam.  Prints microseconds and GB/s against the algorithmic bytes of
+LayerCAM epilogue (cfg1), cross-entropy, the Lovasz losses, Adam.  Prints microseconds and GB/s against the algorithmic bytes of
 SURVEY.md 8(d)."""
 import os
 import sys
@@ -49,6 +49,19 @@ def main():
         us = timeit(lambda: ops.lovasz_softmax(pl, lab))
         print(f"{'lovasz-softmax fwd+bwd ' + name:44s} {us:9.1f} {24 * px / us / 1e3:9.1f}  24 B/px (8 probas + 8 int64 label + 8 grad; "
               "2 sorts of (key, index) pairs + 2 scans in between)")
+        us = timeit(lambda: ops.lovasz_softmax(pl, lab, per_image=True))
+        print(f"{'lovasz-softmax per image (loop) ' + name:44s} {us:9.1f} {24 * px / us / 1e3:9.1f}  24 B/px ({2 * B} sorts of one image each)")
+        # the segmented pipeline (csrc/lovasz_seg.hip): one device-wide sort with the images / list entries as segments
+        hz = preds[:, 1].contiguous().requires_grad_()
+        us = timeit(lambda: ops.lovasz_hinge(hz, lab, per_image=False))
+        print(f"{'lovasz-hinge whole batch fwd+bwd ' + name:44s} {us:9.1f} {16 * px / us / 1e3:9.1f}  16 B/px (4 logit + 8 int64 label + 4 grad; "
+              "1 sort of (64-bit key, index) pairs + 1 scan)")
+        us = timeit(lambda: ops.lovasz_hinge(hz, lab, per_image=True))
+        print(f"{'lovasz-hinge per image fwd+bwd ' + name:44s} {us:9.1f} {16 * px / us / 1e3:9.1f}  16 B/px ({B} segments in 1 sort)")
+        us = timeit(lambda: ops.lovasz_hinge(lg, lab, per_image=True))
+        print(f"{'lovasz-hinge per image, two planes ' + name:44s} {us:9.1f} {24 * px / us / 1e3:9.1f}  24 B/px (8 logits + 8 int64 label + 8 grad)")
+        us = timeit(lambda: ops.lovasz_softmax(pl, lab, classes=[0, 1], per_image=True))
+        print(f"{'lovasz-softmax [0, 1] per image ' + name:44s} {us:9.1f} {24 * px / us / 1e3:9.1f}  24 B/px ({2 * B} segments in 1 sort)")
     acts = [torch.relu(torch.randn(8, c, 14, 14, device=dev)) for c in (1024, 2048)]
     grads = [torch.randn(8, c, 14, 14, device=dev) * 1e-3 for c in (1024, 2048)]
     nbytes = sum(8 * a.numel() for a in acts) + 8 * 224 * 224 * 5

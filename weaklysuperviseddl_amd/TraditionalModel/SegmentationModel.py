@@ -321,8 +321,9 @@ def _one(device):
 
 def train_step(model, optimizer, images, masks, extra_loss=None, loss_fn="cross_entropy", criterion=None):
     """One training iteration; returns the (device) loss tensor, no host synchronisation.  ``loss_fn``: 'cross_entropy' or
-    'lovasz_softmax' (reference SegmentationModel.py:65,103-107); ``criterion``: a reference-style loss object instead
-    (``resolve_criterion``).
+    'lovasz_softmax' (reference SegmentationModel.py:65,103-107), or 'lovasz_hinge': the binary Lovasz hinge of the
+    reference's loss file (LossFunctions/Lovasz-Softmax_Loss.py:71-104) on the logit difference z1 - z0, per image;
+    ``criterion``: a reference-style loss object instead (``resolve_criterion``).
 
     On the device, in train mode and outside data parallelism the iteration is issued as ONE host call from its third
     occurrence on (``plan.PlannedTrainStep``: the launches of an eager iteration recorded behind the C ABI, verified to
@@ -351,10 +352,12 @@ def _train_step_eager(model, optimizer, images, masks, extra_loss=None, loss_fn=
             loss = resolve_criterion(criterion)(outputs, masks)
         elif loss_fn == "lovasz_softmax":
             loss = ops.lovasz_softmax(ops.softmax_channels(outputs), masks.long(), classes="present", per_image=False, ignore=None)
+        elif loss_fn == "lovasz_hinge":
+            loss = ops.lovasz_hinge(outputs, masks.long(), per_image=True, ignore=None)      # two planes: z1 - z0 in the kernel
         elif loss_fn == "cross_entropy":
             loss = ops.cross_entropy(outputs, masks.long())
         else:
-            raise ValueError(f"loss_fn {loss_fn!r}: 'cross_entropy' or 'lovasz_softmax'")
+            raise ValueError(f"loss_fn {loss_fn!r}: 'cross_entropy', 'lovasz_softmax' or 'lovasz_hinge'")
         if extra_loss is not None:
             extra = extra_loss(outputs_x, images)
             if torch.is_tensor(extra) and extra.is_cuda and extra.dim() == 0 and loss.dim() == 0 and extra.dtype == loss.dtype:
@@ -446,7 +449,7 @@ def train_segmentation_model(loss_fn, run_id, lr=1e-4, num_epochs=10, batch_size
 
     Trains DeepLabV3-ResNet50 (``build_segmentation_model``) with Adam(lr) on the pseudo masks of run ``run_id`` -
     ``{out_root}/images_{run_id}`` / ``{out_root}/pseudo_masks_{run_id}``, what ``generate_pseudo_masks`` wrote - with
-    ``loss_fn`` 'cross_entropy' or 'lovasz_softmax'; batches of one image are skipped (:97-98), masks clamped to {0,1} (:100).
+    ``loss_fn`` 'cross_entropy', 'lovasz_softmax' or 'lovasz_hinge'; batches of one image are skipped (:97-98), masks clamped to {0,1} (:100).
 
     Where the reference's text cannot run, the working notebook decides: the reference builds the
     pseudo-mask dataset (:73-77) and then trains on ``load_split_data()`` (:80-83), whose items are not (image, mask)
@@ -457,8 +460,8 @@ def train_segmentation_model(loss_fn, run_id, lr=1e-4, num_epochs=10, batch_size
     device, an existing model to continue from."""
     from torch.utils.data import DataLoader
     from .SegmentationDataset import PseudoSegmentationDataset
-    if loss_fn not in ("cross_entropy", "lovasz_softmax"):
-        raise ValueError(f"loss_fn {loss_fn!r}: 'cross_entropy' or 'lovasz_softmax'")
+    if loss_fn not in ("cross_entropy", "lovasz_softmax", "lovasz_hinge"):
+        raise ValueError(f"loss_fn {loss_fn!r}: 'cross_entropy', 'lovasz_softmax' or 'lovasz_hinge'")
     import os as _os
     image_dir = _os.path.join(out_root, f"images_{run_id}")
     mask_dir = _os.path.join(out_root, f"pseudo_masks_{run_id}")

@@ -75,6 +75,12 @@ SIGNATURES = {
     "wsdl_softmax_ce_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _ll, _vp, _sz, _vp]),
     "wsdl_lovasz_softmax_workspace": (_sz, [_i, _i, _i, _i]),
     "wsdl_lovasz_softmax_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _ll, _vp, _sz, _vp]),
+    "wsdl_lovasz_hinge_workspace": (_sz, [_i, _i, _i, _i]),
+    "wsdl_lovasz_hinge_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _ll, _vp, _sz, _vp]),
+    "wsdl_lovasz_softmax_classes_workspace": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "wsdl_lovasz_softmax_classes_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _ll, _vp, _sz, _vp]),
+    "wsdl_iou_counts": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _ll, _vp]),
+    "wsdl_binary_xloss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _vp, _sz, _vp]),
     "wsdl_dense_crf_workspace": (_sz, [_i, _i, _i, _i]),
     "wsdl_dense_crf": (_i, [_vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _sz, _vp]),
     "wsdl_dense_crf_quantize": (_i, [_vp, _vp, _i, _i, _i, _vp]),

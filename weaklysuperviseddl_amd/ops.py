@@ -2225,17 +2225,169 @@ class _LovaszSoftmax(torch.autograd.Function):
         return dp * g, None, None, None
 
 
+_NO_LABEL = -(1 << 62)         # "ignore=None": a value no label has
+
+
+def _ignore(ignore):
+    return _NO_LABEL if ignore is None else int(ignore)
+
+
+class _LovaszSoftmaxClasses(torch.autograd.Function):
+    """lovasz_softmax with an explicit class list (reference Lovasz-Softmax_Loss.py:146-211): every (image or batch) x
+    (list entry) is a segment of ONE device-wide sort (csrc/lovasz_seg.hip)."""
+
+    @staticmethod
+    def forward(ctx, probas, labels, classes, per_image, ignore):
+        probas = _dense(probas, "probas")
+        labels = _req(labels, "labels", torch.int64).contiguous()
+        B, Cc, H, W = probas.shape
+        if tuple(labels.shape) != (B, H, W):
+            raise WsdlError(f"lovasz_softmax: labels {tuple(labels.shape)} do not match probas {tuple(probas.shape)}")
+        cls = (C.c_int * len(classes))(*classes)
+        loss = torch.empty((), device=probas.device, dtype=torch.float32)
+        dp = torch.empty_like(probas) if ctx.needs_input_grad[0] else None       # (a copy made dense above requires no grad)
+        ws = workspace(_ws_bytes("wsdl_lovasz_softmax_classes_workspace", B, Cc, H, W, len(classes), int(per_image)),
+                       probas.device)
+        check(lib().wsdl_lovasz_softmax_classes_fwd_bwd(_p(probas), _p(labels), _p(loss), _p(dp), B, Cc, H, W,
+                                                        C.cast(cls, C.c_void_p), len(classes), int(per_image), int(ignore),
+                                                        _p(ws), ws.numel(), _stream()))
+        ctx.save_for_backward(dp)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dp,) = ctx.saved_tensors
+        return dp * g, None, None, None, None
+
+
 def lovasz_softmax(probas, labels, classes="present", per_image=False, ignore=None):
-    """probas (B,C,H,W) class probabilities (or (B,H,W): one sigmoid map), labels (B,H,W)."""
-    if classes not in ("present", "all"):
-        raise WsdlError("lovasz_softmax: classes must be 'present' or 'all' (an explicit class list is not supported)")
+    """probas (B,C,H,W) class probabilities (or (B,H,W): one sigmoid map), labels (B,H,W).  ``classes``: 'present', 'all'
+    or a list of classes to average: every listed class is a term whether or not it occurs; with one sigmoid map (C = 1)
+    the list has exactly one entry c and channel 0 is compared with ``labels == c`` (a longer list: ValueError, as in the
+    reference).  Per image, an image whose pixels are all void is a zero term that counts in the mean (the reference
+    returns an empty tensor there)."""
     if probas.dim() == 3:
         probas = probas.unsqueeze(1)
-    ign = -(1 << 62) if ignore is None else int(ignore)
+    ign = _ignore(ignore)
+    if not isinstance(classes, str):
+        classes = [int(c) for c in classes]
+        if not classes:
+            raise WsdlError("lovasz_softmax: an empty class list")
+        if probas.shape[1] == 1 and len(classes) > 1:
+            raise ValueError("Sigmoid output possible only with 1 class")
+        return _LovaszSoftmaxClasses.apply(probas, labels, classes, bool(per_image), ign)
+    if classes not in ("present", "all"):
+        raise WsdlError("lovasz_softmax: classes must be 'present', 'all' or a list of classes")
     if per_image:
         vals = [_LovaszSoftmax.apply(probas[b:b + 1], labels[b:b + 1], classes == "all", ign) for b in range(probas.shape[0])]
         return torch.stack(vals).mean()
     return _LovaszSoftmax.apply(probas, labels, classes == "all", ign)
+
+
+class _LovaszHinge(torch.autograd.Function):
+    """lovasz_hinge(logits, labels, per_image, ignore) - reference Lovasz-Softmax_Loss.py:71-119; loss and d loss / d logits
+    in one call: one device-wide sort with the images as segments, one scan, one pass (csrc/lovasz_seg.hip)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, per_image, ignore):
+        logits = _dense(logits, "logits")
+        labels = _req(labels, "labels", torch.int64).contiguous()
+        if logits.dim() == 4 and logits.shape[1] == 2:
+            (B, _two, H, W), ch = logits.shape, 2
+        elif logits.dim() == 3:
+            (B, H, W), ch = logits.shape, 1
+        else:
+            raise WsdlError(f"lovasz_hinge: logits must be (B,H,W) or (B,2,H,W), got {tuple(logits.shape)}")
+        if tuple(labels.shape) != (B, H, W):
+            raise WsdlError(f"lovasz_hinge: labels {tuple(labels.shape)} do not match logits {tuple(logits.shape)}")
+        loss = torch.empty((), device=logits.device, dtype=torch.float32)
+        dl = torch.empty_like(logits) if ctx.needs_input_grad[0] else None
+        ws = workspace(_ws_bytes("wsdl_lovasz_hinge_workspace", B, H, W, int(per_image)), logits.device)
+        check(lib().wsdl_lovasz_hinge_fwd_bwd(_p(logits), _p(labels), _p(loss), _p(dl), B, ch, H, W, int(per_image),
+                                              int(ignore), _p(ws), ws.numel(), _stream()))
+        ctx.save_for_backward(dl)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dl,) = ctx.saved_tensors
+        return dl * g, None, None, None
+
+
+def lovasz_hinge(logits, labels, per_image=True, ignore=None):
+    """Binary Lovasz hinge: logits (B,H,W), or (B,2,H,W) whose binary logit is plane 1 - plane 0; labels (B,H,W) int64 in
+    {0, 1, ignore}.  Mean over the images (``per_image``) or one term for the batch; an image without a valid pixel is a
+    zero term with zero gradient that still counts in the mean."""
+    return _LovaszHinge.apply(logits, labels, bool(per_image), _ignore(ignore))
+
+
+def iou_counts(preds, labels, C, ignore=None, per_image=False):
+    """int64 (images, C, 2) on the device - images = B with ``per_image``, else 1: [..., 0] = #(label = c and pred = c),
+    [..., 1] = #(label = c or (pred = c and label != ignore)) (wsdl_iou_counts).  preds, labels int64 (B,H,W).  No host
+    synchronisation; ``iou_from_counts`` turns a host copy into the reference's numbers."""
+    _req(preds, "preds", torch.int64)
+    _req(labels, "labels", torch.int64)
+    if preds.dim() < 2 or preds.shape != labels.shape:
+        raise WsdlError(f"iou_counts: preds {tuple(preds.shape)} / labels {tuple(labels.shape)} must be equal (B,...) shapes")
+    preds, labels = preds.contiguous(), labels.contiguous()
+    B = preds.shape[0]
+    HW = preds.numel() // max(B, 1)
+    out = torch.empty((B if per_image else 1, int(C), 2), device=preds.device, dtype=torch.int64)
+    check(lib().wsdl_iou_counts(_p(preds), _p(labels), _p(out), B, HW, int(C), int(bool(per_image)), _ignore(ignore), _stream()))
+    return out
+
+
+def iou_from_counts(counts, EMPTY=1.0, ignore=None):
+    """Host arithmetic of the reference's ``iou`` (Lovasz-Softmax_Loss.py:46-65) on (images, C, 2) counts (anything
+    ``np.asarray`` takes): per class - the ``ignore`` class left out - the mean over the images of intersection / union as
+    Python floats, ``EMPTY`` where the union is 0; returns 100 x that as a float64 array."""
+    counts = np.asarray(counts)
+    ious = []
+    for c in range(counts.shape[1]):
+        if ignore is not None and c == ignore:
+            continue
+        per = [float(i) / float(u) if u else EMPTY for i, u in counts[:, c].tolist()]
+        acc = per[0]
+        for v in per[1:]:
+            acc += v
+        ious.append(acc if len(per) == 1 else acc / len(per))
+    return 100 * np.array(ious)
+
+
+class _BinaryXLoss(torch.autograd.Function):
+    """binary_xloss / StableBCELoss (reference Lovasz-Softmax_Loss.py:122-140) with a void label; forward and gradient in
+    one kernel.  ``labels``: int64 labels, or float32 targets (no void label then)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ignore):
+        logits = _dense(logits, "logits")
+        soft = labels.dtype == torch.float32
+        labels = _req(labels, "labels", torch.float32 if soft else torch.int64).contiguous()
+        if labels.numel() != logits.numel():
+            raise WsdlError(f"binary_xloss: labels {tuple(labels.shape)} do not match logits {tuple(logits.shape)}")
+        loss = torch.empty((), device=logits.device, dtype=torch.float32)
+        dl = torch.empty_like(logits) if ctx.needs_input_grad[0] else None
+        inv = torch.empty(1, device=logits.device, dtype=torch.float32)
+        ws = workspace(lib().wsdl_reduce_workspace(), logits.device)
+        check(lib().wsdl_binary_xloss_fwd_bwd(_p(logits), None if soft else _p(labels), _p(labels) if soft else None, _p(loss),
+                                              _p(dl), _p(inv), logits.numel(), int(ignore), _p(ws), ws.numel(), _stream()))
+        ctx.save_for_backward(dl, inv)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dl, inv = ctx.saved_tensors
+        out = torch.empty_like(dl)
+        sc = torch.empty_like(inv)
+        check(lib().wsdl_mul(_p(_dense(g.reshape(1))), _p(inv), _p(sc), 1, _stream()))      # upstream gradient x 1 / #valid pixels
+        check(lib().wsdl_scale_by_device_scalar(_p(dl), _p(sc), _p(out), dl.numel(), _stream()))
+        return out, None, None
+
+
+def binary_xloss(logits, labels, ignore=None):
+    """Mean over the pixels with ``labels != ignore`` of max(x,0) - x t + log(1 + exp(-|x|)); NaN when every pixel is void
+    (the reference's mean of nothing), with a zero gradient.  ``labels`` int64, or float32 targets (every element counts)."""
+    return _BinaryXLoss.apply(logits, labels, _ignore(ignore))
 
 
 def _crf_rgb(images):
