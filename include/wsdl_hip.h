@@ -650,7 +650,7 @@ int wsdl_keep_largest(const uint8_t* mask, uint8_t* out, int n, int h, int w, vo
                       wsdl_stream_t stream);
 
 /* classic CAM normalisation (CAMGenerator.generate_all_cams, TraditionalModel/AlternatingDirectionCutLoss.py:343-372):
- * y = (relu(x) - min) / (max + 1e-8) per plane; the class-weighted channel sum itself is wsdl_conv2d_fwd with
+ * y = (relu(x) - min) / ((max - min) + 1e-8) per plane (min, max of relu(x)); the class-weighted channel sum itself is wsdl_conv2d_fwd with
  * fc.weight as a 1x1 kernel. */
 int wsdl_plane_relu_minmax(const float* x, float* y, int planes, int hw, wsdl_stream_t stream);
 

@@ -1,6 +1,10 @@
 """GPU parity tests of the individual HIP kernels (through the C ABI via ops.py) against the CPU
 oracle primitives (torch CPU ATen ops - the arithmetic the reference reaches through torchvision) and the
-golden fixtures.  Tolerances: fp32 1e-3 relative (north_star), integer outputs bit-exact."""
+golden fixtures.  Tolerances: fp32 1e-3 relative (north_star), integer outputs bit-exact.
+
+Each small op (pooling, bilinear, dropout, cross entropy, softmax / KL, Adam, the one-liners of csrc/plan.hip) has ONE plain
+case here; their edge cases - stride loops, vector tails, kernel switches, batch strides, more than 65535 planes, ties, NaN,
+all against float64 - are in tests/test_hip_small_ops.py."""
 import json
 
 import numpy as np

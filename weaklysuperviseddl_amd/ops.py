@@ -2547,7 +2547,8 @@ def keep_largest_batched(masks):
 
 
 def plane_relu_minmax(x):
-    """(..., h, w) -> per-plane (relu(x) - min) / (max + 1e-8)."""
+    """(..., h, w) -> per plane: r = relu(x) - min(relu(x)); r / (max(r) + 1e-8)  (the reference's in-place
+    ``cam -= cam.min(); cam /= cam.max() + 1e-8``: the maximum is taken AFTER the minimum has been subtracted)."""
     x = _dense(x, "x")
     hw = x.shape[-1] * x.shape[-2]
     y = torch.empty_like(x)
