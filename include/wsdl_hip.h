@@ -491,6 +491,42 @@ typedef struct {
 int wsdl_pil_resize_u8(const uint8_t* src, const wsdl_pil_image_t* images, const int* tables, int N, int C, int out_h,
                        int out_w, uint8_t* dst_u8, float* dst_f32, const float* lut, wsdl_stream_t stream);
 
+/* ---- joint image / label augmentation of a training batch (csrc/augment.hip) ----
+ * The reference has no counterpart: its pipelines resize and normalise only.  This is what the training loops need beyond
+ * it, and it plugs into the device loaders that stand in for FullySupervisedModel/SupervisedModel.py:18-27
+ * (PetDataset.DeviceLoader) and TraditionalModel/SegmentationDataset.py:19-28 (InMemoryPseudoDataset.batches): one launch
+ * does their index gather, the uint8 -> float table and the label mapping, plus an affine warp and a gain / bias.
+ *
+ *   src        the image source, N x C x H x W dense: float32 (src_is_u8 = 0), or uint8 (src_is_u8 = 1) read through
+ *              lut, C x 256 floats, value = lut[c * 256 + u8] (the table of wsdl_pil_resize_u8)
+ *   src_label  N x H x W uint8; label_lut: 256 int64, raw byte -> class, NULL = identity
+ *   idx        B int64: item b reads source row idx[b] (repeats and any order are legal; a row outside [0, N) reads
+ *              nothing and yields an all-padding item)
+ *   params     B x 8 float32: a00 a01 a02 a10 a11 a12 gain bias, the map from output to source coordinates
+ *   images_out B x C x out_h x out_w float32, labels_out B x out_h x out_w int64
+ * All of these are device memory.  Per output pixel (ox, oy), pixel i covering [i, i + 1):
+ *   u = ox + 0.5f, v = oy + 0.5f
+ *   xs = (a00 * u + a01 * v) + a02,  ys = (a10 * u + a11 * v) + a12
+ *   fill = WSDL_AUGMENT_REFLECT:  P = 2 * W; q = floorf(xs / P); r = xs - P * q; if (r < 0) r += P; if (r >= W) r = P - r;
+ *                                 xs = r  (and ys with H): the source mirrored about its borders, numpy's "symmetric"
+ *   inside = fill == reflect, or (0 <= xs < W and 0 <= ys < H)
+ *   label:  inside ? label_lut[src_label[min(floor(ys), H - 1)][min(floor(xs), W - 1)]] : pad_label
+ *   image:  xc = xs - 0.5f, x0 = floor(xc), fx = xc - x0 (likewise y); the taps x0, x0 + 1, y0, y0 + 1 clamped to the
+ *           source (replicate); top = v00 + fx * (v01 - v00); bot = v10 + fx * (v11 - v10); val = top + fy * (bot - top);
+ *           inside ? gain * val + bias : pad_value
+ * Every coordinate operation above is float32 and rounded on its own (no FMA contraction), so a float32 restatement selects
+ * the same source pixels; validity is shared by image and label, so the padded regions coincide and padding never bleeds
+ * into the image.  With fx = fy = 0, gain = 1, bias = 0 the output is the (finite) source value exactly: the identity
+ * parameters 1 0 0 0 1 0 1 0 at out = source size reproduce the plain gather.  One launch, no workspace, no atomics; 64-bit
+ * offsets throughout; results do not depend on B.  C in {1, 3}, 1 <= H, W, out_h, out_w <= 16384 and the two fills; other
+ * values are refused on the host before any device is touched. */
+#define WSDL_AUGMENT_IGNORE 0
+#define WSDL_AUGMENT_REFLECT 1
+int wsdl_augment_batch(const void* src, int src_is_u8, const float* lut, const uint8_t* src_label,
+                       const long long* label_lut, const long long* idx, const float* params, int N, int C, int H, int W,
+                       int B, int out_h, int out_w, int fill, float pad_value, long long pad_label, float* images_out,
+                       long long* labels_out, wsdl_stream_t stream);
+
 /* ---- losses --------------------------------------------------------------------------------- */
 size_t wsdl_reduce_workspace(void);
 /* lovasz_softmax(probas, labels, classes, per_image=False, ignore) - the optional loss of train_segmentation_model

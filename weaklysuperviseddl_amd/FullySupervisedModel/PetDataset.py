@@ -3,7 +3,9 @@
 The reference re-decodes and re-resizes every JPEG with PIL on one host thread in every epoch (``DataLoader(...,
 num_workers=0)``).  Its pipeline has no augmentation, so the decoded, resized dataset is the same in every epoch: here it is
 built once - decoded on a host thread pool (at most 16 workers) - and kept on the device as uint8 (images (N,3,224,224),
-raw trimaps (N,224,224), categories (N,)): about 740 MB for trainval.
+raw trimaps (N,224,224), categories (N,)): about 740 MB for trainval.  An augmentation the reference does not have is opt-in:
+``DeviceLoader(..., augment=Augment(...))`` warps image and label together in the launch that gathers the batch
+(``ops.augment_batch``), so the resident tensors stay what they are.
 
 Batches are ``(images float32 (B,3,224,224), labels int64 (B,224,224))`` on the device:
   images = uint8 / 255 through a 256-entry table computed the way ToTensor computes it (bit-identical to the reference's
@@ -155,13 +157,30 @@ class DeviceLoader:
     ``random_split`` Subset's), ``shuffle`` draws a new order every epoch with ``generator`` (torch's global generator when
     None, as DataLoader).  ``drop_single``: a trailing batch of ONE image is skipped, as ``InMemoryPseudoDataset.batches``
     does - train-mode BatchNorm in the ASPP pooling branch normalises one pooled value per channel and cannot take B = 1.
-    The training loader sets it; evaluation keeps every image."""
+    The training loader sets it; evaluation keeps every image.
 
-    def __init__(self, dataset, batch_size, indices=None, shuffle=False, generator=None, drop_single=False):
+    ``augment``: an ``augment.Augment`` (default None: the plain batches above, nothing else is imported or called).  A
+    batch is then ONE launch, ``ops.augment_batch``: the gather, the uint8 -> float table, the joint warp of image and
+    label, the photometric map and the ``trimap == 1`` mapping; padded pixels carry ``augment.pad_label``.  The parameters
+    of a whole epoch are drawn from ``generator`` (after the epoch's order) and uploaded when the iteration starts; the
+    identity augmentation yields the plain batches bit for bit."""
+
+    def __init__(self, dataset, batch_size, indices=None, shuffle=False, generator=None, drop_single=False, augment=None):
         self.dataset, self.batch_size = dataset, int(batch_size)
         n = len(dataset)
         self.indices = torch.as_tensor(list(range(n)) if indices is None else list(indices), dtype=torch.int64)
         self.shuffle, self.generator, self.drop_single = shuffle, generator, drop_single
+        self.augment = augment
+        self._tables = None
+
+    def _augment_tables(self):
+        """(the dataset's float table per channel (3,256), the label table: 1 -> 1, else 0), made once."""
+        if self._tables is None:
+            ds = self.dataset
+            label_lut = torch.zeros(256, dtype=torch.int64)
+            label_lut[1] = 1
+            self._tables = (ds._table.view(1, 256).repeat(3, 1).contiguous(), label_lut.to(ds.device))
+        return self._tables
 
     def __len__(self):
         n, r = divmod(len(self.indices), self.batch_size)
@@ -172,11 +191,18 @@ class DeviceLoader:
         if self.shuffle:
             idx = idx[torch.randperm(len(idx), generator=self.generator)]
         idx = idx.to(self.dataset.device)
+        aug, ds = self.augment, self.dataset
+        if aug is not None:
+            lut, label_lut = self._augment_tables()
+            params = aug.epoch_params(len(idx), ds.images.shape[-2:], ds.device, self.generator)
         for s in range(0, len(self.indices), self.batch_size):
             part = idx[s:s + self.batch_size]
             if self.drop_single and part.numel() == 1 and self.batch_size > 1:
                 continue
-            yield self.dataset.batch(part)
+            if aug is None:
+                yield ds.batch(part)
+            else:
+                yield aug.apply(ds.images, ds.trimaps, part, params[s:s + self.batch_size], lut=lut, label_lut=label_lut)
 
 
 class DeviceItemLoader:

@@ -47,19 +47,21 @@ def initialize_model(num_classes=2, device=None, *, backbone_state_dict=None):
 
 
 def get_dataloaders(data_path='./data', train_ratio=0.85, batch_size=16, num_workers=0, *, device=None, generator=None,
-                    log=print, resize="host"):
+                    log=print, resize="host", augment=None):
     """Reference ``get_dataloaders(data_path='./data', train_ratio=0.85, batch_size=16, num_workers=0)``
     (SupervisedModel.py:18-27): the train / val split of 'trainval' (``load_split_data``) and 'test', as device loaders
     (``PetDataset.DeviceLoader``) over datasets decoded once.  ``num_workers`` is accepted and unused (the decode runs on a
     host thread pool of at most 16 workers, once).  ``generator``: the split's and the train loader's shuffling generator
     (default torch's global one, as the reference).  ``resize``: "host" (PIL resizes on the pool) or "device"
-    (``DevicePetDataset(resize="device")``: the pool only decodes); the same tensors either way."""
+    (``DevicePetDataset(resize="device")``: the pool only decodes); the same tensors either way.  ``augment``: an
+    ``augment.Augment`` for the TRAIN loader only (``DeviceLoader(augment=)``; the reference has none); validation and test
+    are never augmented."""
     dev = _device(device)
     train_subset, val_subset = load_split_data(pth=data_path, train_ratio=train_ratio, generator=generator)
     trainval = DevicePetDataset(train_subset.dataset, device=dev, resize=resize)
     test = DevicePetDataset(download_data(pth=data_path, split='test'), device=dev, resize=resize)
     train_loader = DeviceLoader(trainval, batch_size, indices=train_subset.indices, shuffle=True, generator=generator,
-                                drop_single=True)
+                                drop_single=True, augment=augment)
     val_loader = DeviceLoader(trainval, batch_size, indices=val_subset.indices)
     test_loader = DeviceLoader(test, batch_size)
     if log:
@@ -121,16 +123,18 @@ def evaluate_model(model, dataloader, device, num_classes=2):
 
 def run_supervised_training(data_path='./data', num_epochs=10, batch_size=16, train_ratio=0.85, num_classes=2, lr=1e-4,
                             device=None, *, save_path=SAVE_PATH, seed=None, log=print, backbone_state_dict=None,
-                            resize="host"):
+                            resize="host", augment=None):
     """Reference ``run_supervised_training`` (SupervisedModel.py:85-122): Adam(lr) (``make_optimizer``) on CrossEntropy,
     validation after every epoch, the final state_dict saved to ``save_path`` (None: not saved), then three evaluations
     of the test split.  ``seed`` seeds torch's global generator first (split, shuffling, initialisation).  Returns the
-    final numbers as a dict (the reference returns None).  ``resize``: see ``get_dataloaders``."""
+    final numbers as a dict (the reference returns None).  ``resize``, ``augment``: see ``get_dataloaders`` (the padding of
+    ``fill="ignore"`` carries -100, which the CrossEntropyLoss below ignores)."""
     dev = _device(device)
     if seed is not None:
         torch.manual_seed(seed)
     say = log or (lambda *a: None)
-    train_loader, val_loader, test_loader = get_dataloaders(data_path, train_ratio, batch_size, device=dev, log=log, resize=resize)
+    train_loader, val_loader, test_loader = get_dataloaders(data_path, train_ratio, batch_size, device=dev, log=log, resize=resize,
+                                                            augment=augment)
     model = initialize_model(num_classes=num_classes, device=dev, backbone_state_dict=backbone_state_dict)
     criterion = nn.CrossEntropyLoss()
     optimizer = make_optimizer(model, lr=lr)

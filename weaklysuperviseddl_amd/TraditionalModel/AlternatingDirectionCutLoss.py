@@ -190,7 +190,7 @@ def refine_dataset(model, dataset, repeats=5, chunk=64, threshold=0.3, lr=1e-4, 
 
 def run_alternating_training(model, optimizer, dataset, num_alternations=10, epochs_per_round=10, refine_repeats=5,
                              first_batch_size=4, later_batch_size=32, refine_chunk=64, refine_kwargs=None,
-                             evaluate=None, seed=0, device="cuda", log=print):
+                             evaluate=None, seed=0, device="cuda", log=print, augment=None):
     """The alternating-direction outer loop (reference AlternatingDirectionCutLoss.py:791-818; the modular re-write
     AlternatingDirectionBoundaryLoss.py:153-206 is dead code): per alternation
       1. ``train_model`` for ``epochs_per_round`` epochs on the current pseudo masks (batch 4 in the first
@@ -201,7 +201,8 @@ def run_alternating_training(model, optimizer, dataset, num_alternations=10, epo
     ``dataset`` is THIS RANK's ``InMemoryPseudoDataset`` shard.  Under data parallelism (``torch.distributed``
     initialised, a ``dp.GradBucketReducer`` on the optimizer) every rank must run the same number of optimiser steps:
     the per-epoch step count is the minimum over the ranks; refinement is per-image independent and needs no
-    collective."""
+    collective.  ``augment``: an ``augment.Augment`` handed to ``dataset.batches`` - the training batches
+    only; refinement reads the stored images and masks (the reference has no augmentation)."""
     import torch.distributed as dist
     rk = dict(threshold=0.3, lr=1e-4, num_steps=10, lambda_boundary=0.1)
     rk.update(refine_kwargs or {})
@@ -217,8 +218,9 @@ def run_alternating_training(model, optimizer, dataset, num_alternations=10, epo
             t = torch.tensor([steps], dtype=torch.int64)
             dist.all_reduce(t, op=dist.ReduceOp.MIN, group=control_group())
             steps = int(t.item())
+        kw = {} if augment is None else {"augment": augment}
         losses = train_model(model, optimizer, None, epochs_per_round,
-                             train_loader=lambda: dataset.batches(bs, shuffle=True, generator=gen, limit=steps),
+                             train_loader=lambda: dataset.batches(bs, shuffle=True, generator=gen, limit=steps, **kw),
                              device=device, log=log if rank == 0 else None)
         metrics = evaluate(model) if evaluate is not None else None
         if log and rank == 0 and metrics is not None:

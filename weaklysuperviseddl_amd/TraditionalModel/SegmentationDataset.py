@@ -112,12 +112,19 @@ class InMemoryPseudoDataset(Dataset):
         n, r = divmod(len(self), batch_size)
         return n + (1 if r > (1 if drop_single else 0) else 0)
 
-    def batches(self, batch_size, shuffle=True, generator=None, limit=None):
+    def batches(self, batch_size, shuffle=True, generator=None, limit=None, augment=None):
         """Yields (images, masks int64, index tensor).  A trailing batch of ONE image is skipped like the reference's
-        trainer does (SegmentationModel.py:97-98: train-mode BN cannot normalise one pooled value)."""
+        trainer does (SegmentationModel.py:97-98: train-mode BN cannot normalise one pooled value).
+
+        ``augment``: an ``augment.Augment`` (default None: nothing new is imported or called).  Images and masks of a batch
+        then come from one launch (``ops.augment_batch`` on the float images, the mask bytes kept as they are: 255 stays
+        255, padded pixels carry ``augment.pad_label``); the parameters of the whole epoch are drawn from ``generator``
+        (after the epoch's order) and uploaded before the first batch.  The identity yields the plain batches bit for bit."""
         n = len(self)
         order = torch.randperm(n, generator=generator) if shuffle else torch.arange(n)
         order = order.to(self.images.device)
+        if augment is not None:
+            params = augment.epoch_params(n, self.images.shape[-2:], self.images.device, generator)
         done = 0
         for s in range(0, n, batch_size):
             idx = order[s:s + batch_size]
@@ -126,4 +133,7 @@ class InMemoryPseudoDataset(Dataset):
             if limit is not None and done >= limit:
                 return
             done += 1
-            yield self.images[idx], self.masks[idx].long(), idx
+            if augment is None:
+                yield self.images[idx], self.masks[idx].long(), idx
+            else:
+                yield augment.apply(self.images, self.masks, idx, params[s:s + batch_size]) + (idx,)

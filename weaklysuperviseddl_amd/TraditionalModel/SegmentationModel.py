@@ -319,26 +319,38 @@ def _one(device):
     return t
 
 
-def train_step(model, optimizer, images, masks, extra_loss=None, loss_fn="cross_entropy", criterion=None):
+def train_step(model, optimizer, images, masks, extra_loss=None, loss_fn="cross_entropy", criterion=None, *,
+               ignore_label=None):
     """One training iteration; returns the (device) loss tensor, no host synchronisation.  ``loss_fn``: 'cross_entropy' or
     'lovasz_softmax' (reference SegmentationModel.py:65,103-107), or 'lovasz_hinge': the binary Lovasz hinge of the
     reference's loss file (LossFunctions/Lovasz-Softmax_Loss.py:71-104) on the logit difference z1 - z0, per image;
     ``criterion``: a reference-style loss object instead (``resolve_criterion``).
+
+    ``ignore_label`` (default None: nothing changes): a label the ``loss_fn`` losses leave out - ``ignore=`` of the two
+    Lovasz losses, ``ignore_index`` of the cross entropy (a ``criterion`` keeps its own).  Batches augmented with
+    ``fill="ignore"`` carry -100 where the warp left the source: the cross entropy ignores that value by default, with or
+    without a ``criterion``, but a Lovasz ``loss_fn`` needs ``ignore_label=-100``.  ``fill="reflect"`` pads nothing and
+    needs nothing - the mode to use with the NCut and boundary terms (``extra_loss``), which would otherwise see an edge
+    at the pad border.
 
     On the device, in train mode and outside data parallelism the iteration is issued as ONE host call from its third
     occurrence on (``plan.PlannedTrainStep``: the launches of an eager iteration recorded behind the C ABI, verified to
     reproduce it bit for bit, then replayed); WSDL_PLAN_STEP=0 keeps every iteration eager."""
     if isinstance(optimizer, FlatAdam) and images.is_cuda and plan.PLAN_STEP[0]:
         tag = (plan.loss_tag(extra_loss), loss_fn, plan.loss_tag(criterion))
+        if ignore_label is not None:
+            tag += (int(ignore_label),)
         st = plan.planned_step_for(model, optimizer,
-                                   lambda i, m: _train_step_eager(model, optimizer, i, m, extra_loss, loss_fn, criterion), tag)
+                                   lambda i, m: _train_step_eager(model, optimizer, i, m, extra_loss, loss_fn, criterion,
+                                                                  ignore_label), tag)
         # host scalars inside the loss objects (weights, window sizes, sigmas) are kernel arguments a plan freezes: part of its key
         st.loss_scalars = (plan.host_scalars(extra_loss), plan.host_scalars(criterion)) if (extra_loss is not None or criterion is not None) else None
         return st(images, masks)
-    return _train_step_eager(model, optimizer, images, masks, extra_loss, loss_fn, criterion)
+    return _train_step_eager(model, optimizer, images, masks, extra_loss, loss_fn, criterion, ignore_label)
 
 
-def _train_step_eager(model, optimizer, images, masks, extra_loss=None, loss_fn="cross_entropy", criterion=None):
+def _train_step_eager(model, optimizer, images, masks, extra_loss=None, loss_fn="cross_entropy", criterion=None,
+                      ignore_label=None):
     masks = ops.clamp_max_labels(masks, 1)
     with ops.prof_range("train_step/forward"):
         outputs = model(images)["out"]
@@ -351,11 +363,12 @@ def _train_step_eager(model, optimizer, images, masks, extra_loss=None, loss_fn=
         if criterion is not None:
             loss = resolve_criterion(criterion)(outputs, masks)
         elif loss_fn == "lovasz_softmax":
-            loss = ops.lovasz_softmax(ops.softmax_channels(outputs), masks.long(), classes="present", per_image=False, ignore=None)
+            loss = ops.lovasz_softmax(ops.softmax_channels(outputs), masks.long(), classes="present", per_image=False,
+                                      ignore=ignore_label)
         elif loss_fn == "lovasz_hinge":
-            loss = ops.lovasz_hinge(outputs, masks.long(), per_image=True, ignore=None)      # two planes: z1 - z0 in the kernel
+            loss = ops.lovasz_hinge(outputs, masks.long(), per_image=True, ignore=ignore_label)      # two planes: z1 - z0 in the kernel
         elif loss_fn == "cross_entropy":
-            loss = ops.cross_entropy(outputs, masks.long())
+            loss = ops.cross_entropy(outputs, masks.long(), -100 if ignore_label is None else int(ignore_label))
         else:
             raise ValueError(f"loss_fn {loss_fn!r}: 'cross_entropy', 'lovasz_softmax' or 'lovasz_hinge'")
         if extra_loss is not None:

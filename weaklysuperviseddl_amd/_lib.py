@@ -93,6 +93,7 @@ SIGNATURES = {
     "wsdl_seg_counts": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "wsdl_pil_coeffs": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "wsdl_pil_resize_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "wsdl_augment_batch": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp] + [_i] * 8 + [_f, _ll, _vp, _vp, _vp]),
     "wsdl_pairwise_affinity_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _sz, _vp]),
     "wsdl_pairwise_cache_bytes": (_sz, [_i, _i, _i, _i]),
     "wsdl_pairwise_cache": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),

@@ -2174,6 +2174,74 @@ def pil_resize_arrays(arrays, size, filter, channels=3, device="cuda", *, out=No
     return pil_resize(torch.from_numpy(flat).to(device), desc, channels, size, out=out, out_f32=out_f32, lut=lut)
 
 
+# ---- joint image / label augmentation of a training batch (csrc/augment.hip) -------------------------------------------
+AUGMENT_FILLS = {"ignore": 0, "reflect": 1}         # WSDL_AUGMENT_IGNORE / WSDL_AUGMENT_REFLECT
+AUGMENT_MAX_SIDE = 16384
+
+
+def augment_batch(images, labels, idx, params, out_size=None, *, lut=None, label_lut=None, fill="ignore", pad_value=0.0,
+                  pad_label=-100):
+    """Gather, warp and map a batch of a device-resident dataset in one launch (wsdl_augment_batch; the reference has no
+    augmentation).
+
+    images     (N,C,H,W) dense, C in {1, 3}: float32, or uint8 read through ``lut`` (C,256) float32 (``lut[c, u8]``);
+    labels     (N,H,W) dense uint8; ``label_lut``: (256,) int64, raw byte -> class (None: the byte itself);
+    idx        (B,) int64 on the device: item b reads source row ``idx[b]``;
+    params     (B,8) float32 on the device: ``a00 a01 a02 a10 a11 a12 gain bias`` per item - the affine map from output to
+               source pixel coordinates and the photometric map (``augment.Augment.draw``; include/wsdl_hip.h states the
+               arithmetic);
+    out_size   (out_h, out_w), default the source's;
+    fill       "ignore": output pixels whose source point lies outside the image get ``pad_value`` / ``pad_label``;
+               "reflect": the source is mirrored about its borders, nothing is padded.
+    Returns ``(images_out (B,C,out_h,out_w) float32, labels_out (B,out_h,out_w) int64)``.  Current stream, no host
+    synchronisation, no CPU fallback."""
+    for t, name in ((images, "images"), (labels, "labels"), (idx, "idx"), (params, "params"), (lut, "lut"),
+                    (label_lut, "label_lut")):
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda):
+            raise WsdlError(f"augment_batch: {name}: the HIP path needs a device tensor "
+                            f"(got {t.device if torch.is_tensor(t) else type(t).__name__}); there is no CPU fallback")
+    if images.dim() != 4 or images.dtype not in (torch.float32, torch.uint8) or not images.is_contiguous():
+        raise WsdlError("augment_batch: images must be a dense (N,C,H,W) float32 or uint8 tensor")
+    N, Cc, H, W = images.shape
+    if Cc not in (1, 3):
+        raise WsdlError(f"augment_batch: C = {Cc}, supported 1 and 3")
+    dev = images.device
+    _req(labels, "augment_batch: labels", torch.uint8)
+    if tuple(labels.shape) != (N, H, W) or not labels.is_contiguous() or labels.device != dev:
+        raise WsdlError(f"augment_batch: labels must be a dense uint8 {(N, H, W)} on the images' device, got {tuple(labels.shape)}")
+    _req(idx, "augment_batch: idx", torch.int64)
+    _req(params, "augment_batch: params")
+    B = idx.numel()
+    if idx.dim() != 1 or B == 0 or not idx.is_contiguous() or idx.device != dev:
+        raise WsdlError("augment_batch: idx must be a dense non-empty (B,) int64 tensor on the images' device")
+    if tuple(params.shape) != (B, 8) or not params.is_contiguous() or params.device != dev:
+        raise WsdlError(f"augment_batch: params must be a dense float32 {(B, 8)} on the images' device, got {tuple(params.shape)}")
+    u8 = images.dtype == torch.uint8
+    if u8:
+        if lut is None:
+            raise WsdlError("augment_batch: a uint8 source needs lut, the (C, 256) float32 table")
+        _req(lut, "augment_batch: lut")
+        if tuple(lut.shape) != (Cc, 256) or not lut.is_contiguous() or lut.device != dev:
+            raise WsdlError(f"augment_batch: lut must be a dense float32 {(Cc, 256)} on the images' device")
+    elif lut is not None:
+        raise WsdlError("augment_batch: lut goes with a uint8 source")
+    if label_lut is not None:
+        _req(label_lut, "augment_batch: label_lut", torch.int64)
+        if label_lut.numel() != 256 or not label_lut.is_contiguous() or label_lut.device != dev:
+            raise WsdlError("augment_batch: label_lut must be a dense int64 table of 256 on the images' device")
+    if fill not in AUGMENT_FILLS:
+        raise WsdlError(f"augment_batch: fill {fill!r}: 'ignore' or 'reflect'")
+    out_h, out_w = (H, W) if out_size is None else (int(v) for v in out_size)
+    if not (1 <= out_h <= AUGMENT_MAX_SIDE and 1 <= out_w <= AUGMENT_MAX_SIDE):
+        raise WsdlError(f"augment_batch: out_size {(out_h, out_w)}: side lengths 1..{AUGMENT_MAX_SIDE}")
+    images_out = torch.empty(B, Cc, out_h, out_w, dtype=torch.float32, device=dev)
+    labels_out = torch.empty(B, out_h, out_w, dtype=torch.int64, device=dev)
+    check(lib().wsdl_augment_batch(_p(images), int(u8), _p(lut), _p(labels), _p(label_lut), _p(idx), _p(params), N, Cc, H, W,
+                                   B, out_h, out_w, AUGMENT_FILLS[fill], float(pad_value), int(pad_label), _p(images_out),
+                                   _p(labels_out), _stream()))
+    return images_out, labels_out
+
+
 DROPOUT_SEED_OFFSET = [0]      # dp.init_distributed: a different offset on every rank, so replicas draw different masks
 
 
