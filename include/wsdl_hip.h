@@ -627,6 +627,25 @@ int wsdl_dense_crf_filter(const uint8_t* rgb, const float* in, float* out, int B
 int wsdl_softmax_ce_fwd_bwd(const float* logits, const int64_t* labels, float* loss, float* dlogits,
                             float* inv_count, int B, int C, int H, int W, float grad_scale,
                             long long ignore_index, void* ws, size_t ws_bytes, wsdl_stream_t stream);
+/* nn.CrossEntropyLoss(weight, ignore_index, reduction, label_smoothing) extended by a per-pixel weight: the same kernel
+ * with its options switched on (wsdl_softmax_ce_fwd_bwd is this call with none of them).  For pixel i with label y,
+ * softmax s, class weights w (class_weight, C floats, or null: all 1), pixel weight p (pixel_weight, B*H*W floats >= 0,
+ * or null: all 1; p == 0 is an ignored pixel) and e = label_smoothing in [0, 1]:
+ *     l_i = p_i * [ (1-e) w[y] (-log s[y]) + (e/C) sum_c w[c] (-log s[c]) ]        (0 where y == ignore_index)
+ * reduction 0 (mean): *loss = sum_i l_i / sum_i p_i w[y_i] (PyTorch's denominator: the target classes only, also with
+ * smoothing; 0/0 = NaN), *inv_count = 1 / that denominator; 1 (sum): *loss = sum_i l_i, *inv_count = 1; 2 (none): loss
+ * points at B*H*W floats and receives l, inv_count is not written (may be null).  dlogits (optional) = grad_scale *
+ * d l_i / d logits, still to be multiplied by inv_count x the upstream gradient (wsdl_scale_by_device_scalar) or, for
+ * reduction 2, by the upstream gradient of each pixel (wsdl_scale_by_pixel).  A label outside [0,C) that is not
+ * ignore_index: NaN loss (reduction 2: NaN at that pixel only).  Deterministic: fixed-order partial sums, no atomics. */
+int wsdl_softmax_ce_ex_fwd_bwd(const float* logits, const int64_t* labels, float* loss, float* dlogits,
+                               float* inv_count, int B, int C, int H, int W, float grad_scale,
+                               long long ignore_index, const float* class_weight, const float* pixel_weight,
+                               float label_smoothing, int reduction, void* ws, size_t ws_bytes,
+                               wsdl_stream_t stream);
+/* out[b,c,h,w] = dl[b,c,h,w] * g[b,h,w]: the backward of nn.CrossEntropyLoss(reduction='none') */
+int wsdl_scale_by_pixel(const float* dl, const float* g, float* out, int B, int C, int H, int W,
+                        wsdl_stream_t stream);
 /* Pairwise-affinity loss over a reflect-padded window x window neighbourhood:
  *   apply_softmax=1, normalise=0, sigma_space<=0 : LocalNormalizedCutLoss.forward
  *                                  (TraditionalModel/AlternatingDirectionCutLoss.py:65-105)

@@ -123,12 +123,14 @@ def evaluate_model(model, dataloader, device, num_classes=2):
 
 def run_supervised_training(data_path='./data', num_epochs=10, batch_size=16, train_ratio=0.85, num_classes=2, lr=1e-4,
                             device=None, *, save_path=SAVE_PATH, seed=None, log=print, backbone_state_dict=None,
-                            resize="host", augment=None):
+                            resize="host", augment=None, criterion=None):
     """Reference ``run_supervised_training`` (SupervisedModel.py:85-122): Adam(lr) (``make_optimizer``) on CrossEntropy,
     validation after every epoch, the final state_dict saved to ``save_path`` (None: not saved), then three evaluations
     of the test split.  ``seed`` seeds torch's global generator first (split, shuffling, initialisation).  Returns the
     final numbers as a dict (the reference returns None).  ``resize``, ``augment``: see ``get_dataloaders`` (the padding of
-    ``fill="ignore"`` carries -100, which the CrossEntropyLoss below ignores)."""
+    ``fill="ignore"`` carries -100, which the CrossEntropyLoss below ignores).  ``criterion``: the loss object instead of
+    the reference's ``nn.CrossEntropyLoss()`` - one with class weights, or a ``weaklysuperviseddl_amd.nn.CrossEntropyLoss``
+    (label smoothing, pixel weights); see ``SegmentationModel.resolve_criterion``."""
     dev = _device(device)
     if seed is not None:
         torch.manual_seed(seed)
@@ -136,7 +138,8 @@ def run_supervised_training(data_path='./data', num_epochs=10, batch_size=16, tr
     train_loader, val_loader, test_loader = get_dataloaders(data_path, train_ratio, batch_size, device=dev, log=log, resize=resize,
                                                             augment=augment)
     model = initialize_model(num_classes=num_classes, device=dev, backbone_state_dict=backbone_state_dict)
-    criterion = nn.CrossEntropyLoss()
+    if criterion is None:
+        criterion = nn.CrossEntropyLoss()
     optimizer = make_optimizer(model, lr=lr)
 
     train_loss = val_acc = val_iou = float('nan')

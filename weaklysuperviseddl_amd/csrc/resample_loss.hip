@@ -116,44 +116,140 @@ __global__ void finalize_sum_kernel(const float* __restrict__ part, int n, int g
 }
 
 // ------------------------------------------------------------------------------- cross entropy
-// nn.CrossEntropyLoss() semantics: mean over the pixels whose label is not `ignore_index` (default -100); such
-// pixels get zero loss and zero gradient.  Any other label outside [0, C) is an error in PyTorch (IndexError on the
-// CPU, a device assert on a GPU); a kernel cannot raise, so it POISONS the loss with NaN - loud, instead of silently
+// nn.CrossEntropyLoss(weight, ignore_index, reduction, label_smoothing) extended by a pixel weight p.  For pixel i with
+// label y, softmax s, class weights w (default 1), smoothing e:
+//     l_i = p_i [ (1-e) w[y] (-log s[y]) + (e/C) sum_c w[c] (-log s[c]) ]                 (0 where y == ignore_index)
+//     dl_i/dz[c] = p_i [ s[c] A - (1-e) w[y] [c == y] - (e/C) w[c] ],   A = (1-e) w[y] + (e/C) sum_c w[c]
+// 'mean' divides by sum_i p_i w[y_i] over the pixels that are not ignored (the target classes only, also with smoothing:
+// PyTorch's rule); p_i == 0 is an ignored pixel.  Any other label outside [0, C) is an error in PyTorch (IndexError on
+// the CPU, a device assert on a GPU); a kernel cannot raise, so it POISONS the loss with NaN - loud, instead of silently
 // training the pixel as a real class (e.g. an un-clamped 255 of a mask PNG; the reference clamps before the loss:
-// AlternatingDirectionCutLoss.py:695).  part[0..blocks) = loss partials, part[blocks..2*blocks) = valid-pixel counts.
+// AlternatingDirectionCutLoss.py:695).  part[0..blocks) = loss partials, part[blocks..2*blocks) = denominators (the
+// valid-pixel counts without weights).  With MAP the per-pixel loss goes to `map` and no partial is written.
+//
+// NC: the C logits of a pixel are read ONCE into registers - NC == C for 2 and 3, NC == 8 holds any C <= 8 (predicated,
+// fully unrolled); NC == 0 re-reads them from memory per pass (any C).  Every instantiation evaluates max over c,
+// sum_c expf(l - m) for c = 0..C-1, m + logf(se) and expf(l - m) * inv in this order; the instantiation without options
+// keeps the expressions of the kernel it grew from, bit for bit (launch-plan verification and the golden gradients rest
+// on them).
+template <int NC, bool CW, bool SM, bool PW, bool MAP>
 __global__ void softmax_ce_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
                                   float* __restrict__ part, float* __restrict__ dlogits, int C, int HW,
-                                  long long npix, float gscale, long long ignore_index) {
+                                  long long npix, float gscale, long long ignore_index,
+                                  const float* __restrict__ cweight, const float* __restrict__ pweight, float eps,
+                                  float* __restrict__ map) {
+    constexpr bool kPlain = !CW && !SM && !PW && !MAP;
+    constexpr int NR = NC > 0 ? NC : 1;
     __shared__ float sm[16];
     float acc = 0.f, cnt = 0.f;
+    float wsum = (float)C;                                  // sum_c w[c] (smoothing)
+    if (CW && SM) {
+        wsum = 0.f;
+        for (int c = 0; c < C; ++c) wsum += cweight[c];
+    }
+    const float e_c = SM ? eps / (float)C : 0.f, e_1 = SM ? 1.f - eps : 1.f;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < npix;
          i += (long long)gridDim.x * blockDim.x) {
         const long long b = i / HW;
         const int r = (int)(i - b * HW);
         const float* lp = logits + b * C * HW + r;
         const long long lab = labels[i];
-        const bool ignored = lab == ignore_index;
+        const float pw = PW ? pweight[i] : 1.f;
+        const bool ignored = lab == ignore_index || (PW && pw == 0.f);
         const bool bad = !ignored && (lab < 0 || lab >= C);
-        float m = -INFINITY;
-        for (int c = 0; c < C; ++c) m = fmaxf(m, lp[(long long)c * HW]);
-        float se = 0.f;
-        for (int c = 0; c < C; ++c) se += expf(lp[(long long)c * HW] - m);
+        float reg[NR];
+        if (NC > 0) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) reg[c] = (NC == 8 && c >= C) ? -INFINITY : lp[(long long)c * HW];
+        }
+        float m = -INFINITY, se = 0.f, ly = 0.f;
+        if (NC > 0) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c)
+                if (NC != 8 || c < C) m = fmaxf(m, reg[c]);
+#pragma unroll
+            for (int c = 0; c < NC; ++c)
+                if (NC != 8 || c < C) se += expf(reg[c] - m);
+#pragma unroll
+            for (int c = 0; c < NC; ++c)
+                if (c == lab) ly = reg[c];
+        } else {
+            for (int c = 0; c < C; ++c) m = fmaxf(m, lp[(long long)c * HW]);
+            for (int c = 0; c < C; ++c) se += expf(lp[(long long)c * HW] - m);
+            if (!ignored && !bad) ly = lp[lab * HW];
+        }
         const float lse = m + logf(se);
-        if (bad)
-            acc += NAN;
-        else if (!ignored) {
-            acc += lse - lp[lab * HW];
-            cnt += 1.f;
+        // the weight of the target class; NaN for a label that is no class (never an out-of-bounds read)
+        const float wy = !CW ? 1.f : (ignored ? 0.f : (bad ? NAN : cweight[lab]));
+        if (kPlain) {
+            if (bad)
+                acc += NAN;
+            else if (!ignored) {
+                acc += lse - ly;
+                cnt += 1.f;
+            }
+        } else {
+            float li = 0.f;
+            if (bad)
+                li = NAN;
+            else if (!ignored) {
+                li = e_1 * wy * (lse - ly);
+                if (SM) {
+                    float sw = 0.f;
+                    if (NC > 0) {
+#pragma unroll
+                        for (int c = 0; c < NC; ++c)
+                            if (NC != 8 || c < C) sw += (CW ? cweight[c] : 1.f) * (lse - reg[c]);
+                    } else {
+                        for (int c = 0; c < C; ++c) sw += (CW ? cweight[c] : 1.f) * (lse - lp[(long long)c * HW]);
+                    }
+                    li += e_c * sw;
+                }
+                if (PW) li *= pw;
+                cnt += PW ? pw * wy : wy;
+            }
+            if (MAP)
+                map[i] = li;
+            else
+                acc += li;
         }
         if (dlogits) {
             float* dp = dlogits + b * C * HW + r;
             const float inv = 1.f / se;
-            for (int c = 0; c < C; ++c) {
-                const float pr = expf(lp[(long long)c * HW] - m) * inv;
-                dp[(long long)c * HW] = ignored ? 0.f : (pr - (c == lab ? 1.f : 0.f)) * gscale;
+            if (kPlain) {
+                if (NC > 0) {
+#pragma unroll
+                    for (int c = 0; c < NC; ++c)
+                        if (NC != 8 || c < C) {
+                            const float pr = expf(reg[c] - m) * inv;
+                            dp[(long long)c * HW] = ignored ? 0.f : (pr - (c == lab ? 1.f : 0.f)) * gscale;
+                        }
+                } else {
+                    for (int c = 0; c < C; ++c) {
+                        const float pr = expf(lp[(long long)c * HW] - m) * inv;
+                        dp[(long long)c * HW] = ignored ? 0.f : (pr - (c == lab ? 1.f : 0.f)) * gscale;
+                    }
+                }
+            } else {
+                const float A = e_1 * wy + e_c * wsum;
+                const float ps = (PW ? pw : 1.f) * gscale;
+                auto grad = [&](int c, float l) {
+                    const float pr = expf(l - m) * inv;
+                    float g = pr * A - (c == lab ? e_1 * wy : 0.f);
+                    if (SM) g -= e_c * (CW ? cweight[c] : 1.f);
+                    dp[(long long)c * HW] = ignored ? 0.f : g * ps;
+                };
+                if (NC > 0) {
+#pragma unroll
+                    for (int c = 0; c < NC; ++c)
+                        if (NC != 8 || c < C) grad(c, reg[c]);
+                } else {
+                    for (int c = 0; c < C; ++c) grad(c, lp[(long long)c * HW]);
+                }
             }
         }
     }
+    if (MAP) return;
     acc = block_sum(acc, sm);
     cnt = block_sum(cnt, sm);
     if (threadIdx.x == 0) {
@@ -162,9 +258,10 @@ __global__ void softmax_ce_kernel(const float* __restrict__ logits, const int64_
     }
 }
 
-// loss = sum / count, inv_count = 1 / count (the factor the gradient still lacks); count == 0 -> NaN like PyTorch
+// reduction 0 (mean): loss = sum / denominator, inv_count = 1 / denominator (the factor the gradient still lacks);
+// denominator == 0 -> NaN like PyTorch.  reduction 1 (sum): loss = sum, inv_count = 1.
 __global__ void ce_finalize_kernel(const float* __restrict__ part, int blocks, float* __restrict__ loss,
-                                   float* __restrict__ inv_count) {
+                                   float* __restrict__ inv_count, int reduction) {
     __shared__ double sm[16];
     double s = 0.0, c = 0.0;
     for (int i = threadIdx.x; i < blocks; i += blockDim.x) {
@@ -174,8 +271,24 @@ __global__ void ce_finalize_kernel(const float* __restrict__ part, int blocks, f
     s = block_sum_d(s, sm);
     c = block_sum_d(c, sm);
     if (threadIdx.x == 0) {
-        *loss = (float)(s / c);
-        if (inv_count) *inv_count = (float)(1.0 / c);
+        if (reduction == 1) {
+            *loss = (float)s;
+            if (inv_count) *inv_count = 1.f;
+        } else {
+            *loss = (float)(s / c);
+            if (inv_count) *inv_count = (float)(1.0 / c);
+        }
+    }
+}
+
+// backward of reduction 'none': out[b,c,r] = dl[b,c,r] * g[b,r]
+__global__ void scale_by_pixel_kernel(const float* __restrict__ dl, const float* __restrict__ g,
+                                      float* __restrict__ out, int C, int HW, long long n) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
+         i += (long long)gridDim.x * blockDim.x) {
+        const long long plane = i / HW;
+        const int r = (int)(i - plane * HW);
+        out[i] = dl[i] * g[(plane / C) * HW + r];
     }
 }
 
@@ -512,6 +625,38 @@ inline dim3 plane_grid(int planes, int HW) {
 }
 inline int flat_blocks(long long n) { return (int)std::min<long long>((n + 255) / 256, wsdl::kReduceSlots); }
 
+struct CeArgs {
+    const float* logits; const int64_t* labels; float* part; float* dlogits; int C, HW; long long npix;
+    float gscale; long long ignore_index; const float* cweight; const float* pweight; float eps; float* map;
+};
+
+template <int NC, bool CW, bool SM, bool PW, bool MAP>
+void ce_launch(const CeArgs& a, int blocks, hipStream_t s) {
+    hipLaunchKernelGGL((softmax_ce_kernel<NC, CW, SM, PW, MAP>), dim3(blocks), dim3(256), 0, s, a.logits, a.labels, a.part,
+                       a.dlogits, a.C, a.HW, a.npix, a.gscale, a.ignore_index, a.cweight, a.pweight, a.eps, a.map);
+}
+
+template <int NC>
+void ce_launch_options(const CeArgs& a, bool sm, bool mp, int blocks, hipStream_t s) {
+    const int o = (a.cweight ? 1 : 0) | (sm ? 2 : 0) | (a.pweight ? 4 : 0) | (mp ? 8 : 0);
+    switch (o) {
+#define WSDL_CE_CASE(k) \
+    case k: ce_launch<NC, ((k) & 1) != 0, ((k) & 2) != 0, ((k) & 4) != 0, ((k) & 8) != 0>(a, blocks, s); break;
+        WSDL_CE_CASE(0) WSDL_CE_CASE(1) WSDL_CE_CASE(2) WSDL_CE_CASE(3) WSDL_CE_CASE(4) WSDL_CE_CASE(5)
+        WSDL_CE_CASE(6) WSDL_CE_CASE(7) WSDL_CE_CASE(8) WSDL_CE_CASE(9) WSDL_CE_CASE(10) WSDL_CE_CASE(11)
+        WSDL_CE_CASE(12) WSDL_CE_CASE(13) WSDL_CE_CASE(14) WSDL_CE_CASE(15)
+#undef WSDL_CE_CASE
+    }
+}
+
+// C = 2 and 3 unrolled, any other C <= 8 through the predicated 8-register form, larger C re-reads memory
+void ce_launch_any(const CeArgs& a, bool sm, bool mp, int blocks, hipStream_t s) {
+    if (a.C == 2) ce_launch_options<2>(a, sm, mp, blocks, s);
+    else if (a.C == 3) ce_launch_options<3>(a, sm, mp, blocks, s);
+    else if (a.C <= 8) ce_launch_options<8>(a, sm, mp, blocks, s);
+    else ce_launch_options<0>(a, sm, mp, blocks, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -548,8 +693,19 @@ int wsdl_bilinear_bwd(const float* dy, float* dx, int B, int C, int h, int w, in
 int wsdl_softmax_ce_fwd_bwd(const float* logits, const int64_t* labels, float* loss, float* dlogits,
                             float* inv_count, int B, int C, int H, int W, float grad_scale, long long ignore_index,
                             void* ws, size_t ws_bytes, wsdl_stream_t stream) {
+    return wsdl_softmax_ce_ex_fwd_bwd(logits, labels, loss, dlogits, inv_count, B, C, H, W, grad_scale, ignore_index,
+                                      nullptr, nullptr, 0.f, 0, ws, ws_bytes, stream);
+}
+
+int wsdl_softmax_ce_ex_fwd_bwd(const float* logits, const int64_t* labels, float* loss, float* dlogits,
+                               float* inv_count, int B, int C, int H, int W, float grad_scale, long long ignore_index,
+                               const float* class_weight, const float* pixel_weight, float label_smoothing,
+                               int reduction, void* ws, size_t ws_bytes, wsdl_stream_t stream) {
     WSDL_REQUIRE(logits && labels && loss && ws && B > 0 && C > 0 && H > 0 && W > 0, "softmax_ce: bad arguments");
-    WSDL_REQUIRE(!dlogits || inv_count, "softmax_ce: the gradient needs inv_count (it is left unnormalised)");
+    WSDL_REQUIRE(reduction >= 0 && reduction <= 2, "softmax_ce: reduction must be 0 (mean), 1 (sum) or 2 (none)");
+    WSDL_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f, "softmax_ce: label_smoothing must be in [0, 1]");
+    WSDL_REQUIRE(!dlogits || inv_count || reduction == 2,
+                 "softmax_ce: the gradient needs inv_count (it is left unnormalised)");
     if (ws_bytes < wsdl_reduce_workspace()) {
         wsdl::set_error("softmax_ce: workspace too small");
         return WSDL_EWORKSPACE;
@@ -558,10 +714,24 @@ int wsdl_softmax_ce_fwd_bwd(const float* logits, const int64_t* labels, float* l
     const int blocks = std::min(flat_blocks(npix), wsdl::kReduceSlots / 2);
     hipStream_t s = wsdl::as_stream(stream);
     float* part = static_cast<float*>(ws);
-    hipLaunchKernelGGL(softmax_ce_kernel, dim3(blocks), dim3(256), 0, s, logits, labels, part, dlogits, C, H * W,
-                       npix, grad_scale, ignore_index);
+    const bool none = reduction == 2;
+    const CeArgs a{logits, labels, part, dlogits, C, H * W, npix, grad_scale, ignore_index, class_weight, pixel_weight,
+                   label_smoothing, none ? loss : nullptr};
+    ce_launch_any(a, label_smoothing != 0.f, none, blocks, s);
     WSDL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, s, part, blocks, loss, inv_count);
+    if (!none) {
+        hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, s, part, blocks, loss, inv_count, reduction);
+        WSDL_LAUNCH_CHECK();
+    }
+    return WSDL_OK;
+}
+
+int wsdl_scale_by_pixel(const float* dl, const float* g, float* out, int B, int C, int H, int W,
+                        wsdl_stream_t stream) {
+    WSDL_REQUIRE(dl && g && out && B > 0 && C > 0 && H > 0 && W > 0, "scale_by_pixel: bad arguments");
+    const long long n = (long long)B * C * H * W;
+    hipLaunchKernelGGL(scale_by_pixel_kernel, dim3(flat_blocks(n)), dim3(256), 0, wsdl::as_stream(stream), dl, g, out, C,
+                       H * W, n);
     WSDL_LAUNCH_CHECK();
     return WSDL_OK;
 }

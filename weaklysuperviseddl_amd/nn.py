@@ -207,3 +207,68 @@ def make_resnet50_stages(replace_stride_with_dilation):
         if isinstance(m, Conv2d):
             nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
     return conv1, bn1, layers
+
+
+class CrossEntropyLoss(nn.Module):
+    """``torch.nn.CrossEntropyLoss(weight, ignore_index, reduction, label_smoothing)`` on (B,C,H,W) logits and (B,H,W)
+    labels, run by the fused cross-entropy kernel (``ops.cross_entropy``), plus a per-pixel confidence weight that lives
+    on the device.
+
+    ``set_pixel_weight(t)`` copies a float32 (B,H,W) map (finite, >= 0; 0 = ignore the pixel) into a buffer this object
+    owns; the buffer is allocated anew only when the shape changes, so its address - which a launch plan freezes - stays
+    put while the values change every step.  ``set_pixel_weight(None)`` drops it.  The smoothing factor, the reduction,
+    ``ignore_index``, the addresses of both buffers and the shape of the pixel weights are plain attributes: ``plan.host_scalars`` puts them into the
+    plan key, so changing one records a new plan instead of replaying a stale one.
+
+    Pseudo masks with a confidence, e.g. from the CRF posterior or from the CAM's distance to its threshold::
+
+        crit = wnn.CrossEntropyLoss(weight=ops.class_weights_from_labels(masks, 2), label_smoothing=0.1)
+        refined, q = ops.dense_crf(images_u8, unary, return_q=True)       # q: (B,2,H,W) posterior
+        crit.set_pixel_weight(q.amax(1))                                    # or (2 * cam - 1).abs() for a CAM in [0, 1]
+        loss = train_step(model, optimizer, images, refined, criterion=crit)
+    """
+
+    def __init__(self, weight=None, ignore_index=-100, reduction="mean", label_smoothing=0.0):
+        super().__init__()
+        ops.check_cross_entropy_options(reduction, label_smoothing)
+        if weight is not None and (not torch.is_tensor(weight) or weight.dim() != 1):
+            raise ValueError("CrossEntropyLoss: weight must be a (C,) tensor")
+        self.register_buffer("weight", None if weight is None else weight.detach().to(torch.float32).clone())
+        self.register_buffer("pixel_weight", None, persistent=False)
+        self.ignore_index = int(ignore_index)
+        self.reduction = reduction
+        self.label_smoothing = float(label_smoothing)
+        self._refresh_pointers()
+
+    def _refresh_pointers(self):
+        self.weight_ptr = 0 if self.weight is None else self.weight.data_ptr()
+        self.pixel_weight_ptr = 0 if self.pixel_weight is None else self.pixel_weight.data_ptr()
+        self.pixel_weight_shape = "" if self.pixel_weight is None else "x".join(str(d) for d in self.pixel_weight.shape)
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)      # .to(device) / .cuda() move the buffers
+        self._refresh_pointers()
+        return out
+
+    def set_pixel_weight(self, t):
+        if t is None:
+            self.pixel_weight = None
+        else:
+            if not torch.is_tensor(t) or t.dim() != 3:
+                raise ValueError("CrossEntropyLoss.set_pixel_weight: a (B,H,W) tensor or None")
+            cur = self.pixel_weight
+            if cur is None or cur.shape != t.shape or cur.device != t.device:
+                self.pixel_weight = torch.empty(t.shape, device=t.device, dtype=torch.float32)
+            self.pixel_weight.copy_(t.detach())
+        self._refresh_pointers()
+        return self
+
+    def forward(self, logits, labels):
+        self._refresh_pointers()
+        return ops.cross_entropy(logits, labels.long(), self.ignore_index, weight=self.weight,
+                                 label_smoothing=self.label_smoothing, reduction=self.reduction,
+                                 pixel_weight=self.pixel_weight)
+
+    def extra_repr(self):
+        return (f"ignore_index={self.ignore_index}, reduction={self.reduction!r}, label_smoothing={self.label_smoothing}, "
+                f"weight={self.weight is not None}, pixel_weight={None if self.pixel_weight is None else tuple(self.pixel_weight.shape)}")

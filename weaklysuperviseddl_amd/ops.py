@@ -1812,6 +1812,47 @@ class _SoftmaxCE(torch.autograd.Function):
         return out, None, None
 
 
+_CE_REDUCTIONS = {"mean": 0, "sum": 1, "none": 2}
+
+
+class _SoftmaxCEEx(torch.autograd.Function):
+    """nn.CrossEntropyLoss(weight, ignore_index, reduction, label_smoothing) with an optional pixel weight: the same kernel
+    with its options on (wsdl_softmax_ce_ex_fwd_bwd).  The gradient flows into the logits only."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index, weight, pixel_weight, label_smoothing, reduction):
+        logits = _dense(logits, "logits")
+        labels = _req(labels, "labels", torch.int64).contiguous()
+        B, Cc, H, W = logits.shape
+        if tuple(labels.shape) != (B, H, W):
+            raise WsdlError(f"cross entropy: labels {tuple(labels.shape)} do not match logits {tuple(logits.shape)}")
+        none = reduction == 2
+        loss = torch.empty((B, H, W) if none else (), device=logits.device, dtype=torch.float32)
+        need = logits.requires_grad
+        dl = torch.empty_like(logits) if need else None
+        inv = None if none else torch.empty(1, device=logits.device, dtype=torch.float32)
+        ws = workspace(lib().wsdl_reduce_workspace(), logits.device)
+        check(lib().wsdl_softmax_ce_ex_fwd_bwd(_p(logits), _p(labels), _p(loss), _p(dl), _p(inv), B, Cc, H, W, 1.0,
+                                               int(ignore_index), _p(weight), _p(pixel_weight), float(label_smoothing),
+                                               int(reduction), _p(ws), ws.numel(), _stream()))
+        ctx.none = none
+        ctx.save_for_backward(dl, inv)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dl, inv = ctx.saved_tensors
+        out = torch.empty_like(dl)
+        if ctx.none:
+            B, Cc, H, W = dl.shape
+            check(lib().wsdl_scale_by_pixel(_p(dl), _p(_dense(g, "upstream gradient")), _p(out), B, Cc, H, W, _stream()))
+        else:
+            sc = torch.empty_like(inv)
+            check(lib().wsdl_mul(_p(_dense(g.reshape(1))), _p(inv), _p(sc), 1, _stream()))      # upstream gradient x 1 / denominator
+            check(lib().wsdl_scale_by_device_scalar(_p(dl), _p(sc), _p(out), dl.numel(), _stream()))
+        return out, None, None, None, None, None, None
+
+
 class _PairwiseAffinityLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, preds, image, window, sigma_color, sigma_space, apply_softmax, normalise, cache=None):
@@ -2263,8 +2304,58 @@ def add_act(a, b, relu=False):
     return _AddAct.apply(a, b, bool(relu))
 
 
-def cross_entropy(logits, labels, ignore_index=-100):
-    return _SoftmaxCE.apply(logits, labels, ignore_index)
+def check_cross_entropy_options(reduction, label_smoothing):
+    """ValueError for a reduction or a smoothing factor the cross entropy does not know (no device needed)."""
+    if reduction not in _CE_REDUCTIONS:
+        raise ValueError(f"cross_entropy: reduction {reduction!r}: 'mean', 'sum' or 'none'")
+    if isinstance(label_smoothing, bool) or not isinstance(label_smoothing, (int, float)) or not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError(f"cross_entropy: label_smoothing {label_smoothing!r} must be a number in [0, 1]")
+
+
+def cross_entropy(logits, labels, ignore_index=-100, *, weight=None, label_smoothing=0.0, reduction="mean",
+                  pixel_weight=None):
+    """``F.cross_entropy`` on (B,C,H,W) logits and int64 (B,H,W) labels, forward and gradient in one kernel.
+
+    ``weight`` (C,) float32 class weights, ``label_smoothing`` in [0, 1] and ``reduction`` 'mean' | 'sum' | 'none' are
+    PyTorch's; ``pixel_weight`` (B,H,W) float32, finite and >= 0 (not checked on the device), multiplies the loss of each
+    pixel - a pixel of weight 0 is an ignored pixel.  'mean' divides by the sum of ``pixel_weight * weight[label]`` over
+    the pixels that are not ignored (PyTorch's denominator: the target classes only, also with smoothing); where that is
+    0 the result is NaN.  A label outside [0, C) other than ``ignore_index`` gives NaN ('none': at that pixel only).
+    Weights are constants: the gradient flows into ``logits`` only.  With every option at its default this is the plain
+    kernel call (wsdl_softmax_ce_fwd_bwd)."""
+    check_cross_entropy_options(reduction, label_smoothing)
+    if weight is None and pixel_weight is None and label_smoothing == 0.0 and reduction == "mean":
+        return _SoftmaxCE.apply(logits, labels, ignore_index)
+    if logits.dim() != 4:
+        raise WsdlError(f"cross entropy: logits {tuple(logits.shape)} must be (B,C,H,W)")
+    B, Cc, H, W = logits.shape
+    for t, name, shape in ((weight, "weight", (Cc,)), (pixel_weight, "pixel_weight", (B, H, W))):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise WsdlError(f"cross entropy: {name} must be a float32 tensor")
+        if tuple(t.shape) != shape:
+            raise WsdlError(f"cross entropy: {name} {tuple(t.shape)} must be {shape}")
+        if t.device != logits.device:
+            raise WsdlError(f"cross entropy: {name} is on {t.device}, the logits on {logits.device}")
+    weight = None if weight is None else weight.detach().contiguous()
+    pixel_weight = None if pixel_weight is None else pixel_weight.detach().contiguous()
+    return _SoftmaxCEEx.apply(logits, labels, ignore_index, weight, pixel_weight, float(label_smoothing),
+                              _CE_REDUCTIONS[reduction])
+
+
+def class_weights_from_labels(labels, C, ignore=None, mode="inverse"):
+    """float32 (C,) class weights on the device from the pixel counts n_c of int64 ``labels`` (``ignore`` left out):
+    ``mode='inverse'`` N / (C n_c) with N = sum_c n_c, ``'median'`` median(n) / n_c (the median of all C counts,
+    the ignored class counting as 0); a class without a pixel gets weight 0.  The counts are ``iou_counts(labels, labels, C, ignore)[..., 0]``;
+    no host synchronisation."""
+    if mode not in ("inverse", "median"):
+        raise ValueError(f"class_weights_from_labels: mode {mode!r}: 'inverse' or 'median'")
+    n = iou_counts(labels, labels, C, ignore)[0, :, 0].to(torch.float64)
+    if ignore is not None and 0 <= int(ignore) < int(C):
+        n = n * torch.tensor([float(c != int(ignore)) for c in range(int(C))], dtype=torch.float64).to(n.device, non_blocking=True)
+    num = n.sum() / float(C) if mode == "inverse" else torch.quantile(n, 0.5)      # the mean of the two middle counts for an even C
+    return torch.where(n > 0, num / n.clamp_min(1.0), torch.zeros_like(n)).to(torch.float32)
 
 
 class _LovaszSoftmax(torch.autograd.Function):
