@@ -60,13 +60,7 @@ const char* wsdl_target_arch(void);   /* "gfx950" */
  *                      on the training step, profiles/r04_notes.md; use it when gradients span more than 2^25 inside one tensor)
  *   conv_split     1*  0 = forward / input-gradient convolutions on the exact-fp32 MFMA kernels everywhere
  *   wgrad_split    1*  0 = weight gradients on the exact-fp32 MFMA kernels everywhere
- *   tile256        1*  256x128 workgroup tiles (512 threads) where they still give >= 256 workgroups
- *   tile64         1*  64x64 tiles for layers that give fewer than `tile_threshold` tiles of 128x64 (128 output rows at 32 x 32 x 16):
- *                      two four-wave workgroups per CU instead of one (round 6: 3-9 % per launch on layer2's convolutions)
- *   split_bk32     1*  K chunks of 32 in the small-tile split forms;   bk32  1*  same for the fp32 kernels
- *   ksplit_big     1*  128x128 tiles + 2 K slices for grids of 200..399 tiles with K >= 2048
  *   tile_threshold 400* workgroups below which the half-size pixel tile is used
- *   col_bands      1*  dilated convolutions: one pixel-tile range per output-column band (exact padding-tap skipping)
  *   xcd_map        1*  XCD-aware tile order of the split kernels (0 off, 1 auto, 10 + py forces py row groups)
  *   wgrad_min_tiles 1*  which shapes the fp16x2 weight-gradient kernel takes: from this many 128-wide N tiles on (rounds 2-5: 6 - from
  *                      one tile on the layer2 1x1 kernels were 20-30 % faster and the step 1 % slower: pre-split, reduce and amax
@@ -75,14 +69,6 @@ const char* wsdl_target_arch(void);   /* "gfx950" */
  *                      -1.4 % on the kernel sweep, +0.4 % on the step (half the traffic past L2 for the kernels beside it)
  *   group_tps10   45*  wsdl_conv2d_fwd_group: taps per K slice in tenths (45: a 9-tap problem in 2 slices, the others whole; 20 -
  *                      round 5's default: 4 and 2 slices, eight streams; same box 575.7 us at 45 against 638.6 at 20)
- *   tile_img_major 1*  pixel tiles taken image-fastest inside a column band: 1 = in the grouped forward launch only, 2 = in every
- *                      split launch with taps, 0 = off.  Tiles at the same place of different images run the same tap list;
- *                      bit-identical; grouped forward 601.0 -> 575.7 us, multi-source input gradient 693 -> 709 (hence 1, not 2)
- *   group_interleave 1* ... with the workgroups of its (problem, slice) streams interleaved, one stream per XCD when there are 8
- *   ms_rowfast     1*  wsdl_conv2d_dgrad_multi: XCD-aware tile order taken row tile fastest;  ms_py 0* = 4 row groups (1 / 2 / 4 / 8)
- *   bn_coop        0*  (64 = on for the 64-channel layers) channel-resident BatchNorm kernels with 4 / 2 workgroups per channel for layers of up to this many channels
- *                      (when the caller passes the `coop` counters): 64 channels at B=16, 64x64 forward 17.2 -> 13.8 us, backward
- *                      21.7 -> 16.2 us; two per channel at 128 / 256 channels LOSE 1-9 us to the hand-over (bn_coop_wide 0*)
  *   range_sentinel 0*  1 = the amax arguments of wsdl_bn_train_fwd / _bwd are (max, ~min channel maximum) pairs (wsdl_range_check)
  *   bn_resident    1*  channel-resident fused BatchNorm kernels where a channel fits one workgroup's registers (0 off, 1 = from
  *                      64 channels, n > 1 = from n channels; measured: resident wins at every channel count of the networks)
@@ -93,10 +79,7 @@ const char* wsdl_target_arch(void);   /* "gfx950" */
  *                      and staging instructions interleaved (branch-free body + scheduling directives) - both waves of a SIMD run
  *                      the same phase, so staging otherwise never overlaps the other wave's MFMAs; bit-identical, 2-8 % faster
  *                      per launch in isolation, +0.5 % on the (power-bound) step
- *   wgrad_blocks 768*  target workgroups of a weight-gradient launch;  wgrad_force_s 0*  fixed number of pixel splits
- *   wgrad_imbalance_split 1*  one more pixel split for the fp16x2 weight gradient of a dilated convolution whose outer taps do less
- *                      than 70 % of the centre tap's work (padding-only chunks are skipped): ASPP d12 463 -> 442 us, d24 357 -> 287
- *   wgrad_bk      16*  pixel chunk of the fp32 weight-gradient kernel (16 | 32)
+ *   wgrad_blocks 768*  target workgroups of a weight-gradient launch
  *   wgrad_direct   1*  fp16x2 weight-gradient kernel with the x operand's MFMA fragments loaded straight from global memory (no LDS, no
  *                      lane exchange for x; dY double-buffered in LDS, one barrier per chunk) where OW % 32 == 0, stride 1 and every
  *                      tap's column shift is a multiple of 4 elements (1x1, dilation 4 / 12 / 24 / 36): 7-10 % faster there, bit-identical;
@@ -124,7 +107,14 @@ const char* wsdl_target_arch(void);   /* "gfx950" */
  *  wgrad_tile64 - 64-row weight-gradient tiles; occupancy_cap.  Figures: profiles/r02_notes.md.  Round 4: t256_bk32 - K chunks of 32
  *  in the 256x128 form (1-2.6 % slower per step); wgrad_direct = 2 - the direct-fragment weight gradient for misaligned taps (0-7 %
  *  slower, spills); conv_mfma16 / wgrad_mfma16 = 0 - the 32x32x16 MFMA shape in the K-chunk-32 forward forms and in the fp16x2 weight
- *  gradient (2.2 % / 2 % slower on the step; v_mfma_f32_16x16x32_f16 is what those kernels run on).)
+ *  gradient (2.2 % / 2 % slower on the step; v_mfma_f32_16x16x32_f16 is what those kernels run on).
+ *  Rounds 5 and 6, removed whole: bn_coop / bn_coop_wide - several workgroups per channel in the resident BatchNorm kernels, waiting
+ *  for each other's partial sums (0.3 % of the step, off since it was written; profiles/r05_notes.md); the deferred slab reductions
+ *  of the weight gradients - one launch for all layers' slabs at the end of the backward pass (1.2 % slower in every grouping;
+ *  profiles/r06_notes.md); the timing-only and lane-pairing experiment builds of the split kernels (profiles/r06_notes.md).
+ *  One-off experiment switches hard-wired to their defaults (profiles/r05_notes.md, profiles/r06_notes.md): xcd_rowfast (off),
+ *  ms_rowfast (on), ms_py (4 row groups), group_interleave (on), wgrad_force_s (off), wgrad_bk (16), tile_img_major (grouped forward
+ *  only), bk32, split_bk32, ksplit_big, tile256, tile64, col_bands, stem_wgrad, wgrad_imbalance_split (all on).)
  * (* = default). */
 int wsdl_set_option(const char* name, int value);
 
@@ -276,31 +266,6 @@ int wsdl_conv2d_wgrad(const float* x, const float* dy, float* dw,
                       int stride, int pad, int dil, int accumulate,
                       long long x_bs, long long dy_bs, const float* x_amax, const float* dy_amax,
                       void* ws, size_t ws_bytes, wsdl_stream_t stream);
-/* Weight gradient with the slab reduction DEFERRED (round 6).  wsdl_conv2d_wgrad splits the pixel dimension over S workgroup
- * slabs and ends with a small launch that adds them in fixed order into dw - ~60 such launches per training step, 9-10 us each
- * for a few MB (launch and tail latency, not bandwidth).  The deferred form runs everything but that launch and fills *desc (a
- * HOST struct) with what is left to do; the caller collects the descriptors of many layers, uploads them as ONE device table
- * (block_begin = the running sum of nblocks) and runs wsdl_wgrad_reduce_multi when the gradients are needed - before the
- * optimiser step or a gradient bucket's all-reduce (reference: the loss.backward() / optimizer.step() pair of
- * TraditionalModel/SegmentationModel.py:110-111).  Same sums in the same order: bit-identical to wsdl_conv2d_wgrad.
- *   - the slabs live in `ws`: the caller keeps each layer's workspace untouched until the multi launch has run;
- *   - desc->kind < 0: nothing is pending (the call reduced by itself: a batch processed in slices);
- *   - two deferred gradients into the same dw must not share a multi launch (flush in between). */
-enum { WSDL_WGRAD_REDUCE_PLAIN = 0, WSDL_WGRAD_REDUCE_TILED = 1, WSDL_WGRAD_REDUCE_VEC4 = 2, WSDL_WGRAD_REDUCE_MANY = 3,
-       WSDL_WGRAD_REDUCE_TRANSPOSED = 4, WSDL_WGRAD_REDUCE_MANY16 = 5 };
-typedef struct wsdl_wgrad_reduce_desc {
-    const float* slab;       /* [S][Cout][taps*Cin]   (TRANSPOSED: [S][Cin][Cout]) */
-    float* dw;               /* [Cout][Cin][taps] */
-    unsigned long long live; /* bit t: tap t has slab data */
-    int S, Cout, Cin, T;
-    int accumulate, kind;
-    int grid_x, nblocks;     /* blocks of 256 threads this reduction takes (grid_x: its inner extent where it is 2-D) */
-    int block_begin, reserved;
-} wsdl_wgrad_reduce_desc;
-int wsdl_conv2d_wgrad_deferred(const float* x, const float* dy, float* dw, int B, int Cin, int H, int W,
-                               int Cout, int kh, int kw, int stride, int pad, int dil, int accumulate,
-                               long long x_bs, long long dy_bs, const float* x_amax, const float* dy_amax, void* ws,
-                               size_t ws_bytes, wsdl_wgrad_reduce_desc* desc, wsdl_stream_t stream);
 /* The weight gradient with PER-CHANNEL operands (round 6; both optional, NULL = as wsdl_conv2d_wgrad):
  *   x_chan_amax[Cin] / dy_chan_amax[Cout]: one maximum per channel of x / dY, as the channel-resident BatchNorm kernels publish
  *     them (wsdl_bn_train_fwd / _bwd chan_amax).  The fp16x2 kernels then scale each channel by its OWN power of two - exact (a
@@ -309,16 +274,13 @@ int wsdl_conv2d_wgrad_deferred(const float* x, const float* dy, float* dw, int B
  *   dy_presplit: dY already as the kernel's fp16 (high, low) rows [ceil(P / 32)][Cout][128 B], written by the BatchNorm backward that
  *     produced dY (wsdl_bn_train_bwd dy_presplit) with the scales of dy_chan_amax: dy_split16_kernel (one more read and write of
  *     dY per layer, 24 launches per training step) does not run.  wsdl_conv2d_wgrad_presplit_bytes: the buffer's size for a
- *     geometry, 0 where the weight gradient would not use it.
- *   desc_or_null: non-NULL = the deferred form (wsdl_conv2d_wgrad_deferred). */
+ *     geometry, 0 where the weight gradient would not use it. */
 size_t wsdl_conv2d_wgrad_presplit_bytes(int B, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int dil);
 int wsdl_conv2d_wgrad_ex(const float* x, const float* dy, float* dw, int B, int Cin, int H, int W,
                          int Cout, int kh, int kw, int stride, int pad, int dil, int accumulate,
                          long long x_bs, long long dy_bs, const float* x_amax, const float* dy_amax,
                          const float* x_chan_amax, const float* dy_chan_amax, const void* dy_presplit, void* ws,
-                         size_t ws_bytes, wsdl_wgrad_reduce_desc* desc_or_null, wsdl_stream_t stream);
-/* desc: DEVICE array of n entries; total_blocks = the sum of their nblocks */
-int wsdl_wgrad_reduce_multi(const wsdl_wgrad_reduce_desc* desc, int n, int total_blocks, wsdl_stream_t stream);
+                         size_t ws_bytes, wsdl_stream_t stream);
 
 /* out = max|x| over B images of per_image contiguous floats (batch stride x_bs elements, 0 = dense); zero_first != 0
  * zeroes `out` first (else the caller passes a zeroed scalar).  For tensors whose producer did not publish an amax
@@ -344,10 +306,6 @@ int wsdl_bn_train_fwd(const float* x, const float* gamma, const float* beta, flo
                       uint8_t* relu_mask /* optional (relu, HW % 8 == 0, y_bs % 4 == 0): B*C*HW/8 bytes, bit e%8 of byte
                                             e/8 = [y > 0] for the dense element index e - for relu = 3 of the backward */,
                       void* ws, size_t ws_bytes,
-                      int* coop /* optional: 2*C ZERO-INITIALISED ints that persist between calls, one region per stream.  Given
-                                   them, layers of few channels (option bn_coop: 0* = off, 64) run several workgroups per channel, which
-                                   hand their partial sums over through the workspace (64 channels at B=16, 64x64: 17.2 -> 13.8 us;
-                                   profiles/r05_notes.md); the kernel leaves the counters zeroed.  NULL: one workgroup per channel */,
                       float* chan_amax /* optional [C]: max|y| per CHANNEL (a plain store by the channel's workgroup; wants y_amax and
                                           wsdl_bn_channel_resident(B, C, HW, 0)) - the per-channel scales of the weight gradient that
                                           reads y as its x operand (wsdl_conv2d_wgrad_ex) */,
@@ -368,7 +326,7 @@ int wsdl_bn_train_bwd(const float* x, const float* dy, const float* y, const flo
                       long long dy_bs, long long y_bs,
                       float* dx_amax /* optional: atomicMax of max|dx| into a ZEROED device scalar */,
                       const uint8_t* relu_mask /* relu = 3 */,
-                      void* ws, size_t ws_bytes, int* coop /* as for the forward */,
+                      void* ws, size_t ws_bytes,
                       float* chan_amax /* optional [C]: max|dx| per channel (as for the forward; wsdl_bn_channel_resident(.., 1)) */,
                       void* dy_presplit /* optional: dx ALSO as the fp16 (high, low) rows the producing convolution's weight gradient
                                            reads ([B*HW / 32][C][128 B], each channel scaled by the power of two of its chan_amax;

@@ -34,6 +34,34 @@ def test_library_exports_every_declared_symbol():
     assert lib.wsdl_conv2d_wgrad_workspace(16, 2048, 32, 32, 256, 3, 3, 1, 12, 12) > 0
 
 
+OPTION_DEFAULTS = {
+    "conv_arith": 1, "conv_split": 1, "wgrad_split": 1, "conv_il": 1, "wgrad_chan_scale": 0, "range_sentinel": 0, "stem_kernel": 1,
+    "wgrad_direct": 1, "wgrad_dyraw": 1, "layercam_tail_mod": 32, "tile_threshold": 400, "ksplit_target": 512, "ksplit_max": 8,
+    "ksplit_min_chunks": 4, "group_tps10": 45, "wgrad_blocks": 768, "wgrad_min_tiles": 1, "wgrad_xcd": 1, "xcd_map": 1,
+    "bn_resident": 1, "bn_wide_c": 512,
+}
+REMOVED_OPTIONS = (
+    "bn_coop", "bn_coop_wide", "xcd_rowfast", "ms_rowfast", "ms_py", "group_interleave", "wgrad_force_s", "wgrad_bk", "tile_img_major",
+    "bk32", "split_bk32", "ksplit_big", "tile256", "tile64", "col_bands", "stem_wgrad", "wgrad_imbalance_split",
+)
+
+
+def test_option_names_are_the_documented_ones():
+    """wsdl_set_option (host code) takes the 21 options the header's table documents, at their defaults, and refuses every name
+    removed with the experiments it switched - naming it in wsdl_last_error()."""
+    from weaklysuperviseddl_amd import _lib
+    lib = _lib.lib()
+    assert len(OPTION_DEFAULTS) == 21 and not set(OPTION_DEFAULTS) & set(REMOVED_OPTIONS)
+    table = open(os.path.join(ROOT, "include", "wsdl_hip.h")).read().split("Process-wide options.")[1].split("(Options measured slower")[0]
+    for name, default in OPTION_DEFAULTS.items():
+        assert lib.wsdl_set_option(name.encode(), default) == 0, name
+        assert re.search(r"\b%s\s+%d\*" % (name, default), table), name        # the header states the same default
+    for name in REMOVED_OPTIONS:
+        assert lib.wsdl_set_option(name.encode(), 1) != 0, name
+        assert name in lib.wsdl_last_error().decode(), name
+        assert not re.search(r"^ \*   %s\b" % name, table, flags=re.M), name
+
+
 def test_header_cites_reference_lines():
     src = open(os.path.join(ROOT, "include", "wsdl_hip.h")).read()
     for cite in ("AlternatingDirectionCutLoss.py:65-105", "AlternatingDirectionBoundaryLoss.py:12-70", "LayerCAM.py:52-76",

@@ -365,33 +365,3 @@ def test_range_sentinel_speaks_under_replay_and_can_switch_the_guards_on(dev, mo
         optim.RANGE_GUARD_ACTIVE[0] = False
         ops.set_option("conv_arith", 1)
         ops.set_option("wgrad_chan_scale", 0)
-
-
-@pytest.mark.parametrize("group_mb", [100000, 8])
-def test_deferred_slab_reductions_equal_the_per_layer_ones(dev, group_mb):
-    """wsdl_conv2d_wgrad_deferred + wsdl_wgrad_reduce_multi (round 6): every weight gradient leaves its pixel slabs un-reduced and
-    the pending reductions run as ONE launch at the end of the backward pass (or in groups of a few MB) - the same sums in the
-    same order as the per-layer launches, so parameters, Adam moments and losses are bit-identical, eagerly and replayed from
-    a plan.  (Off by default: measured 1.2 % slower on the training step, profiles/r06_notes.md.)"""
-    from weaklysuperviseddl_amd import ops
-    batches = [_batch(4, 64, dev, s) for s in (1, 2)]
-    m0, o0, l0, _ = _run(dev, False, 4, batches)
-    old = ops.WGRAD_DEFER[0], ops.WGRAD_DEFER_BYTES[0]
-    ops.WGRAD_DEFER[0], ops.WGRAD_DEFER_BYTES[0] = True, group_mb << 20
-    ops._reduce_tables.clear()
-    try:
-        m1, o1, l1, _ = _run(dev, False, 4, batches)
-        tables = len(ops._reduce_tables)
-        m2, o2, l2, st = _run(dev, True, 6, batches)
-    finally:
-        ops.WGRAD_DEFER[0], ops.WGRAD_DEFER_BYTES[0] = old
-    assert tables >= (1 if group_mb > 1000 else 2), tables       # descriptor tables were built: the deferred path really ran
-    assert l0 == l1
-    for a, b in zip(_state(m0, o0), _state(m1, o1)):
-        assert torch.equal(a, b)
-    # ... and a planned run with deferral replays (the multi-reduce launch and its descriptor table are part of the plan)
-    assert st is not None and st.disabled is None and st.replays >= 2, getattr(st, "disabled", None)
-    m3, o3, l3, _ = _run(dev, False, 6, batches)
-    assert l2 == l3
-    for a, b in zip(_state(m2, o2), _state(m3, o3)):
-        assert torch.equal(a, b)

@@ -7,7 +7,7 @@ import torch
 from weaklysuperviseddl_amd import ops
 
 dev = torch.device("cuda:0")
-if "--opt" in sys.argv:                 # --opt name=value[,name=value]: library options (e.g. tile_img_major=0)
+if "--opt" in sys.argv:                 # --opt name=value[,name=value]: library options (e.g. group_tps10=20)
     i = sys.argv.index("--opt")
     for kv in sys.argv[i + 1].split(","):
         k, v = kv.split("=")

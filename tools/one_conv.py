@@ -62,8 +62,7 @@ def main():
         x.zero_(); w.zero_(); dy.zero_()
         wf, wd = ops.prep_weights(w)
     # the weight gradient AS THE TRAINING STEP RUNS IT (round 6): its dY operand comes from a BatchNorm backward, which publishes the
-    # per-channel maxima and - where the launch reads them - the pre-split rows (no dy_split16 pass); the slab reduction is deferred
-    # (in the step: one launch for all layers; here one launch for this layer - an upper bound of its share)
+    # per-channel maxima and - where the launch reads them - the pre-split rows (no dy_split16 pass)
     cam = pre = None
     if a.which == "wgrad" and not a.plain:
         gamma, beta = torch.rand(Cout, device=dev) + 0.5, torch.zeros(Cout, device=dev)
@@ -84,8 +83,7 @@ def main():
         elif a.plain:
             ops.conv2d_wgrad(x, dy, w.shape, s, pad, d)
         else:
-            ops.conv2d_wgrad(x, dy, w.shape, s, pad, d, out=dw, defer=True, dy_camax=cam, dy_presplit=pre)
-            ops.flush_wgrad_reduces(dev)
+            ops.conv2d_wgrad(x, dy, w.shape, s, pad, d, out=dw, dy_camax=cam, dy_presplit=pre)
     torch.cuda.synchronize()
 
 

@@ -85,8 +85,6 @@ extern std::atomic<int> g_plans_recording;     // host threads between wsdl_plan
 extern Opt g_bn_resident;
 extern Opt g_bn_wide_c;     // "bn_wide_c": resident BatchNorm kernels with 1024 threads up to this channel count
 extern Opt g_layercam_tail_mod;   // "layercam_tail_mod": see layercam_optim.hip
-extern Opt g_bn_coop;             // "bn_coop": several workgroups per channel in the resident BatchNorm kernels up to this channel count (0 off)
-extern Opt g_bn_coop_wide;        // "bn_coop_wide": ... and two per channel at 256 channels
 extern Opt g_range_sentinel;      // "range_sentinel": the amax pointers of the BatchNorm entry points are (max, ~min piece max) PAIRS
 
 // deterministic two-stage sum: stage 1 kernels write `n` float partials, stage 2 adds them in order.

@@ -11,8 +11,6 @@ namespace wsdl {
 
 static thread_local char g_err[512] = "";
 Opt g_range_sentinel{0};
-Opt g_bn_coop{0}, g_bn_coop_wide{0};      // off by default: four workgroups per channel pay at 64 channels only (0.3 % of the step), and
-                                            // workgroups that wait for each other are not something to have on by default (r05_notes.md)
 
 void set_error(const char* fmt, ...) {
     va_list ap;
@@ -111,7 +109,7 @@ const char* wsdl_last_launches(void) {      // this thread's launches since the 
 }
 
 const char* wsdl_last_error(void) { return wsdl::g_err; }
-int wsdl_version(void) { return 100; }
+int wsdl_version(void) { return 200; }
 const char* wsdl_target_arch(void) { return "gfx950"; }
 
 const char* wsdl_prof_class_name(int cls) {

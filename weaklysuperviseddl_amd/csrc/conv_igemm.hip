@@ -986,9 +986,7 @@ __global__ __launch_bounds__(kThreads, 3) void conv_wgrad_fast_kernel(WgradP p) 
 
 // slab[z][co][tap*Cin+ci] summed over z in order -> dw[co][ci][tap]
 // live: bit t set = tap t has slab data (taps that read only padding everywhere are not computed by the split kernel)
-// Each reduction is a device body of (its arguments, which of `nblocks` 256-thread blocks this is): the per-layer kernels below
-// run one body on their own grid, wgrad_reduce_multi_kernel (round 6) runs the bodies of MANY layers in one launch - the same
-// sums in the same order, so the two are bit-identical.
+// Each reduction is a device body of (its arguments, which of `nblocks` 256-thread blocks this is), run by the kernel below it.
 __device__ __forceinline__ void wgrad_reduce_plain_body(const float* __restrict__ slab, float* __restrict__ dw, int S, int Cout, int Cin,
                                                         int T, int accumulate, unsigned long long live, long long lb, long long nblocks) {
     const long long total = (long long)Cout * Cin * T;
@@ -1153,75 +1151,6 @@ __global__ void wgrad_reduce_tiled_kernel(const float* __restrict__ slab, float*
     wgrad_reduce_tiled_body(slab, dw, S, Cout, Cin, T, accumulate, live, blockIdx.x, blockIdx.y, tile);
 }
 
-// Role-swapped 1x1 weight gradients (wgrad_role_swap): the slabs hold dW^T [Cin][Cout]; dw[co][ci] (+)= sum_z slab[z][ci][co]
-// with the slabs added in wgrad_reduce_vec4_kernel's order (what the two-launch form - that kernel into a scratch matrix, then
-// transpose_add_kernel - computes): 32 x 32 tiles through LDS, both sides in 128-byte runs.  256 threads as (32, 8).
-__device__ __forceinline__ void wgrad_reduce_transposed_body(const float* __restrict__ slab, float* __restrict__ dw, int S, int Cout,
-                                                             int Cin, int accumulate, int co_tile, int ci_tile, float* tile /* [32 * 33] */) {
-    const int co0 = co_tile * 32, ci0 = ci_tile * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const long long total = (long long)Cout * Cin;
-    for (int r = ty; r < 32; r += 8) {
-        const int ci = ci0 + r, co = co0 + tx;
-        float s = 0.f;
-        if (ci < Cin && co < Cout) {
-            const long long idx = (long long)ci * Cout + co;
-            int z = 0;
-            for (; z + 4 <= S; z += 4)
-                s += (slab[(long long)z * total + idx] + slab[(long long)(z + 1) * total + idx]) +
-                     (slab[(long long)(z + 2) * total + idx] + slab[(long long)(z + 3) * total + idx]);
-            for (; z < S; ++z) s += slab[(long long)z * total + idx];
-        }
-        tile[r * 33 + tx] = s;
-    }
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-        const int co = co0 + r, ci = ci0 + tx;
-        if (co < Cout && ci < Cin) {
-            const long long o = (long long)co * Cin + ci;
-            dw[o] = accumulate ? dw[o] + tile[tx * 33 + r] : tile[tx * 33 + r];
-        }
-    }
-}
-
-// The slab reductions of MANY weight gradients in one launch (round 6; wsdl_wgrad_reduce_multi).  A training step ran ~60 of
-// the kernels above, one behind each weight-gradient launch on the side stream: 9-10 us each for a few MB - launch and tail
-// latency, not bandwidth (0.69 ms per step).  With wsdl_conv2d_wgrad_deferred the weight-gradient launches leave their slabs
-// in place and hand back a descriptor; the caller runs ALL pending reductions as one grid when the gradients are needed (the
-// optimiser step, a gradient bucket's all-reduce).  Block b belongs to the last entry whose block_begin <= b.
-__global__ __launch_bounds__(256) void wgrad_reduce_multi_kernel(const wsdl_wgrad_reduce_desc* __restrict__ d, int n) {
-    __shared__ float sm[32 * 33];
-    const int b = blockIdx.x;
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (d[mid].block_begin <= b) lo = mid; else hi = mid - 1;
-    }
-    const wsdl_wgrad_reduce_desc q = d[lo];
-    const int lb = b - q.block_begin;
-    switch (q.kind) {
-        case WSDL_WGRAD_REDUCE_TILED:
-            wgrad_reduce_tiled_body(q.slab, q.dw, q.S, q.Cout, q.Cin, q.T, q.accumulate, q.live, lb % q.grid_x, lb / q.grid_x, sm);
-            break;
-        case WSDL_WGRAD_REDUCE_VEC4:
-            wgrad_reduce_vec4_body(reinterpret_cast<const float4*>(q.slab), reinterpret_cast<float4*>(q.dw), q.S,
-                                   (long long)q.Cout * q.Cin * q.T / 4, q.accumulate, lb, q.nblocks);
-            break;
-        case WSDL_WGRAD_REDUCE_MANY:
-            wgrad_reduce_many_body(q.slab, q.dw, q.S, q.Cout, q.Cin, q.T, q.accumulate, q.live, lb, sm);
-            break;
-        case WSDL_WGRAD_REDUCE_TRANSPOSED:
-            wgrad_reduce_transposed_body(q.slab, q.dw, q.S, q.Cout, q.Cin, q.accumulate, lb % q.grid_x, lb / q.grid_x, sm);
-            break;
-        case WSDL_WGRAD_REDUCE_MANY16:
-            wgrad_reduce_many16_body(q.slab, q.dw, q.S, q.Cout, q.Cin, q.T, q.accumulate, q.live, lb, sm);
-            break;
-        default:
-            wgrad_reduce_plain_body(q.slab, q.dw, q.S, q.Cout, q.Cin, q.T, q.accumulate, q.live, lb, q.nblocks);
-            break;
-    }
-}
-
 // w[co][ci][tap] -> fwd[(tap*Cin+ci)][co], dgrad[(tap*Cout+co)][ci]   (generic, uncoalesced reads)
 __global__ void prep_weights_kernel(const float* __restrict__ w, float* __restrict__ fwd,
                                     float* __restrict__ dg, int Cout, int Cin, int T) {
@@ -1377,17 +1306,11 @@ double wgrad_executed_fraction(int P, int OH, int ow0, int own, int H, int W, in
 }
 
 wsdl::Opt g_tile_threshold{400};   // blocks below which the half-size pixel tile is used
-wsdl::Opt g_xcd_rowfast{0};               // experiment: row-tile-fastest XCD order for every XCD-mapped launch of the split kernels
-wsdl::Opt g_ms_rowfast{1}, g_ms_py{0};   // multi-source launches: row-tile-fastest XCD order; forced number of row groups (0 = auto)
-wsdl::Opt g_group_interleave{1};          // grouped forward: stream-interleaved workgroup order when the streams fill the XCDs evenly
 wsdl::Opt g_group_tps10{45};       // "group_tps10": taps per K slice of a grouped forward launch, in tenths.  20 (round 5's default): d12 in 4 slices,
                               // d24 in 2 = eight streams, one per XCD; 45 (round 6): d12 in 2 slices, the others whole - 67 MB of slabs less, problem-major
                               // order.  Round 5: 648 / 623 / 636 us at 20 / 30 / 45 on one box, 662 / 713 at 20 / 30 on another; round 6 (image-major
                               // tile order on / off): 638.6 / 634.2 at 20, 575.7 / 601.0 at 45, 1058 at 60 (d12 whole: workgroups of 9 taps)
 constexpr int kNumCU = 256, kLdsPerCU = 160 * 1024;
-
-wsdl::Opt g_wgrad_bk{16};   // pixel chunk of the fast weight-gradient kernel: 16 or 32
-wsdl::Opt g_bk32{1};        // K-chunk of 32 for the small-tile configurations (half the barriers per MFMA)
 
 template <int BM, int BN, int WM, int BK>
 int launch_fast(const ConvP& p, hipStream_t s, dim3 grid) {
@@ -1409,15 +1332,13 @@ int launch_fast(const ConvP& p, hipStream_t s, dim3 grid) {
 wsdl::Opt g_conv_split{1};
 wsdl::Opt g_conv_arith{1};    // arithmetic of the split kernels: 1 = fp16x2 (three MFMAs per product, per-tensor power-of-two
                          // scales), 0 = bf16x3 (six MFMAs, no scales) - see conv_split.h
-wsdl::Opt g_split_bk32{1};    // K chunk 32 on the small-tile split configurations
 bool split_eligible(int rows, int kc, int T) {
     return g_conv_split && kc % 16 == 0 && T <= 9 && split_layout_bytes(g_conv_arith, (long long)T * kc, rows) < (1ll << 31);
 }
 
-wsdl::Opt g_tile_img_major{1};   // pixel tiles image-fastest inside a column band (conv_split.h, "image-major tile order"): 0 off, 1 = in the grouped
-                                 // forward launch (ASPP) only - the default, 2 = in every split launch with taps.  Measured (profiles/r06_notes.md):
-                                 // grouped forward 575.7 us with / 601.0 without at group_tps10 = 45; multi-source input gradient 709 with / 693
-                                 // without (and 2.15 / 1.85 GB past L2): there it stays off; plain dilated launches: no difference
+// Pixel tiles image-fastest inside a column band (conv_split.h, "image-major tile order"): in the grouped forward launch (ASPP) only.
+// Measured (profiles/r06_notes.md): grouped forward 575.7 us with / 601.0 without at group_tps10 = 45; multi-source input gradient
+// 709 with / 693 without (and 2.15 / 1.85 GB past L2): there it stays off; plain dilated launches: no difference
 wsdl::Opt g_xcd_map{1};        // XCD-aware tile order of the split kernels: 0 off, 1 auto (by operand bytes), 10 + py forced
 // row groups of the XCD-aware tile order: minimise (weight bytes x pixel groups + activation bytes x row groups); only
 // worth a re-labelling when that beats the launch order (every XCD streams all weights, 1/8 of the pixels) by > 10 %
@@ -1444,7 +1365,7 @@ int launch_split(const ConvP& p_in, hipStream_t s, dim3 grid) {
     ConvP p = p_in;
     grid.z = p.ksplit > 1 ? p.ksplit : 1;
     p.xcd_py = choose_xcd_py(p, grid.x, grid.y);
-    p.tile_img_major = g_tile_img_major == 2 && p.KH * p.KW > 1;
+    p.tile_img_major = 0;
     constexpr bool MF = BK == 32;
     WSDL_TRACE("split<%d,%d,%d> ar=%d %s ks=%d xcd_py=%d nb=%d grid=%ux%ux%u", BM, BN, BK, (int)g_conv_arith,
                (MF && g_conv_arith) ? "mfma16x16x32" : "mfma32x32x16", p.ksplit, p.xcd_py, p.nb, grid.x, grid.y, grid.z);
@@ -1459,10 +1380,10 @@ int launch_split(const ConvP& p_in, hipStream_t s, dim3 grid) {
 }
 
 wsdl::Opt g_conv_il{1};        // 256x128 form: MFMAs and staging instructions interleaved in every wave's stream (conv_split.h, IL)
-wsdl::Opt g_tile64{1};         // 64 x 64 tiles for 128-row layers that give < 400 tiles of 128 x 64 (round 6): two four-wave workgroups per CU instead of
-                               // one - l2.conv1 forward / l2.conv3 input gradient 20.2 -> 18.3 us, l2.conv2 38.8 -> 37.7 / 38.1 -> 36.6; ~20 us of the step
-wsdl::Opt g_tile256{1};        // 256x128 tiles, 512 threads, one workgroup per CU where that still gives >= 256 workgroups: 4-5 % faster on layer4
-                          // (128x256 measured 1 % behind it)
+// 64 x 64 tiles for 128-row layers that give < 400 tiles of 128 x 64 (round 6): two four-wave workgroups per CU instead of
+// one - l2.conv1 forward / l2.conv3 input gradient 20.2 -> 18.3 us, l2.conv2 38.8 -> 37.7 / 38.1 -> 36.6; ~20 us of the step
+// 256x128 tiles, 512 threads, one workgroup per CU where that still gives >= 256 workgroups: 4-5 % faster on layer4
+// (128x256 measured 1 % behind it)
 // (The 256x128 form with K chunks of 32 - "t256_bk32", 169-228 registers and 99-111 KB of LDS - was an option until round 4: faster
 // alone (+3.5 % per kernel), 1-2.6 % slower on the STEP, where it leaves no room for the weight-gradient workgroups beside it
 // (818.6 -> 828.2, 824 -> 845 img/s on two boxes with the 16-deep form, profiles/r02_notes.md).  Removed.)
@@ -1473,14 +1394,14 @@ int launch_split_256x128(const ConvP& p_in, hipStream_t s) {
     ConvP p = p_in;
     dim3 grid(p.grid_x > 0 ? p.grid_x : wsdl::cdiv(p.P, 128), wsdl::cdiv(p.Cout, 256), p.ksplit > 1 ? p.ksplit : 1);
     p.xcd_py = choose_xcd_py(p, grid.x, grid.y);
-    p.xcd_rowfast = g_xcd_rowfast;
-    p.tile_img_major = g_tile_img_major == 2 && (p.KH * p.KW > 1 || p.nsrc > 0);
-    if (p.nsrc > 0 && g_ms_rowfast && grid.y % 2 == 0 && ((long long)grid.x * grid.y) % 8 == 0) {
+    p.xcd_rowfast = 0;
+    p.tile_img_major = 0;
+    if (p.nsrc > 0 && grid.y % 2 == 0 && ((long long)grid.x * grid.y) % 8 == 0) {
         // the sources' weights together are the larger operand and every workgroup streams all of them: let the workgroups
         // an XCD runs at once span row tiles as well as pixel tiles
         // py row groups: an XCD owns grid.y / py row tiles x grid.x * py / 8 pixel tiles and runs ~32 of them at once, row tile
         // fastest.  ASPP's 8 x 128 tiles, same box: pixel-fastest order 792 us; row-fastest py = 1 / 2 / 4: 774 / 804 / 710 us
-        int py = g_ms_py > 0 ? g_ms_py : 4;
+        int py = 4;
         while (py > 1 && (grid.y % py || grid.x % (8 / py))) py /= 2;
         if (grid.y % py == 0 && grid.x % (8 / py) == 0) {
             p.xcd_py = py;
@@ -1513,14 +1434,14 @@ int launch_cfg(const ConvP& p, hipStream_t s, bool aligned, bool split) {
     constexpr bool kSmallTile = BM * BN <= 128 * 64;      // K chunks of 32 only where registers / LDS allow them
     if (split) {
         if constexpr (kSmallTile) {
-            if (g_split_bk32 && p.Cin % 32 == 0) {
+            if (p.Cin % 32 == 0) {
                 return launch_split<BM, BN, WM, 32>(p, s, grid);
             }
         }
         return launch_split<BM, BN, WM, 16>(p, s, grid);
     } else if (aligned) {
         if constexpr (kSmallTile) {
-            if (g_bk32 && p.Cin % 32 == 0) {
+            if (p.Cin % 32 == 0) {
                 return launch_fast<BM, BN, WM, 32>(p, s, grid);
             }
         }
@@ -1538,25 +1459,21 @@ int launch_cfg(const ConvP& p, hipStream_t s, bool aligned, bool split) {
 // the tap-skipping imbalance averages out.  Cout <= 64: 64x256 / 64x128.
 // Split-K for grids that cannot fill the chip (small batches of small maps, e.g. the CAM path at B=8: 14x14 maps
 // give 25 pixel tiles): returns the number of K slices (1 = no split).  Only the fast path supports it.
-wsdl::Opt g_ksplit_big{1};   // 128x128 tiles + 2 K slices for grids of 200..399 such tiles with K >= 2048 (instead of 128x64
-                        // tiles): aux 3x3 505 -> 435 us, layer3 3x3 139 -> 128 us; shorter K loses to the slab reduce
 wsdl::Opt g_ksplit_target{512}, g_ksplit_max{8}, g_ksplit_min_chunks{4};   // small grids: workgroups aimed at, most K slices, fewest 32-deep chunks per slice
 int igemm_ksplit(int P, int Cout, int Cin, int T, int dil) {
     if (Cin % 32 != 0 || Cout % 4 != 0 || Cout <= 64) return 1;
     const long long blocks = (long long)wsdl::cdiv(P, 64) * wsdl::cdiv(Cout, 128);       // 128x64 tile
     const int nq = T * (Cin / 32);
-    if (g_ksplit_big) {
-        const long long b128 = (long long)wsdl::cdiv(P, 128) * wsdl::cdiv(Cout, 128);
-        if (b128 >= 200 && b128 < g_tile_threshold && nq >= 64) return 2;
-    }
+    // 128x128 tiles + 2 K slices for grids of 200..399 such tiles with K >= 2048 (instead of 128x64 tiles): aux 3x3 505 -> 435 us,
+    // layer3 3x3 139 -> 128 us; shorter K loses to the slab reduce
+    const long long b128 = (long long)wsdl::cdiv(P, 128) * wsdl::cdiv(Cout, 128);
+    if (b128 >= 200 && b128 < g_tile_threshold && nq >= 64) return 2;
     if (blocks >= 160 || nq < 8) return 1;
     long long s = g_ksplit_target / blocks;
     if (s > nq / g_ksplit_min_chunks) s = nq / g_ksplit_min_chunks;
     if (s > g_ksplit_max) s = g_ksplit_max;
     return s < 2 ? 1 : (int)s;
 }
-
-wsdl::Opt g_col_bands{1};   // launch dilated convs per output-column band (see column_bands)
 
 int launch_igemm(const ConvP& p_in, hipStream_t s, double flops, void* ws, size_t ws_bytes) {
     ConvP p = p_in;
@@ -1605,14 +1522,14 @@ int launch_igemm(const ConvP& p_in, hipStream_t s, double flops, void* ws, size_
     Band bands[8];
     int nb = 1;
     bands[0] = Band{0, p.OW};
-    if (aligned && g_col_bands) nb = column_bands(p.OW, p.W, p.ah, p.bh, p.ch, p.sh, p.KW, bands);
+    if (aligned) nb = column_bands(p.OW, p.W, p.ah, p.bh, p.ch, p.sh, p.KW, bands);
     // 256-row tiles only where the rows fill them (>= 90 %: not for 128-channel outputs)
-    const bool t256 = cfg == 0 && split && g_tile256 && p.Cout * 10 >= wsdl::cdiv(p.Cout, 256) * 256 * 9 &&
+    const bool t256 = cfg == 0 && split && p.Cout * 10 >= wsdl::cdiv(p.Cout, 256) * 256 * 9 &&
                       (long long)wsdl::cdiv(p.P, 128) * wsdl::cdiv(p.Cout, 256) * p.ksplit >= 256;
-    // 64 x 64 tiles ("tile64"): a 128-row layer at 32 x 32 x 16 is 256 tiles of 128 x 64 - ONE four-wave workgroup per CU,
+    // 64 x 64 tiles: a 128-row layer at 32 x 32 x 16 is 256 tiles of 128 x 64 - ONE four-wave workgroup per CU,
     // whose chunks run staging, barrier, fragment reads and MFMAs one after the other (profiles/r05_notes.md); 512 tiles of 64 x 64 put
     // two workgroups on a CU, out of phase
-    if (cfg == 1 && g_tile64 && split && g_conv_arith >= 1 && g_split_bk32 && p.Cin % 32 == 0 && p.Cout % 64 == 0 && p.ksplit == 1 &&
+    if (cfg == 1 && split && g_conv_arith >= 1 && p.Cin % 32 == 0 && p.Cout % 64 == 0 && p.ksplit == 1 &&
         p.nsrc == 0 && (long long)wsdl::cdiv(p.P, 64) * wsdl::cdiv(p.Cout, 128) < kWant)
         cfg = 4;
     const int bn_tile = cfg == 0 ? 128 : (cfg == 1 || cfg == 4) ? 64 : cfg == 2 ? 256 : 128;
@@ -1695,7 +1612,6 @@ constexpr int kStemIW = 2 * kStemHalf;              // row stride in LDS
 constexpr int kStemPlane = kStemIH * kStemIW;
 constexpr int kStemK = 148;                         // 147 + one zero row: K steps of 2
 wsdl::Opt g_stem_kernel{1};
-wsdl::Opt g_stem_wgrad{1};       // the stem's weight gradient on its own kernel (stem_wgrad7x7s2_kernel)
 
 __global__ __launch_bounds__(256, 2) void stem_conv7x7s2_kernel(ConvP p, int tiles_w, int tiles_h) {
     __shared__ float w_s[kStemK * 64];              // [k][cout]
@@ -1824,7 +1740,6 @@ void wgrad_tile(int Cout, int Cin, int* BM, int* BN, bool* fast) {
 }
 
 wsdl::Opt g_wgrad_split{1};       // weight gradients on the bf16x3-split 32-pixel-chunk kernel where the shape allows (conv_split.h)
-wsdl::Opt g_wgrad_force_s{0};     // experiments: fixed number of pixel splits
 wsdl::Opt g_wgrad_dyraw{1};       // direct-fragment kernel: dY read as fp32 and split while staged (no dy_split16_kernel pass)
 wsdl::Opt g_wgrad_chan_scale{0};  // fp16x2 weight-gradient kernels: one power-of-two scale per CHANNEL of x and of dY (a pre-pass takes the maxima)
 wsdl::Opt g_wgrad_direct{1};      // x fragments of the split weight-gradient kernel straight from global memory (conv_wgrad_split16d_kernel)
@@ -1873,7 +1788,6 @@ double wgrad_tap_balance(int H, int OH, int kh, int stride, int pad, int dil) {
     return hi > 0 ? (double)lo / (double)hi : 1.0;
 }
 
-wsdl::Opt g_wgrad_imbalance_split{1};   // one more pixel split for tap-imbalanced launches (wgrad_splits)
 // n_live: N counted over live taps only (the split kernel's dead-tap workgroups exit at once); tap_balance: wgrad_tap_balance
 int wgrad_splits(int Cout, int Cin, int N, int P, int n_live, double tap_balance = 1.0) {
     int BM, BN;
@@ -1882,7 +1796,6 @@ int wgrad_splits(int Cout, int Cin, int N, int P, int n_live, double tap_balance
     long long tiles = (long long)wsdl::cdiv(Cout, BM) * wsdl::cdiv(N, BN);
     const int chunks = wsdl::cdiv(P, 32);
     const long long smax = std::max<long long>(1, std::min<long long>(256, chunks / 8));
-    if (g_wgrad_force_s > 0) return (int)std::min<long long>(g_wgrad_force_s, smax);
     if (wgrad_chunk32(Cout, Cin, N)) {
         tiles = (long long)wsdl::cdiv(Cout, BM) * wsdl::cdiv(std::max(n_live, BN), BN);
         // two workgroups per CU (one 53 KB LDS image each): fill whole rounds of 512 slots
@@ -1899,7 +1812,7 @@ int wgrad_splits(int Cout, int Cin, int N, int P, int n_live, double tap_balance
         // centre tap's work the round model above (equal workgroups) picks too few, too long workgroups - one more split lets
         // the dispatcher even them out (same box: ASPP d12 463 -> 442 us, d24 357 -> 287 at 32 x 32; d24 895 -> 819, d36 714 ->
         // 541 at 64 x 64; the balanced shapes lose 5-20 % with it)
-        if (g_wgrad_imbalance_split && tap_balance < 0.7 && n_live > BN && best_s + 1 <= smax) ++best_s;
+        if (tap_balance < 0.7 && n_live > BN && best_s + 1 <= smax) ++best_s;
         return (int)best_s;
     }
     long long s0 = (g_wgrad_blocks + tiles - 1) / tiles;
@@ -1945,22 +1858,31 @@ bool wgrad_role_swap(int Cin, int Cout, int kh, int kw, int stride, int pad) {
     return kh == 1 && kw == 1 && stride == 1 && pad == 0 && !wgrad_chunk32(Cout, Cin, Cin) && wgrad_chunk32(Cin, Cout, Cout);
 }
 
-// one reduction as its own launch (the per-layer form)
-int wgrad_reduce_one(const wsdl_wgrad_reduce_desc& d, hipStream_t s) {
+// the reduction over a weight gradient's pixel slabs: which kernel, on how many 256-thread blocks
+enum { WGRAD_REDUCE_PLAIN = 0, WGRAD_REDUCE_TILED, WGRAD_REDUCE_VEC4, WGRAD_REDUCE_MANY, WGRAD_REDUCE_MANY16 };
+struct WgradReduce {
+    const float* slab;       // [S][Cout][taps*Cin]
+    float* dw;               // [Cout][Cin][taps]
+    unsigned long long live; // bit t: tap t has slab data
+    int S, Cout, Cin, T;
+    int accumulate, kind;
+    int grid_x, nblocks;     // blocks of 256 threads (grid_x: the inner extent where the grid is 2-D)
+};
+int wgrad_reduce_one(const WgradReduce& d, hipStream_t s) {
     switch (d.kind) {
-        case WSDL_WGRAD_REDUCE_TILED:
+        case WGRAD_REDUCE_TILED:
             hipLaunchKernelGGL(wgrad_reduce_tiled_kernel, dim3(d.grid_x, d.Cout), dim3(256), 0, s, d.slab, d.dw, d.S, d.Cout, d.Cin, d.T,
                                d.accumulate, d.live);
             break;
-        case WSDL_WGRAD_REDUCE_VEC4:
+        case WGRAD_REDUCE_VEC4:
             hipLaunchKernelGGL(wgrad_reduce_vec4_kernel, dim3(d.nblocks), dim3(256), 0, s, reinterpret_cast<const float4*>(d.slab),
                                reinterpret_cast<float4*>(d.dw), d.S, (long long)d.Cout * d.Cin * d.T / 4, d.accumulate);
             break;
-        case WSDL_WGRAD_REDUCE_MANY:
+        case WGRAD_REDUCE_MANY:
             hipLaunchKernelGGL(wgrad_reduce_many_kernel, dim3(d.nblocks), dim3(256), 0, s, d.slab, d.dw, d.S, d.Cout, d.Cin, d.T,
                                d.accumulate, d.live);
             break;
-        case WSDL_WGRAD_REDUCE_MANY16:
+        case WGRAD_REDUCE_MANY16:
             hipLaunchKernelGGL(wgrad_reduce_many16_kernel, dim3(d.nblocks), dim3(256), 0, s, d.slab, d.dw, d.S, d.Cout, d.Cin, d.T,
                                d.accumulate, d.live);
             break;
@@ -1992,21 +1914,12 @@ int wsdl_set_option(const char* name, int value) {
     WSDL_REQUIRE(wsdl::g_plans_recording.load() == 0,
                  "set_option(%s): a launch plan is being recorded (its launches are chosen under ONE option set)", name);
     if (!strcmp(name, "tile_threshold")) { g_tile_threshold = value; return WSDL_OK; }
-    if (!strcmp(name, "bk32")) { g_bk32 = value; return WSDL_OK; }
-    if (!strcmp(name, "col_bands")) { g_col_bands = value; return WSDL_OK; }
     if (!strcmp(name, "conv_split")) { g_conv_split = value != 0; return WSDL_OK; }
     if (!strcmp(name, "stem_kernel")) { g_stem_kernel = value != 0; return WSDL_OK; }
-    if (!strcmp(name, "stem_wgrad")) { g_stem_wgrad = value != 0; return WSDL_OK; }
     if (!strcmp(name, "wgrad_direct")) { g_wgrad_direct = value; return WSDL_OK; }
-    if (!strcmp(name, "wgrad_imbalance_split")) { g_wgrad_imbalance_split = value != 0; return WSDL_OK; }
     if (!strcmp(name, "wgrad_chan_scale")) { g_wgrad_chan_scale = value != 0; return WSDL_OK; }
     if (!strcmp(name, "wgrad_dyraw")) { g_wgrad_dyraw = value; return WSDL_OK; }
-    if (!strcmp(name, "split_bk32")) { g_split_bk32 = value != 0; return WSDL_OK; }
-    if (!strcmp(name, "ksplit_big")) { g_ksplit_big = value; return WSDL_OK; }
-    if (!strcmp(name, "tile256")) { g_tile256 = value; return WSDL_OK; }
-    if (!strcmp(name, "tile64")) { g_tile64 = value; return WSDL_OK; }
     if (!strcmp(name, "conv_il")) { g_conv_il = value != 0; return WSDL_OK; }
-    if (!strcmp(name, "tile_img_major")) { g_tile_img_major = value; return WSDL_OK; }
     if (!strcmp(name, "xcd_map")) { g_xcd_map = value; return WSDL_OK; }
     if (!strcmp(name, "ksplit_target")) { g_ksplit_target = value; return WSDL_OK; }
     if (!strcmp(name, "ksplit_max")) { g_ksplit_max = value; return WSDL_OK; }
@@ -2018,12 +1931,6 @@ int wsdl_set_option(const char* name, int value) {
     }
     if (!strcmp(name, "range_sentinel")) { wsdl::g_range_sentinel = value != 0; return WSDL_OK; }
     if (!strcmp(name, "group_tps10")) { g_group_tps10 = value > 0 ? value : 45; return WSDL_OK; }
-    if (!strcmp(name, "group_interleave")) { g_group_interleave = value; return WSDL_OK; }
-    if (!strcmp(name, "ms_rowfast")) { g_ms_rowfast = value; return WSDL_OK; }
-    if (!strcmp(name, "xcd_rowfast")) { g_xcd_rowfast = value; return WSDL_OK; }
-    if (!strcmp(name, "ms_py")) { g_ms_py = value; return WSDL_OK; }
-    if (!strcmp(name, "bn_coop")) { wsdl::g_bn_coop = value; return WSDL_OK; }
-    if (!strcmp(name, "bn_coop_wide")) { wsdl::g_bn_coop_wide = value; return WSDL_OK; }
     if (!strcmp(name, "bn_resident")) { wsdl::g_bn_resident = value; return WSDL_OK; }
     if (!strcmp(name, "bn_wide_c")) { wsdl::g_bn_wide_c = value; return WSDL_OK; }
     if (!strcmp(name, "layercam_tail_mod")) {
@@ -2031,12 +1938,10 @@ int wsdl_set_option(const char* name, int value) {
         wsdl::g_layercam_tail_mod = value;
         return WSDL_OK;
     }
-    if (!strcmp(name, "wgrad_force_s")) { g_wgrad_force_s = value; return WSDL_OK; }
     if (!strcmp(name, "wgrad_split")) { g_wgrad_split = value != 0; return WSDL_OK; }
     if (!strcmp(name, "wgrad_xcd")) { g_wgrad_xcd = value; return WSDL_OK; }
     if (!strcmp(name, "wgrad_min_tiles")) { g_wgrad_min_tiles = value > 0 ? value : 1; return WSDL_OK; }
     if (!strcmp(name, "wgrad_blocks")) { g_wgrad_blocks = value > 0 ? value : 768; return WSDL_OK; }
-    if (!strcmp(name, "wgrad_bk")) { g_wgrad_bk = value == 32 ? 32 : 16; return WSDL_OK; }
     wsdl::set_error("set_option: unknown option %s", name);
     return WSDL_EINVAL;
 }
@@ -2168,7 +2073,7 @@ static int group_max_taps(int H, int W, int k, int dil) {
 }
 
 int wsdl_conv2d_fwd_group_ok(int n, int B, int Cin, int H, int W, int Cout) {
-    if (n < 2 || n > 4 || !g_conv_split || !g_tile256) return 0;
+    if (n < 2 || n > 4 || !g_conv_split) return 0;
     if (Cout % 256 != 0 || Cin % 16 != 0 || (H * W) % 4 != 0) return 0;
     if (((long long)(B - 1) * Cin * H * W + (long long)Cin * H * W) * 4 > (1ll << 31) - 4) return 0;
     if (wsdl::cdiv((long long)B * H * W, 128) % 8 != 0) return 0;        // every problem starts on a multiple of 8 workgroups
@@ -2227,7 +2132,7 @@ int wsdl_conv2d_fwd_group(int n, const float* x, const void* const* wt_fwd, floa
         Band bands[8];
         int nb = 1;
         bands[0] = Band{0, W};
-        if (g_col_bands) nb = column_bands(W, W, p.ah, p.bh, p.ch, p.sh, p.KW, bands);
+        nb = column_bands(W, W, p.ah, p.bh, p.ch, p.sh, p.KW, bands);
         int tiles = 0;
         for (int b = 0; b < nb && nb > 1; ++b) {
             p.b_ow0[b] = bands[b].ow0;
@@ -2245,7 +2150,7 @@ int wsdl_conv2d_fwd_group(int n, const float* x, const void* const* wt_fwd, floa
             wsp += wsdl::align_up((size_t)ks * Cout * p.P * sizeof(float), 256);
         }
         p.xcd_py = (start % 8 == 0) ? choose_xcd_py(p, gx, gy) : 0;
-        p.tile_img_major = g_tile_img_major >= 1 && k[i] > 1;
+        p.tile_img_major = k[i] > 1;
         grp.start[j] = start;
         grp.gx[j] = gx;
         grp.gy[j] = gy;
@@ -2271,7 +2176,7 @@ int wsdl_conv2d_fwd_group(int n, const float* x, const void* const* wt_fwd, floa
             ns += grp.p[j].ksplit;
             same = same && grp.gx[j] * grp.gy[j] == grp.gx[0] * grp.gy[0];
         }
-        if (g_group_interleave && same && ns <= 8 && (8 % ns == 0)) {
+        if (same && ns <= 8 && (8 % ns == 0)) {
             grp.ns = ns;
             int s = 0;
             for (int j = 0; j < n; ++j)
@@ -2317,7 +2222,7 @@ int wsdl_conv2d_fwd_group(int n, const float* x, const void* const* wt_fwd, floa
 // Is the one-launch input gradient of n convolutions over the same input available for this geometry (what
 // wsdl_conv2d_dgrad_multi requires beyond its arguments being well-formed)?
 int wsdl_conv2d_dgrad_multi_ok(int n, int B, int Cin, int H, int W, int Cout) {
-    if (n < 2 || n > 4 || !g_conv_split || !g_tile256) return 0;
+    if (n < 2 || n > 4 || !g_conv_split) return 0;
     if (Cin % 256 != 0 || Cout % 16 != 0) return 0;
     if ((long long)wsdl::cdiv((long long)B * H * W, 128) * (Cin / 256) < 256) return 0;                  // the 256 x 128 form's own rule
     if ((long long)wsdl::cdiv((long long)B * H * W, 128) * wsdl::cdiv(Cin, 128) < g_tile_threshold) return 0;
@@ -2528,7 +2433,7 @@ __global__ __launch_bounds__(256, 2) void stem_wgrad7x7s2_kernel(WgradP p, int t
 }
 
 static bool stem_wgrad_eligible(int B, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int dil) {
-    return g_stem_wgrad && Cin == 3 && Cout == 64 && kh == 7 && kw == 7 && stride == 2 && pad == 3 && dil == 1 && H >= 7 && W >= 7;
+    return Cin == 3 && Cout == 64 && kh == 7 && kw == 7 && stride == 2 && pad == 3 && dil == 1 && H >= 7 && W >= 7;
 }
 static int stem_wgrad_grid(int B, int OH, int OW) {
     const long long tiles = (long long)B * wsdl::cdiv(OH, kSwTH) * wsdl::cdiv(OW, kStemTW);
@@ -2547,7 +2452,7 @@ static int wgrad_bands(int Cout, int Cin, int OW, int W, int kw, int stride, int
     bool fast;
     wgrad_tile(Cout, Cin, &BM, &BN, &fast);
     bands[0] = Band{0, OW};
-    if (!fast || !g_col_bands || stride != 1) return 1;
+    if (!fast || stride != 1) return 1;
     if (wgrad_chunk32(Cout, Cin, kw * kw * Cin)) return 1;     // 32-pixel-chunk kernel: no bands
     return column_bands(OW, W, 1, dil, -pad, 1, kw, bands);
 }
@@ -2591,8 +2496,6 @@ size_t wsdl_conv2d_wgrad_workspace(int B, int Cin, int H, int W, int Cout, int k
            (g_wgrad_chan_scale ? wsdl::align_up((size_t)(Cin + Cout) * sizeof(float), 256) : 0);
 }
 
-// `defer` (wsdl_conv2d_wgrad_deferred): the slabs are left un-reduced and *defer describes the reduction (kind < 0: nothing is
-// pending - the call reduced by itself, e.g. a batch processed in slices).
 // per-channel operands (optional; wsdl_conv2d_wgrad_ex): x_chan / dy_chan = one maximum per channel of x / dY as published by the
 // channel-resident BatchNorm kernels; dy_presplit = dY already as the kernel's fp16 rows, scaled per channel by dy_chan
 struct WgradExtra {
@@ -2603,44 +2506,18 @@ struct WgradExtra {
 static int wgrad_impl(const float* x, const float* dy, float* dw, int B, int Cin, int H, int W,
                       int Cout, int kh, int kw, int stride, int pad, int dil, int accumulate,
                       long long x_bs, long long dy_bs, const float* x_amax, const float* dy_amax, void* ws,
-                      size_t ws_bytes, wsdl_stream_t stream, wsdl_wgrad_reduce_desc* defer, WgradExtra ex = WgradExtra{}) {
+                      size_t ws_bytes, wsdl_stream_t stream, WgradExtra ex = WgradExtra{}) {
     WSDL_REQUIRE(x && dy && dw && ws, "conv2d_wgrad: null pointer");
-    if (defer) defer->kind = -1;
     int OH, OW;
     if (int rc = check_geom(B, Cin, H, W, Cout, kh, kw, stride, pad, dil, &OH, &OW)) return rc;
     if (wgrad_role_swap(Cin, Cout, kh, kw, stride, pad)) {
         const size_t t_bytes = wsdl::align_up((size_t)Cout * Cin * sizeof(float), 256);
         WSDL_REQUIRE(ws_bytes > t_bytes, "conv2d_wgrad: workspace too small");
         float* dwt = static_cast<float*>(ws);
-        if (defer) {
-            // the transposed problem's slabs, reduced AND transposed by the deferred launch (no scratch matrix in between)
-            wsdl_wgrad_reduce_desc inner{};
-            if (int rc = wgrad_impl(dy, x, dwt, B, Cout, OH, OW, Cin, 1, 1, 1, 0, 1, 0,
-                                    dy_bs ? dy_bs : (long long)Cout * OH * OW, x_bs ? x_bs : (long long)Cin * H * W,
-                                    dy_amax, x_amax, static_cast<char*>(ws) + t_bytes, ws_bytes - t_bytes, stream, &inner,
-                                    WgradExtra{ex.dy_chan, ex.x_chan, nullptr}))
-                return rc;
-            if (inner.kind == WSDL_WGRAD_REDUCE_VEC4) {
-                *defer = inner;                      // slab, S as recorded: slab[z][ci][co]
-                defer->kind = WSDL_WGRAD_REDUCE_TRANSPOSED;
-                defer->dw = dw;
-                defer->Cout = Cout; defer->Cin = Cin; defer->T = 1;
-                defer->accumulate = accumulate;
-                defer->grid_x = wsdl::cdiv(Cout, 32);
-                defer->nblocks = defer->grid_x * wsdl::cdiv(Cin, 32);
-                WSDL_TRACE("role-swapped (dW^T), reduce + transpose deferred");
-                return WSDL_OK;
-            }
-            // (another reduction kind, or already reduced into dwt by the inner call: finish the two-launch form here)
-            if (inner.kind >= 0) {
-                wsdl_wgrad_reduce_desc one = inner;
-                one.block_begin = 0;
-                if (int rc = wgrad_reduce_one(one, wsdl::as_stream(stream))) return rc;
-            }
-        } else if (int rc = wgrad_impl(dy, x, dwt, B, Cout, OH, OW, Cin, 1, 1, 1, 0, 1, 0,
-                                       dy_bs ? dy_bs : (long long)Cout * OH * OW, x_bs ? x_bs : (long long)Cin * H * W,
-                                       dy_amax, x_amax, static_cast<char*>(ws) + t_bytes, ws_bytes - t_bytes, stream, nullptr,
-                                       WgradExtra{ex.dy_chan, ex.x_chan, nullptr}))
+        if (int rc = wgrad_impl(dy, x, dwt, B, Cout, OH, OW, Cin, 1, 1, 1, 0, 1, 0,
+                                dy_bs ? dy_bs : (long long)Cout * OH * OW, x_bs ? x_bs : (long long)Cin * H * W,
+                                dy_amax, x_amax, static_cast<char*>(ws) + t_bytes, ws_bytes - t_bytes, stream,
+                                WgradExtra{ex.dy_chan, ex.x_chan, nullptr}))
             return rc;
         WSDL_TRACE("role-swapped (dW^T) + transpose");
         hipLaunchKernelGGL(transpose_add_kernel, dim3(wsdl::cdiv(Cout, 32), wsdl::cdiv(Cin, 32)), dim3(32, 8), 0,
@@ -2673,24 +2550,19 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, int B, int Cin
             hipLaunchKernelGGL(stem_wgrad7x7s2_kernel, dim3(G), dim3(256), 0, s, p, tiles_w, tiles_h, B * tiles_w * tiles_h);
             WSDL_LAUNCH_CHECK();
         }
-        wsdl_wgrad_reduce_desc rd{};
+        WgradReduce rd{};
         rd.slab = p.slab; rd.dw = dw; rd.S = G; rd.Cout = Cout; rd.Cin = Cin; rd.T = kh * kw; rd.accumulate = accumulate;
         rd.live = ~0ull;
         const long long total = (long long)Cout * p.N;
         if (G >= 64) {
-            rd.kind = WSDL_WGRAD_REDUCE_MANY16;
+            rd.kind = WGRAD_REDUCE_MANY16;
             rd.nblocks = (int)((total + 15) / 16);
         } else if (G >= 16) {
-            rd.kind = WSDL_WGRAD_REDUCE_MANY;
+            rd.kind = WGRAD_REDUCE_MANY;
             rd.nblocks = (int)((total + 63) / 64);
         } else {
-            rd.kind = WSDL_WGRAD_REDUCE_PLAIN;
+            rd.kind = WGRAD_REDUCE_PLAIN;
             rd.nblocks = (int)std::min<long long>((total + 255) / 256, 4096);
-        }
-        if (defer) {
-            *defer = rd;
-            WSDL_TRACE("wgrad_reduce slabs=%d deferred", G);
-            return WSDL_OK;
         }
         WSDL_TRACE("wgrad_reduce slabs=%d", G);
         return wgrad_reduce_one(rd, s);
@@ -2698,7 +2570,7 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, int B, int Cin
     const unsigned long long live_all = live_taps(H, W, OH, OW, kh, kw, stride, pad, dil);
     const int S = wgrad_splits(Cout, Cin, p.N, p.P, __builtin_popcountll(live_all) * Cin, wgrad_tap_balance(H, OH, kh, stride, pad, dil));
     Band bands[8];
-    const int nb = (g_wgrad_bk == 32) ? 1 : wgrad_bands(Cout, Cin, OW, W, kw, stride, pad, dil, bands);
+    const int nb = wgrad_bands(Cout, Cin, OW, W, kw, stride, pad, dil, bands);
     if (nb == 1) bands[0] = Band{0, OW};
     const int S_total = nb * S;
     p.ow0 = 0; p.own = OW; p.slab0 = 0; p.nb = 1; p.splits = S;
@@ -2726,7 +2598,7 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, int B, int Cin
             const int nb_img = (int)std::min<long long>(per, B - b0);
             if (int rc = wgrad_impl(x + (long long)b0 * p.x_bs, dy + (long long)b0 * p.dy_bs, dw, nb_img, Cin, H, W,
                                     Cout, kh, kw, stride, pad, dil, (accumulate || b0 > 0) ? 1 : 0, p.x_bs, p.dy_bs,
-                                    x_amax, dy_amax, ws, ws_bytes, stream, nullptr, WgradExtra{ex.x_chan, ex.dy_chan, nullptr}))
+                                    x_amax, dy_amax, ws, ws_bytes, stream, WgradExtra{ex.x_chan, ex.dy_chan, nullptr}))
                 return rc;
         }
         return WSDL_OK;
@@ -2743,7 +2615,7 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, int B, int Cin
             for (int i = 0; i < nb; ++i)
                 executed += flops * ((double)bands[i].own / OW) *
                             wgrad_executed_fraction(B * OH * bands[i].own, OH, bands[i].ow0, bands[i].own, H, W, kh, kw,
-                                                    stride, pad, dil, (chunk32 || g_wgrad_bk == 32) ? 32 : 16);
+                                                    stride, pad, dil, chunk32 ? 32 : 16);
         }
         // which fp16x2 kernel a chunk32 launch takes (the condition of the dispatch below): the direct-fragment kernel has a
         // timing class of its own
@@ -2766,9 +2638,6 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, int B, int Cin
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds64);
             if (attr_rc == hipSuccess)
                 attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<128, 128, 2>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds128);
-            if (attr_rc == hipSuccess)
-                attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_fast_kernel<128, 128, 2, 32>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds128);
         });
         WSDL_HIP_CHECK(attr_rc);
@@ -2878,9 +2747,6 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, int B, int Cin
                     hipLaunchKernelGGL((conv_wgrad_split32_kernel<128, 128, 0>), grid, dim3(kThreads), 0, s, p, dys,
                                        (unsigned)dys_bytes, static_cast<const float*>(nullptr));
                 }
-            } else if (tBM == 128 && tBN == 128 && g_wgrad_bk == 32) {
-                dim3 grid(p.N / 128, Cout / 128, S);
-                hipLaunchKernelGGL((conv_wgrad_fast_kernel<128, 128, 2, 32>), grid, dim3(kThreads), lds128, s, p);
             } else {
                 WgradP q = p;                            // ONE launch: blockIdx.z = band * S + split
                 q.nb = nb;
@@ -2910,32 +2776,27 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, int B, int Cin
     }
     WSDL_LAUNCH_CHECK();
     // the reduction over the pixel slabs: which kernel, on how many 256-thread blocks
-    wsdl_wgrad_reduce_desc rd{};
+    WgradReduce rd{};
     rd.slab = p.slab; rd.dw = dw; rd.S = S_total; rd.Cout = Cout; rd.Cin = Cin; rd.T = kh * kw; rd.accumulate = accumulate;
     rd.live = live_mask;
     const long long total = (long long)Cout * p.N;
     const int T = kh * kw;
     if (T >= 2 && T <= 16 && Cout <= 65535) {
-        rd.kind = WSDL_WGRAD_REDUCE_TILED;
+        rd.kind = WGRAD_REDUCE_TILED;
         rd.grid_x = wsdl::cdiv(Cin, 32);
         rd.nblocks = rd.grid_x * Cout;
     } else if (T == 1 && total % 4 == 0 && (reinterpret_cast<uintptr_t>(dw) & 15) == 0) {
-        rd.kind = WSDL_WGRAD_REDUCE_VEC4;
+        rd.kind = WGRAD_REDUCE_VEC4;
         rd.nblocks = (int)std::min<long long>((total / 4 + 255) / 256, 8192);
     } else if (S_total >= 64 && total < 64 * 512) {
-        rd.kind = WSDL_WGRAD_REDUCE_MANY16;        // few outputs, very many slabs: more blocks, 16 slab lanes each
+        rd.kind = WGRAD_REDUCE_MANY16;        // few outputs, very many slabs: more blocks, 16 slab lanes each
         rd.nblocks = (int)((total + 15) / 16);
     } else if (S_total >= 16 && total <= (1ll << 24)) {
-        rd.kind = WSDL_WGRAD_REDUCE_MANY;
+        rd.kind = WGRAD_REDUCE_MANY;
         rd.nblocks = (int)((total + 63) / 64);
     } else {
-        rd.kind = WSDL_WGRAD_REDUCE_PLAIN;
+        rd.kind = WGRAD_REDUCE_PLAIN;
         rd.nblocks = (int)std::min<long long>((total + 255) / 256, 4096);
-    }
-    if (defer) {
-        *defer = rd;
-        WSDL_TRACE("wgrad_reduce slabs=%d deferred", S_total);
-        return WSDL_OK;
     }
     WSDL_TRACE("wgrad_reduce slabs=%d", S_total);
     return wgrad_reduce_one(rd, s);
@@ -2946,35 +2807,19 @@ int wsdl_conv2d_wgrad(const float* x, const float* dy, float* dw, int B, int Cin
                       long long x_bs, long long dy_bs, const float* x_amax, const float* dy_amax, void* ws,
                       size_t ws_bytes, wsdl_stream_t stream) {
     return wgrad_impl(x, dy, dw, B, Cin, H, W, Cout, kh, kw, stride, pad, dil, accumulate, x_bs, dy_bs, x_amax, dy_amax, ws,
-                      ws_bytes, stream, nullptr);
-}
-
-int wsdl_conv2d_wgrad_deferred(const float* x, const float* dy, float* dw, int B, int Cin, int H, int W,
-                               int Cout, int kh, int kw, int stride, int pad, int dil, int accumulate,
-                               long long x_bs, long long dy_bs, const float* x_amax, const float* dy_amax, void* ws,
-                               size_t ws_bytes, wsdl_wgrad_reduce_desc* desc, wsdl_stream_t stream) {
-    WSDL_REQUIRE(desc != nullptr, "conv2d_wgrad_deferred: null descriptor");
-    return wgrad_impl(x, dy, dw, B, Cin, H, W, Cout, kh, kw, stride, pad, dil, accumulate, x_bs, dy_bs, x_amax, dy_amax, ws,
-                      ws_bytes, stream, desc);
+                      ws_bytes, stream);
 }
 
 int wsdl_conv2d_wgrad_ex(const float* x, const float* dy, float* dw, int B, int Cin, int H, int W,
                          int Cout, int kh, int kw, int stride, int pad, int dil, int accumulate,
                          long long x_bs, long long dy_bs, const float* x_amax, const float* dy_amax,
                          const float* x_chan_amax, const float* dy_chan_amax, const void* dy_presplit, void* ws,
-                         size_t ws_bytes, wsdl_wgrad_reduce_desc* desc_or_null, wsdl_stream_t stream) {
+                         size_t ws_bytes, wsdl_stream_t stream) {
     WSDL_REQUIRE(!dy_presplit || dy_chan_amax, "conv2d_wgrad_ex: dy_presplit comes with dy_chan_amax (the scales it was written with)");
     WSDL_REQUIRE(!dy_presplit || wsdl_conv2d_wgrad_presplit_bytes(B, Cin, H, W, Cout, kh, kw, stride, pad, dil) != 0,
                  "conv2d_wgrad_ex: this geometry's weight gradient does not read pre-split dY (wsdl_conv2d_wgrad_presplit_bytes)");
     return wgrad_impl(x, dy, dw, B, Cin, H, W, Cout, kh, kw, stride, pad, dil, accumulate, x_bs, dy_bs, x_amax, dy_amax, ws,
-                      ws_bytes, stream, desc_or_null, WgradExtra{x_chan_amax, dy_chan_amax, dy_presplit});
-}
-
-int wsdl_wgrad_reduce_multi(const wsdl_wgrad_reduce_desc* desc, int n, int total_blocks, wsdl_stream_t stream) {
-    WSDL_REQUIRE(desc && n > 0 && total_blocks > 0, "wgrad_reduce_multi: bad arguments");
-    hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3(total_blocks), dim3(256), 0, wsdl::as_stream(stream), desc, n);
-    WSDL_LAUNCH_CHECK();
-    return WSDL_OK;
+                      ws_bytes, stream, WgradExtra{x_chan_amax, dy_chan_amax, dy_presplit});
 }
 
 int wsdl_multi_amax(const float* const* ptrs, const long long* counts, int n, float* out, wsdl_stream_t stream) {

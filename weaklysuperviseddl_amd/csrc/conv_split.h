@@ -42,7 +42,7 @@
 // consecutive lanes: the weight stores are conflict-free because of which unit each lane carries - 8 consecutive rows per
 // b128 group (round 6; rounds 1-5 stored in unit order: a 2-way conflict per store).  The 8-byte activation stores of the
 // 256 x 128 form keep their 2-way conflict (lanes i and i + 8 of a group): the mapping that removes it was built and measured
-// slower - see kPairB in conv_igemm_split_body.
+// slower - see the activation staging in conv_igemm_split_body.
 #pragma once
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -238,14 +238,9 @@ __device__ __forceinline__ void conv_igemm_split_body(const ConvP& p, const int 
     // MEASURED, NOT ADOPTED (round 6, same box, three builds): the pairing removes the store conflict and costs the global side
     // more than that - a lane quad then reads 2 pixels x 2 channels instead of 16 contiguous bytes.  Training step 847.8 / 852.1
     // img/s with it alone against 853.1 / 853.4 without; the 256 x 128 launches 1.5-2.5 % slower with both mappings
-    // (l4.conv2 d4 221.5 against 217.8 us).  Kept as a build option (-DWSDL_EXP_PAIRB, tools/build_variant.sh).
-#if defined(WSDL_EXP_PAIRB) && !defined(WSDL_EXP_OLD_LDS_MAP)
-    constexpr bool kPairB = !MF && B_PER == 4 && B_STEP == 4;
-#else
-    constexpr bool kPairB = false;
-#endif
-    const int pl = kPairB ? (tid % (2 * BN)) / 2 : tid % BN;
-    const int kr = kPairB ? (tid & 1) + 2 * (tid / (2 * BN)) : tid / BN;
+    // (l4.conv2 d4 221.5 against 217.8 us).  The code was removed; the figures are in profiles/r06_notes.md.
+    const int pl = tid % BN;
+    const int kr = tid / BN;
     const int pix = n0 + pl;
     const bool pix_ok = pix < W_P;
     int pb = 0, poh = 0, pow_ = 0;
@@ -362,11 +357,7 @@ __device__ __forceinline__ void conv_igemm_split_body(const ConvP& p, const int 
     // is unchanged: a wave still loads one contiguous 1 KB run, its lanes permuted inside it.  Same box, three builds: the
     // 16 x 16 x 32 forms 2-3 % faster per launch (l2.conv2 41.3 -> 40.1 us), the training step 853.5 / 855.1 img/s against
     // 853.1 / 853.4 in unit order: kept.
-#if !defined(WSDL_EXP_OLD_LDS_MAP) && !defined(WSDL_EXP_NO_ROWA)
     constexpr bool kRowMajorA = UPR == 4 && (A_UPS % 64) == 0;
-#else
-    constexpr bool kRowMajorA = false;
-#endif
     unsigned voff_a[A_U], lds_a[A_U];
 #pragma unroll
     for (int e = 0; e < A_U; ++e) {
@@ -420,17 +411,12 @@ __device__ __forceinline__ void conv_igemm_split_body(const ConvP& p, const int 
 #pragma unroll
         for (int e = 0; e < B_PER / 2; ++e) {
             const float x0 = __builtin_bit_cast(float, rb[2 * e]), x1 = __builtin_bit_cast(float, rb[2 * e + 1]);
-#ifdef WSDL_EXP_NOSPLIT      // timing-only build: the activations as if they arrived pre-split (no VALU between load and LDS store)
-            pc[0][e] = rb[2 * e] & 0x3fff3fffu;
-            pc[NP - 1][e] = rb[2 * e + 1] & 0x3fff3fffu;
-#else
             if constexpr (AR == 0)
                 split3(x0, x1, pc[0][e], pc[1][e], pc[2][e]);
             else if constexpr (AR == 1)
                 split2h(x0 * xs, x1 * xs, pc[0][e], pc[1][e]);
             else
                 split2hs(x0 * xs, x1 * xs, pc[0][e], pc[1][e]);
-#endif
         }
         unsigned char* rowp = &Bs[buf][pl * ROW];
         if constexpr (MF) {
@@ -530,17 +516,8 @@ __device__ __forceinline__ void conv_igemm_split_body(const ConvP& p, const int 
             }
         }
     };
-#ifdef WSDL_EXP_NOSTAGE          // timing-only build: both LDS images filled once (real data), the loop is barrier + ds_read + MFMA
-    if (nq > 1) store_tiles(1);
-    __syncthreads();
-#endif
     int q_start = 0;
-#if defined(WSDL_EXP_NOSTAGE) || defined(WSDL_EXP_NOMFMA)
-    constexpr bool kTimingBuild = true;                  // the timing-only builds take the plain loop apart, not this one
-#else
-    constexpr bool kTimingBuild = false;
-#endif
-    if constexpr (IL && !kTimingBuild) {
+    if constexpr (IL) {
         static_assert(!IL || (!MF && KS == 1 && AR == 1), "interleaved loop: 32x32x16 form, K chunk 16, fp16x2");
         // the loads of load_next() split in two: `advance` (which chunk comes next: scalar bookkeeping, a branch) at the END of an
         // iteration, `issue` (the loads themselves) inside the interleaved block
@@ -599,17 +576,11 @@ __device__ __forceinline__ void conv_igemm_split_body(const ConvP& p, const int 
     }
     for (int q = q_start; q < nq; ++q) {
         const int cur = q & 1;
-#ifndef WSDL_EXP_NOSTAGE
         if (q + 1 < nq) {
             store_tiles(cur ^ 1);                        // the registers hold chunk q + 1
         }
         if (q + 2 < nq) load_next();
-#endif
-#ifdef WSDL_EXP_NOMFMA           // timing-only build: staging, barriers and one LDS read per chunk, no matrix work
-        acc[0][0][0] += (float)As[cur][(tid * 16) % (BM * ROW)] + (float)Bs[cur][(tid * 16) % (BN * ROW)];
-#else
         mfma_chunk(cur);
-#endif
         lds_barrier();
     }
     }   // sources
@@ -1332,13 +1303,8 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wgrad_split16_kernel(WgradP 
             const unsigned x0 = even ? rb[S][2 * i] : recv;
             const unsigned x1 = even ? recv : rb[S][2 * i + 1];
             unsigned ph, pl;
-#ifdef WSDL_EXP_W_NOSPLIT        // timing-only build: x as if it arrived pre-split
-            ph = x0;
-            pl = x1;
-#else
             const float xsc = CS ? xsr[CS ? 16 * i : 0] : xs;
             split2h(__builtin_bit_cast(float, x0) * xsc, __builtin_bit_cast(float, x1) * xsc, ph, pl);
-#endif
             unsigned char* d = Bs + st_row + i * 16 * ROW;
             *reinterpret_cast<unsigned*>(d + st_u0) = ph;
             *reinterpret_cast<unsigned*>(d + st_u1) = pl;
@@ -1358,19 +1324,12 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wgrad_split16_kernel(WgradP 
         c1 = next_valid(c0 + 1);
         if (c1 < chunk_end) load_tiles(S1{}, c1);
     }
-#ifdef WSDL_EXP_W_NOSTAGE            // timing-only build: the LDS image filled once (real data), the loop is barrier + ds_read + MFMA
-    if (c0 < chunk_end) store_tiles(S0{});
-#endif
     // one chunk: its operands sit in register slot S, the next chunk's in slot 1 - S
     auto step = [&](auto slot_c) {
         int c2 = chunk_end;
-#ifndef WSDL_EXP_W_NOSTAGE
         store_tiles(slot_c);
         if (c1 < chunk_end) c2 = next_valid(c1 + 1);
         if (c2 < chunk_end) load_tiles(slot_c, c2);            // the slot is free again; in flight during two chunks' MFMAs
-#else
-        if (c1 < chunk_end) c2 = c1 + 1;
-#endif
         lds_barrier();
         half8 a[TMI][2], b[TNI][2];
 #pragma unroll
@@ -1383,12 +1342,6 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wgrad_split16_kernel(WgradP 
             b[j][0] = *reinterpret_cast<const half8*>(Bb + j * 16 * ROW + fr0);
             b[j][1] = *reinterpret_cast<const half8*>(Bb + j * 16 * ROW + fr1);
         }
-#ifdef WSDL_EXP_W_NOMFMA             // timing-only build: staging, barriers and the fragment reads, no matrix work
-#pragma unroll
-        for (int i = 0; i < TMI; ++i)
-#pragma unroll
-            for (int j = 0; j < TNI; ++j) acc[i][j][0] += (float)a[i][0][0] + (float)a[i][1][1] + (float)b[j][0][2] + (float)b[j][1][3];
-#else
 #pragma unroll
         for (int i = 0; i < TMI; ++i)
 #pragma unroll
@@ -1399,7 +1352,6 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wgrad_split16_kernel(WgradP 
                 c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i][0], b[j][0], c, 0, 0, 0);
                 acc[i][j] = c;
             }
-#endif
         lds_barrier();
         c0 = c1;
         c1 = c2;
@@ -1671,9 +1623,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wgrad_split16d_kernel(WgradP
             }
             int c2 = chunk_end;
             if (c1 < chunk_end) c2 = next_valid(c1 + 1);
-#ifndef WSDL_EXP_D_NOLOAD            // timing-only build: operands loaded once, the loop is convert + barrier + LDS reads + MFMA
             if (c2 < chunk_end) load_tiles(slot_c, c2);            // slot S is free: x converted, dY stored one step ago
-#endif
             lds_barrier();                                         // As[buf] is complete; nobody still reads As[buf ^ 1]
             const unsigned char* Ab = As[buf];
 #pragma unroll
@@ -1683,20 +1633,14 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wgrad_split16d_kernel(WgradP
 #pragma unroll
                 for (int j = 0; j < TNI; ++j) {
                     f32x4 c = acc[i][j];
-#ifdef WSDL_EXP_D_NOMFMA             // timing-only build: everything but the matrix work
-                    c[0] += (float)a0[0] + (float)a1[1] + (float)b[j][0][2] + (float)b[j][1][3];
-#else
                     c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, b[j][0], c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, b[j][1], c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, b[j][0], c, 0, 0, 0);
-#endif
                     acc[i][j] = c;
                 }
             }
-#ifndef WSDL_EXP_D_NOLOAD
             if (c1 < chunk_end) store_a(std::integral_constant<int, 1 - S>{}, buf ^ 1);
             buf ^= 1;
-#endif
             c0 = c1;
             c1 = c2;
         };

@@ -373,23 +373,6 @@ def _ws_bytes(query, *geom):
     return n
 
 
-_coop_cache = {}
-BN_COOP = [os.environ.get("WSDL_BN_COOP", "1") != "0"]
-
-
-def coop_counters(device):
-    """The zero-initialised counters of the several-workgroups-per-channel BatchNorm kernels (include/wsdl_hip.h
-    wsdl_bn_train_fwd ``coop``): one region per (device, stream) - launches of one stream never overlap, and every launch
-    leaves its counters zeroed.  None switches the form off (WSDL_BN_COOP=0)."""
-    if not BN_COOP[0] or torch.cuda.is_current_stream_capturing() and (device, raw_stream(device)) not in _coop_cache:
-        return None
-    key = (device, raw_stream(device))
-    buf = _coop_cache.get(key)
-    if buf is None:
-        buf = _coop_cache[key] = torch.zeros(2 * 4096, dtype=torch.int32, device=device)
-    return buf
-
-
 def conv_out_hw(H, W, k, stride, pad, dil):
     return ((H + 2 * pad - dil * (k - 1) - 1) // stride + 1, (W + 2 * pad - dil * (k - 1) - 1) // stride + 1)
 
@@ -404,8 +387,6 @@ def set_option(name, value):
     check(lib().wsdl_set_option(name.encode(), int(value)))
     if name == "conv_arith":
         CONV_ARITH[0] = int(value != 0)
-    if name == "bn_coop":
-        BN_COOP_ON[0] = int(value) > 0
     _both_split_cache.clear()          # what the library answered under the old option set
     _size_cache.clear()
     LAYOUT_EPOCH[0] += 1
@@ -841,87 +822,6 @@ def _wgrad_split(wshape):
     return CONV_ARITH[0] == 1 and wshape[0] % 128 == 0 and wshape[1] % 128 == 0
 
 
-class _ReduceDesc(C.Structure):       # wsdl_wgrad_reduce_desc (include/wsdl_hip.h)
-    _fields_ = [("slab", C.c_void_p), ("dw", C.c_void_p), ("live", C.c_ulonglong),
-                ("S", C.c_int), ("Cout", C.c_int), ("Cin", C.c_int), ("T", C.c_int),
-                ("accumulate", C.c_int), ("kind", C.c_int), ("grid_x", C.c_int), ("nblocks", C.c_int),
-                ("block_begin", C.c_int), ("reserved", C.c_int)]
-
-
-# Deferred slab reductions of the weight gradients (wsdl_conv2d_wgrad_deferred / wsdl_wgrad_reduce_multi): a weight gradient
-# written into a parameter's slice of the flat gradient buffer leaves its pixel slabs un-reduced; the pending reductions run
-# as one launch when the gradients are needed - at the end of the backward pass (an autograd engine callback), before a
-# gradient bucket's all-reduce, before the optimiser step - or in groups (WSDL_WGRAD_DEFER_MB: flushed once the pending slabs
-# exceed that many MB).  Bit-identical to the per-layer reductions.
-# BUILT, MEASURED, OFF BY DEFAULT (round 6; WSDL_WGRAD_DEFER=1 switches it on).  ~60 launches of 9-10 us per training step do
-# become 1-10, but the step is SLOWER: 853.8 / 852.5 img/s in 48 MB groups, 846 in 16 MB groups, 854.6 / 856.4 all at the end,
-# against 864.0 / 864.7 with the per-layer launches (same box, profiles/r06_notes.md).  A layer's slabs are reduced by the
-# launch right behind the kernel that wrote them - out of the L2s and the Infinity Cache, from ONE workspace the next layer
-# reuses; deferred, every layer needs slabs of its own (0.5 GB per step) that go out to HBM and come back.  The launches
-# saved were latency on the side stream, which is not what bounds the step.
-WGRAD_DEFER = [os.environ.get("WSDL_WGRAD_DEFER", "0") != "0"]
-WGRAD_DEFER_BYTES = [int(float(os.environ.get("WSDL_WGRAD_DEFER_MB", "100000")) * (1 << 20))]
-_wgrad_pending = {}       # device -> {"descs": [_ReduceDesc], "dws": set of dw pointers, "keep": [tensors], "side": bool, "cb": bool}
-_wgrad_ws = {}            # (device, geometry, dw pointer) -> that layer's own workspace (its slabs outlive the launch)
-_reduce_tables = {}       # descriptor bytes -> (device table, n, total blocks)
-
-
-def _pending_of(device):
-    pend = _wgrad_pending.get(device)
-    if pend is None:
-        pend = _wgrad_pending[device] = {"descs": [], "dws": set(), "keep": [], "side": False, "cb": False, "bytes": 0}
-    return pend
-
-
-def flush_wgrad_reduces(device=None):
-    """Run every pending slab reduction of ``device`` (default: all devices) as ONE launch - on the side stream, behind what the
-    current stream holds, when any of the weight gradients ran there (consumers of the gradients join the side stream anyway:
-    ``join_side_stream`` before Adam, the bucket all-reduces are enqueued on it)."""
-    for dev, pend in list(_wgrad_pending.items()):
-        if (device is not None and _norm_device(device) != dev) or not pend["descs"]:
-            continue
-        descs = pend["descs"]
-        key = b"".join(bytes(d) for d in descs)
-        ent = _reduce_tables.get(key)
-        if ent is None:
-            arr = (_ReduceDesc * len(descs))()
-            blocks = 0
-            for a, d in zip(arr, descs):
-                C.memmove(C.addressof(a), C.addressof(d), C.sizeof(_ReduceDesc))
-                a.block_begin = blocks
-                blocks += d.nblocks
-            with torch.cuda.device(dev):
-                table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-            ent = _reduce_tables[key] = (table, len(descs), blocks)
-            if len(_reduce_tables) > 64:
-                _reduce_tables.pop(next(iter(_reduce_tables)))
-        cur = raw_stream(dev)
-        if pend["side"]:
-            hs = side_stream(dev).cuda_stream
-            stream_wait(hs, cur)
-        else:
-            hs = cur
-        rec = PLAN_REC[0]
-        if rec is not None:
-            rec.keep.extend(pend["keep"])        # the slabs' workspaces: their addresses are inside the table, not arguments
-        check(lib().wsdl_wgrad_reduce_multi(_p(ent[0]), ent[1], ent[2], hs))
-        pend["descs"], pend["keep"], pend["side"], pend["cb"], pend["bytes"] = [], [], False, False, 0
-        pend["dws"].clear()
-
-
-def _queue_flush(pend):
-    """Flush when the running backward pass ends (the engine's final callbacks - what DistributedDataParallel uses for its
-    own finalisation); outside a backward pass, at once."""
-    if pend["cb"]:
-        return True
-    try:
-        torch.autograd.Variable._execution_engine.queue_callback(flush_wgrad_reduces)
-    except RuntimeError:
-        return False
-    pend["cb"] = True
-    return True
-
-
 def wgrad_presplit_bytes(xshape, wshape, stride, pad, dil):
     """Bytes of the pre-split dY rows the weight gradient of this convolution reads when its producer writes them
     (``bn_train_bwd(presplit_bytes=)``); 0 where it would not use them."""
@@ -930,12 +830,11 @@ def wgrad_presplit_bytes(xshape, wshape, stride, pad, dil):
     return _ws_bytes("wsdl_conv2d_wgrad_presplit_bytes", B, Cin, H, W, Cout, kh, kw, stride, pad, dil)
 
 
-def conv2d_wgrad(x, dy, wshape, stride, pad, dil, out=None, accumulate=False, x_amax=None, dy_amax=None, stream=None, defer=False,
+def conv2d_wgrad(x, dy, wshape, stride, pad, dil, out=None, accumulate=False, x_amax=None, dy_amax=None, stream=None,
                  x_camax=None, dy_camax=None, dy_presplit=None):
     """``stream``: raw handle of the stream to launch on (default: the current stream) - the side-stream launches of the
     training step pass it instead of switching torch's current stream (a ``with torch.cuda.stream()`` costs the host ~20 us,
-    61 times per step).  ``defer``: leave the slab reduction to ``flush_wgrad_reduces`` (``out`` given; the caller has made
-    sure a flush follows - ``_wgrad_into``).  ``x_camax`` / ``dy_camax``: per-channel maxima of the operands (``_wsdl_camax`` of a
+    61 times per step).  ``x_camax`` / ``dy_camax``: per-channel maxima of the operands (``_wsdl_camax`` of a
     BatchNorm output / input gradient), ``dy_presplit``: dY as the kernel's fp16 rows (``_wsdl_presplit``) - wsdl_conv2d_wgrad_ex."""
     if dy_camax is None:
         dy_presplit = None
@@ -963,36 +862,12 @@ def conv2d_wgrad(x, dy, wshape, stride, pad, dil, out=None, accumulate=False, x_
     nbytes = _ws_bytes("wsdl_conv2d_wgrad_workspace", *geom)
     if nbytes == 0:
         raise WsdlError("conv2d_wgrad: bad geometry " + repr(geom))
-    if defer and out is not None:
-        dev = _norm_device(x.device)
-        pend = _pending_of(dev)
-        if out.data_ptr() in pend["dws"]:
-            flush_wgrad_reduces(dev)            # a second gradient into the same parameter: the first one's reduction goes first
-        # this layer's OWN workspace: its slabs stay until the multi-reduce has run (and their addresses repeat step after step,
-        # so the descriptor table is uploaded once)
-        wkey = (dev, geom, out.data_ptr())
-        ws = _wgrad_ws.get(wkey)
-        if ws is None or ws.numel() < nbytes:
-            ws = _wgrad_ws[wkey] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=x.device)
-        desc = _ReduceDesc()
-        hs = _stream() if stream is None else stream
-        check(lib().wsdl_conv2d_wgrad_ex(_p(x), _p(dy), _p(out), *geom, int(accumulate), x_bs, dy_bs, _p(x_amax), _p(dy_amax),
-                                         _p(x_camax), _p(dy_camax), _p(dy_presplit), _p(ws), ws.numel(), C.addressof(desc), hs))
-        if desc.kind >= 0:
-            pend["descs"].append(desc)
-            pend["dws"].add(out.data_ptr())
-            pend["keep"].append(ws)
-            pend["side"] = pend["side"] or hs != raw_stream(dev)
-            pend["bytes"] += 4 * desc.S * desc.Cout * desc.Cin * desc.T
-            if pend["bytes"] >= WGRAD_DEFER_BYTES[0] or not _queue_flush(pend):
-                flush_wgrad_reduces(dev)
-        return out
     ws = workspace(nbytes, x.device, stream)
     if out is None:
         out = torch.empty(wshape, device=x.device, dtype=torch.float32)
         accumulate = False
     check(lib().wsdl_conv2d_wgrad_ex(_p(x), _p(dy), _p(out), *geom, int(accumulate), x_bs, dy_bs, _p(x_amax), _p(dy_amax),
-                                     _p(x_camax), _p(dy_camax), _p(dy_presplit), _p(ws), ws.numel(), None,
+                                     _p(x_camax), _p(dy_camax), _p(dy_presplit), _p(ws), ws.numel(),
                                      _stream() if stream is None else stream))
     return out
 
@@ -1038,15 +913,8 @@ def _bn_resident(B, Cc, HW, backward):
     key = ("wsdl_bn_channel_resident", (B, Cc, HW, backward))
     r = _size_cache.get(key)
     if r is None:
-        r = _size_cache[key] = bool(lib().wsdl_bn_channel_resident(B, Cc, HW, backward)) and coop_off()
+        r = _size_cache[key] = bool(lib().wsdl_bn_channel_resident(B, Cc, HW, backward))
     return r
-
-
-def coop_off():
-    return not BN_COOP_ON[0]
-
-
-BN_COOP_ON = [False]       # set by set_option("bn_coop", n > 0): several workgroups per channel publish no per-channel maximum
 
 
 # The ReLU mask of a residual layer as bits written by the forward kernel (1/32 of the bytes of y, which the backward would
@@ -1082,8 +950,7 @@ def bn_train_fwd(x, gamma, beta, running_mean, running_var, momentum, eps, resid
         camax = torch.empty(Cc, device=x.device, dtype=torch.float32)
     check(lib().wsdl_bn_train_fwd(_p(x), _p(gamma), _p(beta), _p(out), _p(mean), _p(invstd), _p(running_mean),
                                   _p(running_var), float(momentum), float(eps), B, Cc, H * W, _p(residual),
-                                  int(relu), y_bs, _p(y_amax), _p(mask), _p(ws), ws.numel(), _p(coop_counters(x.device)),
-                                  _p(camax), _stream()))
+                                  int(relu), y_bs, _p(y_amax), _p(mask), _p(ws), ws.numel(), _p(camax), _stream()))
     if y_amax is not None:
         _publish_amax(out, y_amax)
     if camax is not None:
@@ -1131,7 +998,7 @@ def bn_train_bwd(x, dy, y, gamma, mean, invstd, relu, want_dres, dgamma_out=None
                                   _p(_dense(beta) if mode == 2 else None), _p(mean), _p(invstd), _p(dx),
                                   _p(dgamma), _p(dbeta), _p(dres), B, Cc, H * W, mode, int(acc), dy_bs, y_bs,
                                   _p(dx_amax), _p(relu_mask if mode == 3 else None), _p(ws), ws.numel(),
-                                  _p(coop_counters(x.device)), _p(camax), _p(presplit), _stream()))
+                                  _p(camax), _p(presplit), _stream()))
     if dx_amax is not None:
         _publish_amax(dx, dx_amax)
     if camax is not None:
@@ -1220,7 +1087,7 @@ def _wgrad_into(param, x, dconv, wshape, stride, pad, dil, sink, x_amax=None, la
         stream_wait(hside, _stream())               # dconv / x (and the zero_grad memset) are ready
         # launched ON the side stream by handle: torch's current stream stays the main one
         conv2d_wgrad(x, dconv, wshape, stride, pad, dil, out=param.grad, accumulate=accumulate, x_amax=x_amax,
-                     dy_amax=dy_amax, stream=hside, defer=WGRAD_DEFER[0], x_camax=x_camax, dy_camax=dy_camax,
+                     dy_amax=dy_amax, stream=hside, x_camax=x_camax, dy_camax=dy_camax,
                      dy_presplit=dy_presplit)
         for t in (x_camax, dy_camax, dy_presplit):
             if t is not None:
@@ -1229,7 +1096,7 @@ def _wgrad_into(param, x, dconv, wshape, stride, pad, dil, sink, x_amax=None, la
         dconv.record_stream(side)
     else:
         conv2d_wgrad(x, dconv, wshape, stride, pad, dil, out=param.grad, accumulate=accumulate, x_amax=x_amax,
-                     dy_amax=dy_amax, defer=WGRAD_DEFER[0], x_camax=x_camax, dy_camax=dy_camax, dy_presplit=dy_presplit)
+                     dy_amax=dy_amax, x_camax=x_camax, dy_camax=dy_camax, dy_presplit=dy_presplit)
     sink.grad_ready(param)
 
 

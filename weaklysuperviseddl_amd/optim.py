@@ -155,7 +155,6 @@ class FlatAdam:
         (a collective's work handle)."""
         dev = self.flat_param.device
         lo, hi = self.segments[k]
-        ops.flush_wgrad_reduces(dev)            # the segment's weight gradients may still be un-reduced slabs
         side = ops.side_stream(dev)
         ops.stream_wait(side, ops.raw_stream(dev))
         if not self.capture_mode and self._prep_done[k] is not None:
@@ -222,8 +221,6 @@ class FlatAdam:
 
     def zero_grad(self, set_to_none=False):
         self.sync_hyper()               # (segments may be stepped from backward hooks, before step() is reached)
-        if self.flat_grad.is_cuda:
-            ops.flush_wgrad_reduces(self.flat_grad.device)   # reductions still pending would land in the zeroed buffer
         if self.flat_grad.is_cuda and getattr(self, "_dirty", True):
             ops.join_side_stream(self.flat_grad.device)      # a backward without a step may still be writing
         if self.flat_grad.is_cuda:
@@ -297,8 +294,6 @@ class FlatAdam:
 
     def _step(self):
         self.sync_hyper()
-        if self.flat_param.is_cuda:
-            ops.flush_wgrad_reduces(self.flat_param.device)     # (normally done: the end of the backward pass flushed them)
         if self.pre_step_hook is not None:
             # (the data-parallel reducer's wait(): collectives' work handles, control-plane exchange - host work that a launch
             # plan repeats live at this place)
