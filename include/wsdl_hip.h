@@ -679,6 +679,45 @@ int wsdl_adam_step(float* p, const float* g, float* m, float* v, size_t n, float
 int wsdl_adam_step_dev(float* p, const float* g, float* m, float* v, size_t n, const float* hyper_dev, const int* step_dev,
                        wsdl_stream_t stream);
 
+/* ---- flat optimiser: SGD momentum / Adam + L2 / AdamW, global-norm clipping, non-finite skip (csrc/flat_optim.hip) -
+ * Every per-step quantity is read from device memory (a recorded plan or a captured graph stays valid when one changes):
+ * hyper_dev = WSDL_FLAT_HYPER floats {lr, beta1, beta2, eps, grad_scale, weight_decay, momentum, nesterov, max_norm,
+ * skip_nonfinite} - the first five as wsdl_adam_step_dev reads them; stats_dev = WSDL_FLAT_STATS floats {total_norm,
+ * clip_coef, apply, skipped_steps}.
+ *
+ * Gradient norm in two launches ordered by the stream (no atomics, no last-block counter: bit-reproducible).
+ * wsdl_grad_sqnorm_partials: a fixed grid of wsdl_grad_norm_partials() workgroups of 256 threads, 16-byte loads, grid
+ * stride; every element is squared and summed in double from the first product (1e18 does not overflow, 1e-30 does not
+ * vanish); fixed order inside the workgroup -> one double per workgroup in `partials` (wsdl_grad_norm_workspace() bytes,
+ * 16-byte aligned g). */
+#define WSDL_FLAT_HYPER 10
+#define WSDL_FLAT_STATS 4
+#define WSDL_FLAT_ADAM_L2 0
+#define WSDL_FLAT_ADAMW 1
+#define WSDL_FLAT_SGD 2
+int wsdl_grad_norm_partials(void);
+size_t wsdl_grad_norm_workspace(void);
+int wsdl_grad_sqnorm_partials(const float* g, size_t n, double* partials, wsdl_stream_t stream);
+/* One workgroup sums n_partials doubles in fixed order and writes stats_dev: total_norm = |grad_scale| sqrt(sum);
+ * clip_coef = min(1, max_norm / (total_norm + 1e-6)) when max_norm > 0, else 1 (torch.nn.utils.clip_grad_norm_);
+ * apply = 0 when skip_nonfinite is set and the norm is inf / NaN, else 1.  A skipped step adds 1 to skipped_steps and takes
+ * 1 from *step_dev (later bias corrections are those of a run that did not call step()).  The norm is judged AS THE FLOAT
+ * that total_norm reports: a norm that is finite in double but above FLT_MAX (a few elements of 3e38) is inf there and is
+ * skipped; clip_coef is taken from the double. */
+int wsdl_grad_clip_finalize(const double* partials, int n_partials, const float* hyper_dev, int* step_dev, float* stats_dev,
+                            wsdl_stream_t stream);
+/* One launch over the flat buffers; g is multiplied by grad_scale * clip_coef first, then
+ *   WSDL_FLAT_ADAM_L2: g += wd p; Adam                          (torch.optim.Adam(weight_decay=))
+ *   WSDL_FLAT_ADAMW:   p *= 1 - lr wd; Adam                      (torch.optim.AdamW)
+ *   WSDL_FLAT_SGD:     g += wd p; m = mu m + g; g = nesterov ? g + mu m : m; p -= lr g   (dampening 0, zero-initialised m;
+ *                      mu = 0: m is neither read nor written and may be NULL; v may be NULL always).  The host cannot see
+ *                      mu: with m == NULL the kernel runs SGD WITHOUT momentum whatever hyper_dev says - a caller whose
+ *                      momentum may be non-zero passes m (optim.FlatSGD raises when momentum is set without a buffer).
+ * decay_blocks (optional): one byte per 64 floats of the buffer, 1 = weight decay applies, 0 = it does not; NULL = everywhere.
+ * stats_dev (optional): NULL = no clipping, no skip; apply == 0 leaves p, m, v untouched.  16-byte aligned buffers. */
+int wsdl_flat_step_dev(int algo, float* p, const float* g, float* m, float* v, size_t n, const uint8_t* decay_blocks,
+                       const float* hyper_dev, const int* step_dev, const float* stats_dev, wsdl_stream_t stream);
+
 /* ---- refine_pseudo_mask inner step (TraditionalModel/AlternatingDirectionCutLoss.py:736-757) -
  * KL(softmax(X) || S) with log(X+1e-8), reduction 'batchmean', and its gradient wrt softmax(X). */
 int wsdl_kl_div_fwd_bwd(const float* xn, const float* s, float* loss, float* dxn, size_t n, int batch,

@@ -123,14 +123,17 @@ def evaluate_model(model, dataloader, device, num_classes=2):
 
 def run_supervised_training(data_path='./data', num_epochs=10, batch_size=16, train_ratio=0.85, num_classes=2, lr=1e-4,
                             device=None, *, save_path=SAVE_PATH, seed=None, log=print, backbone_state_dict=None,
-                            resize="host", augment=None, criterion=None):
+                            resize="host", augment=None, criterion=None, optimizer_kind="adam",
+                            optimizer_kwargs=None):
     """Reference ``run_supervised_training`` (SupervisedModel.py:85-122): Adam(lr) (``make_optimizer``) on CrossEntropy,
     validation after every epoch, the final state_dict saved to ``save_path`` (None: not saved), then three evaluations
     of the test split.  ``seed`` seeds torch's global generator first (split, shuffling, initialisation).  Returns the
     final numbers as a dict (the reference returns None).  ``resize``, ``augment``: see ``get_dataloaders`` (the padding of
     ``fill="ignore"`` carries -100, which the CrossEntropyLoss below ignores).  ``criterion``: the loss object instead of
     the reference's ``nn.CrossEntropyLoss()`` - one with class weights, or a ``weaklysuperviseddl_amd.nn.CrossEntropyLoss``
-    (label smoothing, pixel weights); see ``SegmentationModel.resolve_criterion``."""
+    (label smoothing, pixel weights); see ``SegmentationModel.resolve_criterion``.  ``optimizer_kind`` / ``optimizer_kwargs``:
+    ``make_optimizer``'s ``kind`` and keyword arguments - the DeepLabV3 recipe is ``optimizer_kind="sgd",
+    optimizer_kwargs=dict(momentum=0.9, weight_decay=1e-4)``; the default is the reference's Adam(lr)."""
     dev = _device(device)
     if seed is not None:
         torch.manual_seed(seed)
@@ -140,7 +143,7 @@ def run_supervised_training(data_path='./data', num_epochs=10, batch_size=16, tr
     model = initialize_model(num_classes=num_classes, device=dev, backbone_state_dict=backbone_state_dict)
     if criterion is None:
         criterion = nn.CrossEntropyLoss()
-    optimizer = make_optimizer(model, lr=lr)
+    optimizer = make_optimizer(model, lr=lr, kind=optimizer_kind, **(optimizer_kwargs or {}))
 
     train_loss = val_acc = val_iou = float('nan')
     for epoch in range(num_epochs):

@@ -27,7 +27,7 @@ import torch.nn as nn
 from .. import nn as wnn
 from .. import ops
 from .. import plan
-from ..optim import FlatAdam
+from ..optim import FlatAdam, FlatAdamW, FlatSGD
 from .ExtraUtilities import compute_iou_and_acc
 
 
@@ -396,14 +396,20 @@ def _train_step_eager(model, optimizer, images, masks, extra_loss=None, loss_fn=
     return loss.detach()
 
 
-def make_optimizer(model, lr=1e-4, early_step=None):
-    """torch.optim.Adam(model.parameters(), lr) semantics on one flat buffer.  Single process: one Adam launch per step,
+def make_optimizer(model, lr=1e-4, early_step=None, *, kind="adam", **optimizer_kwargs):
+    """torch.optim.Adam(model.parameters(), lr) semantics on one flat buffer.  ``kind``: 'adam' (optim.FlatAdam), 'adamw'
+    (optim.FlatAdamW) or 'sgd' (optim.FlatSGD); ``optimizer_kwargs`` go to that class (weight_decay, momentum, nesterov,
+    max_grad_norm, skip_nonfinite, no_decay, betas, eps ...) - the standard DeepLabV3 recipe is ``kind="sgd", momentum=0.9,
+    weight_decay=1e-4`` with ``optim.PolyLR``.  Single process: one Adam launch per step,
     then the re-layout of every convolution weight on the side stream.  Under ``dp.GradBucketReducer`` the buffer is
     stepped in segments (optim.FlatAdam.enable_early_step): each segment's Adam launch and the re-layout of its
     convolution weights follow its gradient all-reduce.  ``early_step=True`` (or WSDL_EARLY_STEP=1) uses the segments
     in a single process too."""
     params = [p for p in model.parameters() if p.requires_grad]
-    opt = FlatAdam(params, lr=lr)
+    classes = {"adam": FlatAdam, "adamw": FlatAdamW, "sgd": FlatSGD}
+    if kind not in classes:
+        raise ValueError(f"kind {kind!r}: 'adam', 'adamw' or 'sgd'")
+    opt = classes[kind](params, lr=lr, **optimizer_kwargs)
     convs = [m for m in model.modules() if isinstance(m, wnn.Conv2d) and m.weight.requires_grad and m.weight.is_cuda]
     if convs:
         index = {id(p): i for i, p in enumerate(params)}
@@ -467,7 +473,8 @@ def evaluate_model(model, loader, device="cuda", binarize="notebook"):
 
 
 def train_segmentation_model(loss_fn, run_id, lr=1e-4, num_epochs=10, batch_size=4, val_split=0.2, *, out_root="/content",
-                             device="cuda", val_loader=None, num_workers=0, seed=None, log=print, model=None):
+                             device="cuda", val_loader=None, num_workers=0, seed=None, log=print, model=None,
+                             optimizer_kind="adam", optimizer_kwargs=None):
     """Reference ``train_segmentation_model(loss_fn, run_id, lr=1e-4, num_epochs=10, batch_size=4, val_split=0.2)``
     (TraditionalModel/SegmentationModel.py:59-122), same positional signature, returns ``(model, final_loss)``.
 
@@ -481,7 +488,8 @@ def train_segmentation_model(loss_fn, run_id, lr=1e-4, num_epochs=10, batch_size
     accepted and, as in the reference (which never reads it), unused; the per-epoch validation of :118-119 runs when a
     ``val_loader`` of ``(img, (label, trimap))`` items is given (the reference takes it from the Oxford-IIIT Pet download,
     which needs the network).  Keyword-only extras: the directories' root (the reference hard-codes /content), the
-    device, an existing model to continue from."""
+    device, an existing model to continue from, ``optimizer_kind`` / ``optimizer_kwargs`` (``make_optimizer``'s ``kind`` and
+    keyword arguments; the default is the reference's Adam(lr))."""
     from torch.utils.data import DataLoader
     from .SegmentationDataset import PseudoSegmentationDataset
     if loss_fn not in ("cross_entropy", "lovasz_softmax", "lovasz_hinge"):
@@ -495,7 +503,7 @@ def train_segmentation_model(loss_fn, run_id, lr=1e-4, num_epochs=10, batch_size
     if model is None:
         model = build_segmentation_model(num_classes=2)
     model = model.to(device)
-    optimizer = make_optimizer(model, lr=lr)
+    optimizer = make_optimizer(model, lr=lr, kind=optimizer_kind, **(optimizer_kwargs or {}))
     final_loss = 0.0
     for epoch in range(num_epochs):
         model.train()

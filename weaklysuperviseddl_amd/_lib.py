@@ -107,6 +107,11 @@ SIGNATURES = {
     "wsdl_plane_relu_minmax": (_i, [_vp, _vp, _i, _i, _vp]),
     "wsdl_adam_step": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _i, _vp, _f, _vp]),
     "wsdl_adam_step_dev": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "wsdl_grad_norm_partials": (_i, []),
+    "wsdl_grad_norm_workspace": (_sz, []),
+    "wsdl_grad_sqnorm_partials": (_i, [_vp, _sz, _vp, _vp]),
+    "wsdl_grad_clip_finalize": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "wsdl_flat_step_dev": (_i, [_i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "wsdl_kl_div_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, _sz, _vp]),
     "wsdl_kl_div_per_image_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _sz, _vp, _sz, _vp]),
     "wsdl_refine_combine": (_i, [_vp, _vp, _vp, _vp, _f, _f, _vp, _i, _sz, _vp]),

@@ -89,11 +89,13 @@ def control_group(group=None):
 
 
 def sync_initial_state(optimizer, modules=(), group=None, src=0):
-    """Broadcast the flat parameter buffer, the Adam moments / step count and every buffer of ``modules`` from ``src``."""
+    """Broadcast the flat parameter buffer, the Adam moments (FlatSGD: the momentum buffer, if any) / step count and every
+    buffer of ``modules`` from ``src``."""
     if not dist.is_initialized() or _single(group):
         return
     for t in (optimizer.flat_param, optimizer.exp_avg, optimizer.exp_avg_sq):
-        dist.broadcast(t, src=src, group=group)
+        if t is not None:
+            dist.broadcast(t, src=src, group=group)
     step = torch.tensor([optimizer.step_count], dtype=torch.int64)
     dist.broadcast(step, src=src, group=control_group(group))
     optimizer.step_count = int(step.item())

@@ -14,6 +14,8 @@ What makes the step capturable (everything that used to be a host value per step
   * the convolutions' amax slots -> a pool allocated (and therefore re-zeroed) inside the captured region,
   * weight layouts               -> re-written IN PLACE at the end of the step, the main stream joins the side stream
                                     instead of handing events across steps.
+Only the default Adam step is captured: an optimiser with weight decay, ``FlatSGD`` / ``FlatAdamW``, ``max_grad_norm`` or
+``skip_nonfinite`` is refused before capture (``train_step``'s launch plan is the fast path for those).
 Host-side bookkeeping that replay skips (``FlatAdam.step_count``, BatchNorm ``num_batches_tracked``, the cache epochs)
 is advanced by the wrapper.  Data parallelism stays eager: the bucket reducer's control-plane exchange is host code.
 
@@ -37,6 +39,15 @@ class GraphedTrainStep:
         self.key = None
         self._bns = [m for m in model.modules() if isinstance(m, wnn.BatchNorm2d)]
         self._convs = [m for m in model.modules() if isinstance(m, wnn.Conv2d) and m.weight.requires_grad]
+        self._refuse_flat_step()
+
+    def _refuse_flat_step(self):
+        # Weight decay, SGD, clipping and the non-finite skip (optim.FlatAdam.launch_key) are plain kernels but have never been
+        # captured: refused here, before anything is captured.  Their fast path is the launch plan of train_step.
+        launch_key = getattr(self.opt, "launch_key", None)
+        if launch_key is not None and launch_key() != (None, False, False):
+            raise RuntimeError("GraphedTrainStep supports the default FlatAdam step only; with weight decay, FlatSGD, FlatAdamW, "
+                               "max_grad_norm or skip_nonfinite call train_step directly (its launch plan covers them)")
 
     def _eager(self, images, masks):
         return self._train_step(self.model, self.opt, images, masks, self.extra_loss)
@@ -81,6 +92,7 @@ class GraphedTrainStep:
         # copy has to happen OUTSIDE the capture and before each replay (sync_hyper refuses to run inside one)
         opt = self.opt
         key = (tuple(images.shape), tuple(masks.shape), images.device, self.model.training)
+        self._refuse_flat_step()
         if self.calls <= self.warmup or not self.model.training:
             return self._eager(images, masks)
         opt.sync_hyper()

@@ -2595,6 +2595,59 @@ def adam_step_flat(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0, step
                                float(eps), int(step), _p(step_dev), float(grad_scale), _stream()))
 
 
+FLAT_ADAM_L2, FLAT_ADAMW, FLAT_SGD = 0, 1, 2      # WSDL_FLAT_* of the header
+FLAT_HYPER, FLAT_STATS = 10, 4                    # floats in hyper_dev / stats_dev
+FLAT_DECAY_BLOCK = 64                             # floats per entry of a decay table
+
+
+def grad_norm_partials():
+    """Number of double partials the norm's fixed grid writes (its workgroup count)."""
+    return lib().wsdl_grad_norm_partials()
+
+
+def grad_norm(g, hyper_dev, step_dev, stats_dev, partials=None):
+    """Global norm of the flat gradient ``g`` in two stream-ordered launches; writes ``stats_dev`` = (total_norm, clip_coef,
+    apply, skipped_steps) from ``hyper_dev``'s grad_scale, max_norm and skip_nonfinite (include/wsdl_hip.h).  No
+    synchronisation; returns ``stats_dev``.  ``partials``: float64 scratch of ``grad_norm_partials()`` elements."""
+    _req(g, "gradient")
+    _req(hyper_dev, "hyper_dev")
+    _req(stats_dev, "stats_dev")
+    _req(step_dev, "step_dev", torch.int32)
+    if hyper_dev.numel() < FLAT_HYPER or stats_dev.numel() < FLAT_STATS or not g.is_contiguous():
+        raise WsdlError(f"grad_norm: dense gradient, hyper_dev of {FLAT_HYPER} floats and stats_dev of {FLAT_STATS} floats")
+    n_part = grad_norm_partials()
+    if partials is None:
+        partials = torch.empty(lib().wsdl_grad_norm_workspace() // 8, device=g.device, dtype=torch.float64)
+    _req(partials, "partials", torch.float64)
+    if partials.numel() < n_part:
+        raise WsdlError(f"grad_norm: partials needs {n_part} doubles")
+    check(lib().wsdl_grad_sqnorm_partials(_p(g), g.numel(), _p(partials), _stream()))
+    check(lib().wsdl_grad_clip_finalize(_p(partials), n_part, _p(hyper_dev), _p(step_dev), _p(stats_dev), _stream()))
+    return stats_dev
+
+
+def flat_step(algo, p, g, m, v, hyper_dev, step_dev, stats_dev=None, decay_blocks=None):
+    """One launch of the flat step kernel (``algo``: FLAT_ADAM_L2 | FLAT_ADAMW | FLAT_SGD) over dense buffers; every per-step
+    quantity comes from ``hyper_dev`` / ``step_dev`` / ``stats_dev``.  ``decay_blocks``: uint8 per 64 floats (None: decay
+    everywhere); ``stats_dev`` None: no clipping, no skip; ``v`` (and for SGD without momentum ``m``) may be None."""
+    for t in (p, g, m, v):
+        if t is not None:
+            _req(t, "optimiser buffer")
+            if not t.is_contiguous() or t.numel() != p.numel():
+                raise WsdlError("flat_step: buffers must be dense and of one size")
+    _req(hyper_dev, "hyper_dev")
+    if hyper_dev.numel() < FLAT_HYPER or (stats_dev is not None and _req(stats_dev, "stats_dev").numel() < FLAT_STATS):
+        raise WsdlError(f"flat_step: hyper_dev of {FLAT_HYPER} floats, stats_dev of {FLAT_STATS} floats")
+    if step_dev is not None:
+        _req(step_dev, "step_dev", torch.int32)
+    if decay_blocks is not None:
+        _req(decay_blocks, "decay_blocks", torch.uint8)
+        if decay_blocks.numel() < (p.numel() + FLAT_DECAY_BLOCK - 1) // FLAT_DECAY_BLOCK or not decay_blocks.is_contiguous():
+            raise WsdlError("flat_step: decay_blocks needs one dense byte per 64 floats of the buffer")
+    check(lib().wsdl_flat_step_dev(int(algo), _p(p), _p(g), _p(m), _p(v), p.numel(), _p(decay_blocks), _p(hyper_dev),
+                                   _p(step_dev), _p(stats_dev), _stream()))
+
+
 def softmax_channels(x):
     return _SoftmaxChannels.apply(x)
 

@@ -1,5 +1,9 @@
 """FlatAdam - torch.optim.Adam semantics (defaults betas=(0.9,0.999), eps=1e-8, no weight decay;
-reference TraditionalModel/SegmentationModel.py:91) as ONE kernel launch over flat buffers.
+reference TraditionalModel/SegmentationModel.py:91) as ONE kernel launch over flat buffers.  Beyond the reference: weight
+decay (L2 or decoupled: ``FlatAdamW``), SGD with momentum (``FlatSGD``), clipping by the global gradient norm, skipping of steps
+whose gradient is not finite, parameters without decay, and ``PolyLR`` - all of it read from device memory by the kernels of
+csrc/flat_optim.hip, so a launch plan of the step survives a schedule; with those arguments at their defaults the launches are
+the ones below, unchanged.
 
 Parameters are re-homed into one contiguous fp32 buffer (``p.data`` become views) and so are their
 gradients (``p.grad`` views of one flat buffer), which is also what the data-parallel gradient
@@ -33,18 +37,96 @@ RANGE_GUARD_ACTIVE = [False]                                  # "auto" has switc
 RANGE_SENTINEL = [_os.environ.get("WSDL_RANGE_SENTINEL", "1") != "0"]      # FlatAdam.step() checks the step's tensors for regions below the fp16x2 arithmetic's safe range
 
 
+def _is_norm_module(m):
+    from . import nn as wnn
+    import torch.nn as tnn
+    return isinstance(m, (wnn.BatchNorm2d, tnn.modules.batchnorm._BatchNorm, tnn.GroupNorm, tnn.LayerNorm))
+
+
+def no_decay_norm_and_bias(model):
+    """The parameters weight decay usually leaves alone: everything a normalisation layer owns (BatchNorm scale and shift)
+    and every bias.  Returns a list to pass as ``no_decay=``."""
+    out, seen = [], set()
+    for m in model.modules():
+        for name, p in m.named_parameters(recurse=False):
+            if id(p) not in seen and (_is_norm_module(m) or name == "bias" or name.endswith("_bias")):
+                seen.add(id(p))
+                out.append(p)
+    return out
+
+
+def build_decay_blocks(offsets, numels, total, no_decay_flags):
+    """The weight-decay table of the step kernel: one uint8 per ``_ALIGN`` floats of a flat buffer of ``total`` floats, 1 where
+    decay applies.  ``offsets`` / ``numels``: where each parameter starts (a multiple of ``_ALIGN``) and how long it is;
+    ``no_decay_flags[i]`` true: parameter i's blocks are 0.  The padding behind a parameter follows the parameter."""
+    if total % _ALIGN:
+        raise ValueError(f"build_decay_blocks: total {total} is not a multiple of {_ALIGN}")
+    table = torch.ones(total // _ALIGN, dtype=torch.uint8)
+    for off, n, flag in zip(offsets, numels, no_decay_flags):
+        if off % _ALIGN or off + n > total:
+            raise ValueError(f"build_decay_blocks: parameter at {off} (+{n}) does not sit on a {_ALIGN}-float boundary inside {total}")
+        if flag:
+            table[off // _ALIGN:(off + n + _ALIGN - 1) // _ALIGN] = 0
+    return table
+
+
+def _no_decay_flags(params, no_decay):
+    if no_decay is None:
+        return [False] * len(params)
+    if callable(no_decay):
+        return [bool(no_decay(p)) for p in params]
+    ids = {id(p) for p in no_decay}
+    return [id(p) in ids for p in params]
+
+
 class FlatAdam:
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0):
+    """Adam on one flat buffer.  With the keyword arguments at their defaults this is torch.optim.Adam's default step through
+    ``ops.adam_step_flat`` - exactly the launches it always issued.  ``weight_decay`` (L2 as torch.optim.Adam, or
+    ``decoupled=True``: torch.optim.AdamW), ``max_grad_norm`` (torch.nn.utils.clip_grad_norm_ on the whole gradient),
+    ``skip_nonfinite`` (a step whose gradient norm is inf / NaN changes nothing) and ``no_decay`` (a predicate or a
+    collection of parameters without weight decay) go through ``ops.grad_norm`` / ``ops.flat_step`` (csrc/flat_optim.hip).
+    ``max_grad_norm`` / ``skip_nonfinite`` with ``weight_decay=0`` run the Adam + L2 instantiation with wd = 0: the same
+    algorithm, but not the default launch bit for bit (``g += 0 * p`` makes the gradient of a parameter that is already inf
+    a NaN, where the default kernel never multiplies the parameter)."""
+    _early_step = False
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, *, weight_decay=0.0, decoupled=False,
+                 max_grad_norm=None, skip_nonfinite=False, no_decay=None):
+        self._check_args(weight_decay, 0.0, False, max_grad_norm)
+        self.betas, self.eps = betas, eps
+        self.decoupled = bool(decoupled)
+        self.momentum, self.nesterov = 0.0, False
+        self._setup(params, lr, grad_scale, weight_decay, max_grad_norm, skip_nonfinite, no_decay, ("exp_avg", "exp_avg_sq"))
+
+    @staticmethod
+    def _check_args(weight_decay, momentum, nesterov, max_grad_norm):
+        # (host only: no device is touched before the arguments are known to be good)
+        if weight_decay < 0:
+            raise ValueError(f"weight_decay {weight_decay}: must be >= 0")
+        if momentum < 0:
+            raise ValueError(f"momentum {momentum}: must be >= 0")
+        if nesterov and momentum <= 0:
+            raise ValueError("nesterov momentum needs momentum > 0 (and zero dampening)")
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError(f"max_grad_norm {max_grad_norm}: must be > 0 (None: no clipping)")
+
+    def _setup(self, params, lr, grad_scale, weight_decay, max_grad_norm, skip_nonfinite, no_decay, state_names):
         self.params = [p for p in params]
         if not self.params:
-            raise ValueError("FlatAdam: empty parameter list")
+            raise ValueError(f"{type(self).__name__}: empty parameter list")
         dev = self.params[0].device
-        self.lr, self.betas, self.eps, self.grad_scale = lr, betas, eps, grad_scale
-        self.step_count = 0
+        self.lr, self.grad_scale = lr, grad_scale
+        self.weight_decay, self.max_grad_norm, self.skip_nonfinite = weight_decay, max_grad_norm, bool(skip_nonfinite)
+        self.step_count = 0             # calls of step(); the kernels read step_dev, which a skipped step does not advance
         self.step_dev = torch.zeros(1, device=dev, dtype=torch.int32) if dev.type == "cuda" else None   # device twin
-        # lr, beta1, beta2, eps, grad_scale as the Adam kernel reads them (device floats: a schedule or a reducer changing one of
-        # them changes memory, not a launch - a recorded launch plan of the step stays valid); sync_hyper() keeps them current
-        self.hyper_dev = torch.zeros(5, device=dev, dtype=torch.float32) if dev.type == "cuda" else None
+        # lr, beta1, beta2, eps, grad_scale as the Adam kernel reads them, then weight_decay, momentum, nesterov, max_norm,
+        # skip_nonfinite for the flat step (device floats: a schedule or a reducer changing one of them changes memory, not a
+        # launch - a recorded launch plan of the step stays valid); sync_hyper() keeps them current
+        self.hyper_dev = torch.zeros(ops.FLAT_HYPER, device=dev, dtype=torch.float32) if dev.type == "cuda" else None
+        # total_norm, clip_coef, apply, skipped_steps - written by the norm's finalize launch, read by the step kernel
+        self.stats_dev = torch.tensor([0., 1., 1., 0.], device=dev, dtype=torch.float32) if dev.type == "cuda" else None
+        self._norm_partials = (torch.zeros(ops.grad_norm_partials(), device=dev, dtype=torch.float64)
+                               if dev.type == "cuda" else None)     # scratch of the norm's first launch
         self._hyper_host = None
         self.offsets, n = [], 0
         for p in self.params:
@@ -53,8 +135,12 @@ class FlatAdam:
         self.numel = n
         self.flat_param = torch.zeros(n, device=dev, dtype=torch.float32)
         self.flat_grad = torch.zeros(n, device=dev, dtype=torch.float32)
-        self.exp_avg = torch.zeros(n, device=dev, dtype=torch.float32)
-        self.exp_avg_sq = torch.zeros(n, device=dev, dtype=torch.float32)
+        for name in ("exp_avg", "exp_avg_sq"):          # (FlatSGD: exp_avg is the momentum buffer, None without momentum)
+            setattr(self, name, torch.zeros(n, device=dev, dtype=torch.float32) if name in state_names else None)
+        flags = _no_decay_flags(self.params, no_decay)
+        self.decay_blocks = None        # None: weight decay everywhere
+        if any(flags):
+            self.decay_blocks = build_decay_blocks(self.offsets, [p.numel() for p in self.params], n, flags).to(dev)
         with torch.no_grad():
             for p, off in zip(self.params, self.offsets):
                 view = self.flat_param[off:off + p.numel()].view_as(p)
@@ -92,7 +178,7 @@ class FlatAdam:
             self.seg_of.append(max(k for k, (lo, _hi) in enumerate(self.segments) if lo <= off))
         self.seg_params = [[i for i, k in enumerate(self.seg_of) if k == kk] for kk in range(len(self.segments))]
         self.segment_hook = segment_hook
-        self.early_step = False         # True: step segments as backward completes them (False: one launch in step(),
+        self._early_step = False        # True: step segments as backward completes them (False: one launch in step(),
                                         # unless a data-parallel reducer drives the segments - external_trigger)
         self.external_trigger = False   # True: someone else (the DP reducer) decides when a segment is complete
         self.capture_mode = False       # inside hipGraph capture: no cross-replay events
@@ -153,6 +239,7 @@ class FlatAdam:
         """Adam on segment k, enqueued on the side stream behind the main stream's work so far (BatchNorm / bias
         gradients, the input-gradient kernels that still read this segment's weight layouts) and behind ``after``
         (a collective's work handle)."""
+        self._refuse_early_norm()
         dev = self.flat_param.device
         lo, hi = self.segments[k]
         side = ops.side_stream(dev)
@@ -166,9 +253,7 @@ class FlatAdam:
             if not any(self._stepped):
                 self.step_count += 1
                 ops.add_int(self.step_dev, 1)
-            ops.adam_step_flat(self.flat_param[lo:hi], self.flat_grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
-                               self.lr, self.betas[0], self.betas[1], self.eps, self.step_count, self.grad_scale,
-                               step_dev=self.step_dev, hyper_dev=self.hyper_dev)
+            self._launch(lo, hi)
             if not self.capture_mode:
                 ev = self._seg_events[k]               # one event per segment, re-recorded step after step
                 if ev is None:
@@ -194,17 +279,95 @@ class FlatAdam:
         self._remaining = [sum(1 for i in idx if i in self._expected) for idx in self.seg_params]
         self._backward_pending = False
 
+    # ---------------------------------------------------------------------------------- which launches a step issues
+    def algo(self):
+        """None: the default Adam step (``ops.adam_step_flat``); else the ``ops.FLAT_*`` algorithm of ``ops.flat_step``."""
+        if self.weight_decay == 0 and not self.needs_norm():
+            return None
+        return ops.FLAT_ADAMW if self.decoupled else ops.FLAT_ADAM_L2
+
+    def needs_norm(self):
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    def launch_key(self):
+        """What of the optimiser's settings selects LAUNCHES (not values in device memory): part of a launch plan's key."""
+        return (self.algo(), self.needs_norm(), self.decay_blocks is not None)
+
+    @property
+    def early_step(self):
+        return self._early_step
+
+    @early_step.setter
+    def early_step(self, value):
+        if value and self.needs_norm():
+            raise RuntimeError(self._EARLY_NORM)
+        self._early_step = value
+
+    _EARLY_NORM = ("max_grad_norm / skip_nonfinite need the norm of the WHOLE gradient before any parameter is stepped: segments "
+                   "cannot be stepped while backward still runs.  Set optimizer.early_step = False (under a data-parallel reducer "
+                   "the buffer is then stepped once, behind the last all-reduce).")
+
+    def _refuse_early_norm(self):
+        if self.needs_norm():
+            raise RuntimeError(self._EARLY_NORM)
+
+    def _hyper_values(self):
+        return (float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.grad_scale),
+                float(self.weight_decay), float(self.momentum), float(bool(self.nesterov)),
+                float(self.max_grad_norm or 0.0), float(bool(self.skip_nonfinite)))
+
+    def state_tensors(self):
+        """Every device tensor of the optimiser a step changes in place (a launch plan's verification compares and restores
+        them): parameters, state buffers, the device step number, the norm / skip statistics."""
+        return [t for t in (self.flat_param, self.exp_avg, self.exp_avg_sq, self.step_dev, self.stats_dev) if t is not None]
+
+    def _grad_norm_launches(self):
+        ops.grad_norm(self.flat_grad, self.hyper_dev, self.step_dev, self.stats_dev, self._norm_partials)
+
+    def grad_norm(self):
+        """Norm of the (grad_scale-averaged) gradient as a device scalar, no synchronisation: with clipping / skipping on, what
+        the last step measured before it clipped; otherwise measured now from the gradient buffer."""
+        if not self.flat_grad.is_cuda:
+            raise ops.WsdlError("grad_norm: gradients are not on the device; there is no CPU fallback")
+        if not self.needs_norm():
+            self.sync_hyper()
+            self._grad_norm_launches()
+        return self.stats_dev[0]
+
+    def skipped_steps(self):
+        """How many steps ``skip_nonfinite`` has dropped, as a device scalar (float), no synchronisation."""
+        if self.stats_dev is None:
+            raise ops.WsdlError("skipped_steps: the optimiser is not on the device")
+        return self.stats_dev[3]
+
+    def _launch(self, lo, hi):
+        """The step launch on [lo, hi) of the flat buffers (the whole buffer, or one segment: ``lo`` on a parameter boundary)."""
+        algo = self.algo()
+        cut = (lambda t: None if t is None else t[lo:hi]) if (lo, hi) != (0, self.numel) else (lambda t: t)
+        if algo is None:
+            ops.adam_step_flat(cut(self.flat_param), cut(self.flat_grad), cut(self.exp_avg), cut(self.exp_avg_sq), self.lr,
+                               self.betas[0], self.betas[1], self.eps, self.step_count, self.grad_scale,
+                               step_dev=self.step_dev, hyper_dev=self.hyper_dev)
+            return
+        table = self.decay_blocks
+        if table is not None and (lo, hi) != (0, self.numel):
+            table = table[lo // _ALIGN:(hi + _ALIGN - 1) // _ALIGN]
+        ops.flat_step(algo, cut(self.flat_param), cut(self.flat_grad), cut(self.exp_avg), cut(self.exp_avg_sq), self.hyper_dev,
+                      self.step_dev, self.stats_dev if self.needs_norm() else None, table)
+
     def sync_hyper(self):
-        """Copy (lr, beta1, beta2, eps, grad_scale) to the device when one of them changed since the last call.
+        """Copy (lr, beta1, beta2, eps, grad_scale, weight_decay, momentum, nesterov, max_norm, skip_nonfinite) to the device when
+        one of them changed since the last call.
 
         Never inside a stream capture: the copy is a pageable host-to-device transfer (illegal in a hipGraph capture, and a
         captured copy would freeze the values anyway).  ``GraphedTrainStep`` calls this BEFORE it captures and before every
         replay, so the captured Adam node reads current values from ``hyper_dev``; a change that turns up while a capture is
         running is an error, not something to skip silently."""
-        cur = (float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.grad_scale))
+        cur = self._hyper_values()
         if self.hyper_dev is not None and cur != self._hyper_host:
             if self.hyper_dev.is_cuda and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("FlatAdam.sync_hyper: lr / betas / eps / grad_scale changed inside a stream capture; change "
+                raise RuntimeError("FlatAdam.sync_hyper: a value of hyper_dev (lr, betas, eps, grad_scale, weight_decay, momentum, "
+                                   "nesterov, max_grad_norm, skip_nonfinite) changed inside a stream capture; change "
                                    "them between steps (GraphedTrainStep copies them to the device before each replay)")
             self.hyper_dev.copy_(torch.tensor(cur, dtype=torch.float32))
             self._hyper_host = cur
@@ -313,12 +476,82 @@ class FlatAdam:
         if self.flat_param.is_cuda:
             # the kernel reads the step number from the device: a captured (hipGraph) step replays correctly
             ops.add_int(self.step_dev, 1)
-            ops.adam_step_flat(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.lr,
-                               self.betas[0], self.betas[1], self.eps, self.step_count, self.grad_scale,
-                               step_dev=self.step_dev, hyper_dev=self.hyper_dev)
+            if self.needs_norm():
+                # the whole gradient is in flat_grad here (hook run, side stream joined): norm, clip coefficient and the
+                # skip decision stay on the device, the step launch reads them
+                self._grad_norm_launches()
+            self._launch(0, self.numel)
         else:
             raise ops.WsdlError("FlatAdam.step: parameters are not on the device; there is no CPU fallback")
         self._dirty = False                     # (joined above)
         self._sentinel()
         if self.post_step_hook is not None:
             self.post_step_hook()
+
+
+class FlatAdamW(FlatAdam):
+    """torch.optim.AdamW: ``FlatAdam`` with decoupled weight decay, default 1e-2."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, *, weight_decay=1e-2, decoupled=True,
+                 max_grad_norm=None, skip_nonfinite=False, no_decay=None):
+        super().__init__(params, lr, betas, eps, grad_scale, weight_decay=weight_decay, decoupled=decoupled,
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, no_decay=no_decay)
+
+
+class FlatSGD(FlatAdam):
+    """torch.optim.SGD (dampening 0) on the flat buffers: ``g += wd p; buf = mu buf + g; g = nesterov ? g + mu buf : buf;
+    p -= lr g`` - the zero-initialised buffer reproduces torch's first step.  A subclass of ``FlatAdam`` for everything
+    that is not the arithmetic: the flat layout, gradient sinks, segments, hooks, ``sync_hyper``, launch plans.  ``exp_avg``
+    is the momentum buffer (None when constructed without momentum), there is no second buffer."""
+    def __init__(self, params, lr=1e-3, momentum=0.0, nesterov=False, weight_decay=0.0, *, grad_scale=1.0, max_grad_norm=None,
+                 skip_nonfinite=False, no_decay=None):
+        self._check_args(weight_decay, momentum, nesterov, max_grad_norm)
+        self.betas, self.eps = (0.0, 0.0), 0.0          # (unused by the SGD kernel; the slots of hyper_dev stay)
+        self.decoupled = False
+        self.momentum, self.nesterov = momentum, bool(nesterov)
+        self._setup(params, lr, grad_scale, weight_decay, max_grad_norm, skip_nonfinite, no_decay,
+                    ("exp_avg",) if momentum > 0 else ())
+
+    def algo(self):
+        return ops.FLAT_SGD
+
+    def _hyper_values(self):
+        self._check_args(self.weight_decay, self.momentum, self.nesterov, self.max_grad_norm)
+        if self.momentum > 0 and self.exp_avg is None:
+            raise ValueError("FlatSGD: momentum was switched on after construction without momentum: there is no buffer for it")
+        return super()._hyper_values()
+
+
+class PolyLR:
+    """torch.optim.lr_scheduler.PolynomialLR with a linear warm-up and a floor, for the flat optimisers: ``step()`` sets
+    ``optimizer.lr`` on the host, ``sync_hyper()`` carries it to the device before the next step - no kernel, and a recorded
+    launch plan is kept.  After ``t`` calls of ``step()``:
+      t <  warmup_steps: lr = base_lr (t + 1) / (warmup_steps + 1)
+      t >= warmup_steps: lr = min_lr + (base_lr - min_lr) (1 - min(t - warmup_steps, T) / T) ** power,  T = total_steps - warmup_steps
+    (``warmup_steps = 0, min_lr = 0``: PolynomialLR(total_iters=total_steps, power) in closed form)."""
+
+    def __init__(self, optimizer, total_steps, power=0.9, warmup_steps=0, min_lr=0.0):
+        if total_steps <= 0 or not 0 <= warmup_steps < total_steps:
+            raise ValueError("PolyLR: total_steps > 0 and 0 <= warmup_steps < total_steps")
+        if min_lr < 0 or power <= 0:
+            raise ValueError("PolyLR: min_lr >= 0 and power > 0")
+        self.optimizer, self.total_steps, self.power = optimizer, int(total_steps), float(power)
+        self.warmup_steps, self.min_lr = int(warmup_steps), float(min_lr)
+        self.base_lr = float(optimizer.lr)
+        self.last_step = 0
+        optimizer.lr = self.lr_at(0)
+
+    def lr_at(self, t):
+        if t < self.warmup_steps:
+            return self.base_lr * (t + 1) / (self.warmup_steps + 1)
+        T = self.total_steps - self.warmup_steps
+        left = 1.0 - min(t - self.warmup_steps, T) / T
+        return self.min_lr + (self.base_lr - self.min_lr) * left ** self.power
+
+    def step(self):
+        self.last_step += 1
+        self.optimizer.lr = self.lr_at(self.last_step)
+        return self.optimizer.lr
+
+    def get_last_lr(self):
+        return [self.optimizer.lr]

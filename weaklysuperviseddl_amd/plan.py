@@ -181,7 +181,7 @@ class PlannedTrainStep:
                 tuple((d.training, float(d.p)) for d in self._dropouts), self.loss_scalars,
                 tuple(p.requires_grad for p in opt.params), ops.LAYOUT_EPOCH[0],
                 ops.CONV_ARITH[0], ops.OVERLAP_WGRAD[0], ops.WGRAD_AFTER_DGRAD[0], ops.BN_RELU_BITS[0], ops.IDENTITY_LINK[0], ops.ASPP_MULTI[0], ops.ASPP_GROUP_FWD[0],
-                ops.raw_stream(images.device))
+                ops.raw_stream(images.device), opt.launch_key())
 
     def usable(self, images, masks):
         opt = self.opt
@@ -201,7 +201,7 @@ class PlannedTrainStep:
     def _state(self):
         """Every device tensor a training step changes in place (what the verification compares and restores)."""
         opt = self.opt
-        ts = [opt.flat_param, opt.exp_avg, opt.exp_avg_sq, opt.step_dev]
+        ts = list(opt.state_tensors())      # parameters, moments / momentum buffer, device step number, norm / skip statistics
         ts += [b for b in self.model.buffers() if b.is_cuda and b.dim() > 0]
         ts += [m._counter for m in self._dropouts if m._counter is not None]
         return ts
@@ -362,7 +362,7 @@ class PlannedTrainStep:
             return self._record(images, masks, key)
         if not self._layouts_current(ent):
             self._relayout()
-        self.opt.sync_hyper()                   # a learning-rate schedule: five floats in device memory, the plan stays
+        self.opt.sync_hyper()                   # a learning-rate schedule: ten floats in device memory, the plan stays
         self.plan, self.key, self.s_images, self.s_masks, self.s_loss = ent.plan, key, ent.s_images, ent.s_masks, ent.s_loss
         if images.data_ptr() != ent.s_images.data_ptr():
             ent.s_images.copy_(images)
