@@ -718,6 +718,45 @@ int wsdl_grad_clip_finalize(const double* partials, int n_partials, const float*
 int wsdl_flat_step_dev(int algo, float* p, const float* g, float* m, float* v, size_t n, const uint8_t* decay_blocks,
                        const float* hyper_dev, const int* step_dev, const float* stats_dev, wsdl_stream_t stream);
 
+/* ---- pixel mining: selecting pixels by their loss without a host read (csrc/pixel_mining.hip) -
+ * wsdl_kth_value: x holds `segments` runs of n_per_segment floats.  The candidates of segment s are the x[s*n + i] that are
+ * not NaN and, when `valid` (one byte per element) is given, have valid[s*n + i] != 0; n_valid[s] receives their number n.
+ * The rank is computed ON THE DEVICE, in double: k = min(n, k_abs + floor(k_frac * n)); value[s] = the k-th largest
+ * candidate (largest != 0) or the k-th smallest - an element of x, bit for bit (-0.0 and +0.0 are different keys that
+ * compare equal: either may come back).  k == 0 (n == 0 included): +inf for largest, -inf for smallest, so that a
+ * ">= value" / "<= value" test keeps nothing.  Any finite float, denormals and +-inf are ordered by the usual monotone
+ * 32-bit key.
+ * Most-significant-digit radix select, 4 passes of 8 bits, each pass one launch on `stream` (plus the memset of the
+ * workspace and a one-workgroup launch per segment that writes the results): workgroups count their digit in LDS -
+ * privatised per wave, equal digits of a wave aggregated before the atomic - and merge with integer atomics into the
+ * segment's histogram; every workgroup of the next pass finds the chosen bin for itself.  Nothing waits for another
+ * workgroup, no float atomics: the result does not depend on the arrival order (bitwise reproducible).
+ * ws: wsdl_kth_workspace(segments) bytes, 4-byte aligned.  1 <= n_per_segment < 2^31, 1 <= segments <= 65535,
+ * k_abs >= 0, 0 <= k_frac <= 1. */
+#define WSDL_MINING_HARD 0
+#define WSDL_MINING_TRIM 1
+size_t wsdl_kth_workspace(int segments);
+int wsdl_kth_value(const float* x, const uint8_t* valid, long long n_per_segment, int segments, int largest, long long k_abs,
+                   double k_frac, float* value, long long* n_valid, void* ws, size_t ws_bytes, wsdl_stream_t stream);
+/* valid_out[i] = 1 where labels[i] != ignore_index and (pixel_weight == NULL or pixel_weight[i] != 0), else 0: the pixels
+ * wsdl_softmax_ce_ex_fwd_bwd does not ignore. */
+int wsdl_mining_valid(const int64_t* labels, long long ignore_index, const float* pixel_weight, uint8_t* valid_out, long long n,
+                      wsdl_stream_t stream);
+/* The selection as a pixel weight for wsdl_softmax_ce_ex_fwd_bwd: weight_out[i] = pixel_weight[i] (or 1) where pixel i of
+ * segment s is valid and selected, else 0.  WSDL_MINING_HARD selects nll >= min(tau[s], tau_cap) (tau: the k-th largest
+ * loss, tau_cap = -log(thresh) or +inf: online hard example mining, at least k pixels), WSDL_MINING_TRIM selects
+ * nll <= tau[s].  Ties at the threshold are all selected.  A valid pixel whose nll is NaN (a label outside [0,C)) keeps
+ * its weight, so that the cross entropy is poisoned as it is without mining.  kept[s] = the number of selected pixels
+ * (one integer per workgroup in ws, summed in fixed order by a second launch; no atomics).
+ * ws: wsdl_mining_weights_workspace(segments) bytes, 4-byte aligned. */
+size_t wsdl_mining_weights_workspace(int segments);
+int wsdl_mining_weights(const float* nll, const uint8_t* valid, const float* pixel_weight, const float* tau, float tau_cap,
+                        int mode, long long n_per_segment, int segments, float* weight_out, long long* kept, void* ws,
+                        size_t ws_bytes, wsdl_stream_t stream);
+/* out[i] = dl[i] * s[0] with a zero staying zero (wsdl_scale_by_device_scalar otherwise, same bits): when nothing is
+ * selected the mean's denominator is 0 and s = inf - the gradient is then 0 everywhere, as torch's over ignored pixels. */
+int wsdl_mining_scale_grad(const float* dl, const float* s, float* out, size_t n, wsdl_stream_t stream);
+
 /* ---- refine_pseudo_mask inner step (TraditionalModel/AlternatingDirectionCutLoss.py:736-757) -
  * KL(softmax(X) || S) with log(X+1e-8), reduction 'batchmean', and its gradient wrt softmax(X). */
 int wsdl_kl_div_fwd_bwd(const float* xn, const float* s, float* loss, float* dxn, size_t n, int batch,

@@ -474,7 +474,7 @@ def evaluate_model(model, loader, device="cuda", binarize="notebook"):
 
 def train_segmentation_model(loss_fn, run_id, lr=1e-4, num_epochs=10, batch_size=4, val_split=0.2, *, out_root="/content",
                              device="cuda", val_loader=None, num_workers=0, seed=None, log=print, model=None,
-                             optimizer_kind="adam", optimizer_kwargs=None):
+                             optimizer_kind="adam", optimizer_kwargs=None, criterion=None):
     """Reference ``train_segmentation_model(loss_fn, run_id, lr=1e-4, num_epochs=10, batch_size=4, val_split=0.2)``
     (TraditionalModel/SegmentationModel.py:59-122), same positional signature, returns ``(model, final_loss)``.
 
@@ -489,7 +489,9 @@ def train_segmentation_model(loss_fn, run_id, lr=1e-4, num_epochs=10, batch_size
     ``val_loader`` of ``(img, (label, trimap))`` items is given (the reference takes it from the Oxford-IIIT Pet download,
     which needs the network).  Keyword-only extras: the directories' root (the reference hard-codes /content), the
     device, an existing model to continue from, ``optimizer_kind`` / ``optimizer_kwargs`` (``make_optimizer``'s ``kind`` and
-    keyword arguments; the default is the reference's Adam(lr))."""
+    keyword arguments; the default is the reference's Adam(lr)), ``criterion`` (handed to ``train_step`` in place of
+    ``loss_fn``'s loss, e.g. ``wnn.MinedCrossEntropyLoss(mode="trim", drop_frac=0.2)`` against the label noise of the pseudo
+    masks; ``None``: the ``loss_fn`` loss as before)."""
     from torch.utils.data import DataLoader
     from .SegmentationDataset import PseudoSegmentationDataset
     if loss_fn not in ("cross_entropy", "lovasz_softmax", "lovasz_hinge"):
@@ -511,7 +513,7 @@ def train_segmentation_model(loss_fn, run_id, lr=1e-4, num_epochs=10, batch_size
         for images, masks in train_loader:
             if images.size(0) == 1:
                 continue
-            total += train_step(model, optimizer, images.to(device), masks.to(device), loss_fn=loss_fn)
+            total += train_step(model, optimizer, images.to(device), masks.to(device), loss_fn=loss_fn, criterion=criterion)
         final_loss = total.item()                       # one host read per epoch (the reference: one per step)
         if log:
             log(f"[Run {run_id}] Epoch {epoch + 1}/{num_epochs}, Loss: {final_loss:.4f}")

@@ -112,6 +112,12 @@ SIGNATURES = {
     "wsdl_grad_sqnorm_partials": (_i, [_vp, _sz, _vp, _vp]),
     "wsdl_grad_clip_finalize": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "wsdl_flat_step_dev": (_i, [_i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "wsdl_kth_workspace": (_sz, [_i]),
+    "wsdl_kth_value": (_i, [_vp, _vp, _ll, _i, _i, _ll, C.c_double, _vp, _vp, _vp, _sz, _vp]),
+    "wsdl_mining_valid": (_i, [_vp, _ll, _vp, _vp, _ll, _vp]),
+    "wsdl_mining_weights_workspace": (_sz, [_i]),
+    "wsdl_mining_weights": (_i, [_vp, _vp, _vp, _vp, _f, _i, _ll, _i, _vp, _vp, _vp, _sz, _vp]),
+    "wsdl_mining_scale_grad": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "wsdl_kl_div_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, _sz, _vp]),
     "wsdl_kl_div_per_image_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _sz, _vp, _sz, _vp]),
     "wsdl_refine_combine": (_i, [_vp, _vp, _vp, _vp, _f, _f, _vp, _i, _sz, _vp]),

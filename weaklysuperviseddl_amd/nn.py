@@ -272,3 +272,91 @@ class CrossEntropyLoss(nn.Module):
     def extra_repr(self):
         return (f"ignore_index={self.ignore_index}, reduction={self.reduction!r}, label_smoothing={self.label_smoothing}, "
                 f"weight={self.weight is not None}, pixel_weight={None if self.pixel_weight is None else tuple(self.pixel_weight.shape)}")
+
+
+class MinedCrossEntropyLoss(nn.Module):
+    """Cross entropy over the pixels their own loss selects (``ops.cross_entropy_mined``): ``mode="hard"`` is online hard
+    example mining / bootstrapped cross entropy - the pixels whose true-class probability is at most ``thresh``, at least
+    ``min_kept`` per image - and ``mode="trim"`` drops the fraction ``drop_frac`` of largest loss, the guard against the
+    label noise of pseudo masks.  ``scope="batch"`` ranks the pixels of the whole batch (``min_kept * B`` of them),
+    ``"image"`` each image by itself.  The selection is made on the device from a count that never reaches the host, ties
+    at the threshold are all kept (see ``ops.cross_entropy_mined``), and ``weight`` / ``label_smoothing`` / ``reduction``
+    ('mean' or 'sum') apply to the kept pixels as in ``CrossEntropyLoss``.
+
+    Conventions of ``CrossEntropyLoss``: ``set_pixel_weight(t)`` copies a (B,H,W) confidence map into a buffer this object
+    owns (a pixel of weight 0 is no candidate); ``threshold`` (float32), ``kept`` and ``valid`` (int64, one entry per scope
+    segment) and ``selection`` (float32 (B,H,W): the weights the loss was taken with) are buffers of this object, filled by
+    every call and allocated anew only when the shape changes, so the addresses a launch plan freezes stay put; every option
+    and every address is a plain attribute, so ``plan.host_scalars`` puts them into the plan key and a changed ``drop_frac``
+    records a new plan.  Read the statistics after the step; reading them synchronises, the step does not.  (The one step that
+    records a launch plan verifies it on a probe batch and leaves the probe's statistics in the buffers.)
+
+    Under data parallelism each rank selects within its own shard: ``scope="batch"`` means the rank's batch, and the ranks'
+    thresholds differ.
+
+        crit = wnn.MinedCrossEntropyLoss(mode="trim", drop_frac=0.2, scope="image")     # noisy pseudo masks
+        loss = train_step(model, optimizer, images, pseudo_masks, criterion=crit)
+    """
+
+    def __init__(self, mode="hard", thresh=0.7, min_kept=0, drop_frac=0.0, scope="batch", weight=None, ignore_index=-100,
+                 reduction="mean", label_smoothing=0.0):
+        super().__init__()
+        ops.check_mining_options(mode, thresh, min_kept, drop_frac, scope, reduction, label_smoothing)
+        if weight is not None and (not torch.is_tensor(weight) or weight.dim() != 1):
+            raise ValueError("MinedCrossEntropyLoss: weight must be a (C,) tensor")
+        self.register_buffer("weight", None if weight is None else weight.detach().to(torch.float32).clone())
+        for name in ("pixel_weight", "threshold", "kept", "valid", "selection"):
+            self.register_buffer(name, None, persistent=False)
+        self.mode = mode
+        self.thresh = None if thresh is None else float(thresh)
+        self.min_kept = int(min_kept)
+        self.drop_frac = float(drop_frac)
+        self.scope = scope
+        self.ignore_index = int(ignore_index)
+        self.reduction = reduction
+        self.label_smoothing = float(label_smoothing)
+        self._refresh_pointers()
+
+    def _refresh_pointers(self):
+        for name in ("weight", "pixel_weight", "threshold", "kept", "valid", "selection"):
+            t = getattr(self, name)
+            setattr(self, name + "_ptr", 0 if t is None else t.data_ptr())
+        self.pixel_weight_shape = "" if self.pixel_weight is None else "x".join(str(d) for d in self.pixel_weight.shape)
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self._refresh_pointers()
+        return out
+
+    def set_pixel_weight(self, t):
+        if t is None:
+            self.pixel_weight = None
+        else:
+            if not torch.is_tensor(t) or t.dim() != 3:
+                raise ValueError("MinedCrossEntropyLoss.set_pixel_weight: a (B,H,W) tensor or None")
+            cur = self.pixel_weight
+            if cur is None or cur.shape != t.shape or cur.device != t.device:
+                self.pixel_weight = torch.empty(t.shape, device=t.device, dtype=torch.float32)
+            self.pixel_weight.copy_(t.detach())
+        self._refresh_pointers()
+        return self
+
+    def forward(self, logits, labels):
+        # (options may have been assigned since the constructor checked them)
+        ops.check_mining_options(self.mode, self.thresh, self.min_kept, self.drop_frac, self.scope, self.reduction,
+                                 self.label_smoothing)
+        stats = {k: getattr(self, k) for k in ("threshold", "kept", "valid", "selection")}
+        loss = ops.cross_entropy_mined(logits, labels.long(), self.ignore_index, mode=self.mode, thresh=self.thresh,
+                                       min_kept=self.min_kept, drop_frac=self.drop_frac, scope=self.scope, weight=self.weight,
+                                       label_smoothing=self.label_smoothing, pixel_weight=self.pixel_weight,
+                                       reduction=self.reduction, stats=stats)
+        for k, t in stats.items():
+            if getattr(self, k) is not t:
+                setattr(self, k, t)
+        self._refresh_pointers()
+        return loss
+
+    def extra_repr(self):
+        return (f"mode={self.mode!r}, thresh={self.thresh}, min_kept={self.min_kept}, drop_frac={self.drop_frac}, "
+                f"scope={self.scope!r}, ignore_index={self.ignore_index}, reduction={self.reduction!r}, "
+                f"label_smoothing={self.label_smoothing}, weight={self.weight is not None}")

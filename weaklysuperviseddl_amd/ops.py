@@ -1687,7 +1687,7 @@ class _SoftmaxCEEx(torch.autograd.Function):
     with its options on (wsdl_softmax_ce_ex_fwd_bwd).  The gradient flows into the logits only."""
 
     @staticmethod
-    def forward(ctx, logits, labels, ignore_index, weight, pixel_weight, label_smoothing, reduction):
+    def forward(ctx, logits, labels, ignore_index, weight, pixel_weight, label_smoothing, reduction, keep_zeros=False):
         logits = _dense(logits, "logits")
         labels = _req(labels, "labels", torch.int64).contiguous()
         B, Cc, H, W = logits.shape
@@ -1703,6 +1703,7 @@ class _SoftmaxCEEx(torch.autograd.Function):
                                                int(ignore_index), _p(weight), _p(pixel_weight), float(label_smoothing),
                                                int(reduction), _p(ws), ws.numel(), _stream()))
         ctx.none = none
+        ctx.keep_zeros = bool(keep_zeros)
         ctx.save_for_backward(dl, inv)
         return loss
 
@@ -1716,8 +1717,11 @@ class _SoftmaxCEEx(torch.autograd.Function):
         else:
             sc = torch.empty_like(inv)
             check(lib().wsdl_mul(_p(_dense(g.reshape(1))), _p(inv), _p(sc), 1, _stream()))      # upstream gradient x 1 / denominator
-            check(lib().wsdl_scale_by_device_scalar(_p(dl), _p(sc), _p(out), dl.numel(), _stream()))
-        return out, None, None, None, None, None, None
+            if ctx.keep_zeros:      # cross_entropy_mined: a pixel that is not selected has gradient 0 also when NOTHING is selected (sc = inf)
+                check(lib().wsdl_mining_scale_grad(_p(dl), _p(sc), _p(out), dl.numel(), _stream()))
+            else:
+                check(lib().wsdl_scale_by_device_scalar(_p(dl), _p(sc), _p(out), dl.numel(), _stream()))
+        return out, None, None, None, None, None, None, None
 
 
 class _PairwiseAffinityLoss(torch.autograd.Function):
@@ -2193,6 +2197,11 @@ def cross_entropy(logits, labels, ignore_index=-100, *, weight=None, label_smoot
     check_cross_entropy_options(reduction, label_smoothing)
     if weight is None and pixel_weight is None and label_smoothing == 0.0 and reduction == "mean":
         return _SoftmaxCE.apply(logits, labels, ignore_index)
+    return _cross_entropy_ex(logits, labels, ignore_index, weight, label_smoothing, reduction, pixel_weight)
+
+
+def _cross_entropy_ex(logits, labels, ignore_index, weight, label_smoothing, reduction, pixel_weight, keep_zeros=False):
+    """``cross_entropy`` with options, after their check.  ``keep_zeros``: see ``_SoftmaxCEEx.backward``."""
     if logits.dim() != 4:
         raise WsdlError(f"cross entropy: logits {tuple(logits.shape)} must be (B,C,H,W)")
     B, Cc, H, W = logits.shape
@@ -2208,7 +2217,7 @@ def cross_entropy(logits, labels, ignore_index=-100, *, weight=None, label_smoot
     weight = None if weight is None else weight.detach().contiguous()
     pixel_weight = None if pixel_weight is None else pixel_weight.detach().contiguous()
     return _SoftmaxCEEx.apply(logits, labels, ignore_index, weight, pixel_weight, float(label_smoothing),
-                              _CE_REDUCTIONS[reduction])
+                              _CE_REDUCTIONS[reduction], keep_zeros)
 
 
 def class_weights_from_labels(labels, C, ignore=None, mode="inverse"):
@@ -2223,6 +2232,129 @@ def class_weights_from_labels(labels, C, ignore=None, mode="inverse"):
         n = n * torch.tensor([float(c != int(ignore)) for c in range(int(C))], dtype=torch.float64).to(n.device, non_blocking=True)
     num = n.sum() / float(C) if mode == "inverse" else torch.quantile(n, 0.5)      # the mean of the two middle counts for an even C
     return torch.where(n > 0, num / n.clamp_min(1.0), torch.zeros_like(n)).to(torch.float32)
+
+
+def _out_tensor(out, key, shape, dtype, device):
+    """``out[key]`` when it is a dense device tensor of that shape and type (the caller's buffer: its address stays), else a new
+    one, stored under ``key`` when ``out`` is a dict."""
+    t = None if out is None else out.get(key)
+    if not (torch.is_tensor(t) and tuple(t.shape) == tuple(shape) and t.dtype == dtype and t.device == device
+            and t.is_contiguous()):
+        t = torch.empty(shape, device=device, dtype=dtype)
+        if out is not None:
+            out[key] = t
+    return t
+
+
+def kth_value(x, k=0, frac=0.0, *, largest=True, valid=None, segments=1, out=None):
+    """The ``K``-th largest (``largest=False``: smallest) value of each of the ``segments`` equal runs of the dense float32
+    device tensor ``x``, with ``K = min(n, k + floor(frac * n))`` computed ON THE DEVICE from ``n``, the number of candidates
+    of the run: its elements that are not NaN and, with ``valid`` (uint8 / bool, the shape of ``x``), are marked there.
+    Returns ``(value, n_valid)``: float32 and int64 device tensors of ``segments`` entries; no host synchronisation.
+
+    ``value`` is an element of ``x`` bit for bit (of -0.0 and +0.0 either may come back); ``K == 0`` (an empty run included)
+    gives +inf for ``largest`` and -inf otherwise, so that ``x >= value`` / ``x <= value`` keeps nothing.  A radix select in
+    four launches (wsdl_kth_value); bitwise reproducible.  ``out``: a dict whose ``"value"`` / ``"n_valid"`` tensors receive
+    the results."""
+    if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+        raise ValueError(f"kth_value: k {k!r} must be an int >= 0")
+    if isinstance(frac, bool) or not isinstance(frac, (int, float)) or not 0.0 <= frac <= 1.0:
+        raise ValueError(f"kth_value: frac {frac!r} must be a number in [0, 1]")
+    if isinstance(segments, bool) or not isinstance(segments, int) or segments < 1:
+        raise ValueError(f"kth_value: segments {segments!r} must be an int >= 1")
+    x = _req(x, "kth_value: x").detach()
+    x = x if x.is_contiguous() else x.contiguous()
+    if x.numel() == 0 or x.numel() % segments:
+        raise WsdlError(f"kth_value: {x.numel()} elements do not split into {segments} non-empty segments")
+    if valid is not None:
+        if not torch.is_tensor(valid) or valid.dtype not in (torch.uint8, torch.bool) or valid.shape != x.shape or valid.device != x.device:
+            raise WsdlError("kth_value: valid must be a uint8 / bool device tensor of the shape of x")
+        valid = valid if valid.is_contiguous() else valid.contiguous()
+    value = _out_tensor(out, "value", (segments,), torch.float32, x.device)
+    n_valid = _out_tensor(out, "n_valid", (segments,), torch.int64, x.device)
+    ws = workspace(lib().wsdl_kth_workspace(segments), x.device)
+    check(lib().wsdl_kth_value(_p(x), _p(valid), x.numel() // segments, segments, int(bool(largest)), int(k), float(frac),
+                               _p(value), _p(n_valid), _p(ws), ws.numel(), _stream()))
+    return value, n_valid
+
+
+_MINING_MODES = {"hard": 0, "trim": 1}
+
+
+def check_mining_options(mode, thresh, min_kept, drop_frac, scope, reduction, label_smoothing=0.0):
+    """ValueError for an option ``cross_entropy_mined`` does not know (no device needed)."""
+    if mode not in _MINING_MODES:
+        raise ValueError(f"cross_entropy_mined: mode {mode!r}: 'hard' or 'trim'")
+    if scope not in ("batch", "image"):
+        raise ValueError(f"cross_entropy_mined: scope {scope!r}: 'batch' or 'image'")
+    if reduction not in ("mean", "sum"):
+        raise ValueError(f"cross_entropy_mined: reduction {reduction!r}: 'mean' or 'sum'")
+    check_cross_entropy_options(reduction, label_smoothing)
+    if thresh is not None and (isinstance(thresh, bool) or not isinstance(thresh, (int, float)) or not 0.0 < thresh <= 1.0):
+        raise ValueError(f"cross_entropy_mined: thresh {thresh!r} must be None or a number in (0, 1]")
+    if isinstance(min_kept, bool) or not isinstance(min_kept, int) or min_kept < 0:
+        raise ValueError(f"cross_entropy_mined: min_kept {min_kept!r} must be an int >= 0")
+    if isinstance(drop_frac, bool) or not isinstance(drop_frac, (int, float)) or not 0.0 <= drop_frac < 1.0:
+        raise ValueError(f"cross_entropy_mined: drop_frac {drop_frac!r} must be a number in [0, 1)")
+
+
+def cross_entropy_mined(logits, labels, ignore_index=-100, *, mode, thresh=None, min_kept=0, drop_frac=0.0, scope="batch",
+                        weight=None, label_smoothing=0.0, pixel_weight=None, reduction="mean", stats=None):
+    """``ops.cross_entropy`` over the pixels their own loss selects - hard-pixel mining or loss trimming - with the selection
+    made on the device: no ``topk`` / ``sort``, no host read of a pixel count, so a launch plan holds the step.
+
+    The ranking statistic is ``nll = -log softmax(logits)[label]`` (no class weights, no smoothing), over the valid pixels:
+    label != ``ignore_index`` and ``pixel_weight`` != 0.  ``scope="batch"`` ranks the whole batch, ``"image"`` each image
+    by itself.  With ``n`` valid pixels in the scope:
+
+    ``mode="hard"`` (OHEM, bootstrapped cross entropy): keep the pixels whose true-class probability is at most ``thresh``,
+    and at least ``min_kept`` per image of them (``scope="batch"``: ``min_kept * B`` in the batch) - that is
+    ``nll >= min(tau, -log(thresh))`` with ``tau`` the ``min(n, K)``-th largest ``nll``; ``thresh=None`` keeps exactly the
+    ``K`` hardest (``K == 0``: none).  ``mode="trim"`` (small-loss selection against label noise): drop the
+    ``floor(drop_frac * n)`` pixels of largest loss - keep ``nll <= tau``, ``tau`` the ``(floor(drop_frac * n) + 1)``-th
+    largest; ``drop_frac=0`` keeps everything.  The rule is INCLUSIVE: pixels that tie with ``tau`` are all kept, so hard
+    mode keeps at least ``K`` and trim mode drops at most ``floor(drop_frac * n)``; mmsegmentation's OHEM sampler is strict
+    at the boundary (``prob < threshold``) and differs from this exactly on the ties.
+
+    The result is ``ops.cross_entropy(logits, labels, ignore_index, weight=, label_smoothing=, reduction=,
+    pixel_weight=m)`` with ``m`` = ``pixel_weight`` (or 1) on the kept pixels and 0 elsewhere: the gradient flows through
+    that call only, the selection is a constant.  'mean' divides by the sum of ``m * weight[label]``; nothing kept gives NaN
+    ('sum': 0) with a gradient of zeros, as torch's cross entropy over ignored pixels only (a pixel that is not selected
+    has gradient 0 whatever the denominator is; the kept pixels' gradients are those of that call bit for bit).  A label outside [0, C) other than ``ignore_index`` keeps its weight and makes the loss NaN, as without mining.
+
+    ``stats``: a caller-owned dict; its device tensors ``"threshold"`` (float32: ``tau`` as selected, before the ``thresh``
+    cap of hard mode), ``"kept"`` and ``"valid"`` (int64), one entry per scope segment, and ``"selection"`` (float32
+    (B,H,W): ``m``) are filled in place where they have the right shape and created otherwise.  Nothing is read on the host."""
+    check_mining_options(mode, thresh, min_kept, drop_frac, scope, reduction, label_smoothing)
+    if logits.dim() != 4:
+        raise WsdlError(f"cross entropy: logits {tuple(logits.shape)} must be (B,C,H,W)")
+    B, Cc, H, W = logits.shape
+    dev = logits.device
+    labels = _req(labels, "labels", torch.int64).contiguous()
+    if pixel_weight is not None:
+        if not torch.is_tensor(pixel_weight) or pixel_weight.dtype != torch.float32 or tuple(pixel_weight.shape) != (B, H, W) \
+                or pixel_weight.device != dev:
+            raise WsdlError(f"cross entropy: pixel_weight must be a float32 {(B, H, W)} tensor on {dev}")
+        pixel_weight = pixel_weight.detach().contiguous()
+    segments = B if scope == "image" else 1
+    n = B * H * W
+    nll = cross_entropy(logits.detach(), labels, ignore_index, reduction="none")
+    valid = torch.empty((B, H, W), device=dev, dtype=torch.uint8)
+    check(lib().wsdl_mining_valid(_p(labels), int(ignore_index), _p(pixel_weight), _p(valid), n, _stream()))
+    if mode == "hard":
+        k, frac = int(min_kept) * (B if scope == "batch" else 1), 0.0
+        cap = float("inf") if thresh is None else float(np.float32(-np.log(np.float64(thresh))))
+    else:
+        k, frac, cap = 1, float(drop_frac), float("inf")
+    tau = _out_tensor(stats, "threshold", (segments,), torch.float32, dev)
+    n_valid = _out_tensor(stats, "valid", (segments,), torch.int64, dev)
+    kth_value(nll, k, frac, largest=True, valid=valid, segments=segments, out={"value": tau, "n_valid": n_valid})
+    m = _out_tensor(stats, "selection", (B, H, W), torch.float32, dev)
+    kept = _out_tensor(stats, "kept", (segments,), torch.int64, dev)
+    ws = workspace(lib().wsdl_mining_weights_workspace(segments), dev)
+    check(lib().wsdl_mining_weights(_p(nll), _p(valid), _p(pixel_weight), _p(tau), cap, _MINING_MODES[mode], n // segments,
+                                    segments, _p(m), _p(kept), _p(ws), ws.numel(), _stream()))
+    return _cross_entropy_ex(logits, labels, ignore_index, weight, label_smoothing, reduction, m, keep_zeros=True)
 
 
 class _LovaszSoftmax(torch.autograd.Function):
