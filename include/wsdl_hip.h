@@ -757,6 +757,34 @@ int wsdl_mining_weights(const float* nll, const uint8_t* valid, const float* pix
  * selected the mean's denominator is 0 and s = inf - the gradient is then 0 everywhere, as torch's over ignored pixels. */
 int wsdl_mining_scale_grad(const float* dl, const float* s, float* out, size_t n, wsdl_stream_t stream);
 
+/* ---- PAMR: pixel-adaptive mask refinement (Araslanov & Roth, CVPR 2020; csrc/pamr.hip) - the reference has no such step -
+ * A parameter-free local propagation of a score map m (B,C,H,W) whose weights come from the local contrast of an image
+ * x (B,K,H,W) on the same H x W.  Neighbourhood: P = 8 n_dil pixels - for each dilation d, in the order given, the offsets
+ * (dy d, dx d), dy, dx in {-1,0,1} in raster order without the centre; borders are replicated, q_j = (clamp(y + oy_j, 0, H-1),
+ * clamp(x + ox_j, 0, W-1)), every coordinate on its own (below a dilation both borders clamp).
+ *   sigma_k(p) = unbiased (n-1) deviation of the 9 n_dil samples x_k(q): 8 neighbours and the centre per dilation (the
+ *                centre counts n_dil times); from the mean, sums in double - a flat neighbourhood gives exactly 0
+ *   a(p,j)     = mean_k -|x_k(p) - x_k(q_j)| / (1e-8 + 0.1 sigma_k(p))
+ *   w(p,.)     = softmax_j a(p,.)                                   (flat neighbourhood: exactly 1/P)
+ *   one iteration: m'_c(p) = sum_j w(p,j) m_c(q_j)
+ * The result does not depend on a per-channel gain or offset of the image (up to the 1e-8).  fp32 planes, dense NCHW.
+ * 1 <= K <= 4, 1 <= C <= 32, 1 <= n_dil <= 8, 1 <= d <= 64, H W <= 2^28.  No atomics, no sum across threads: bitwise
+ * reproducible.  Every launch copies the dilations by value, so a launch plan may hold the calls.
+ * wsdl_pamr_affinity: weights (B,P,H,W), plane j = neighbour j (W-contiguous: the propagation reads them coalesced).
+ * wsdl_pamr_propagate: n_iter iterations (one launch each per 4 score channels) from mask_in to mask_out, ping-pong
+ *   between two buffers carved from ws (wsdl_pamr_workspace bytes, 16-byte aligned; not needed for n_iter < 2); the result
+ *   lands in mask_out for every n_iter, n_iter = 0 copies; mask_in is never written; mask_in and mask_out must not overlap.
+ * wsdl_pamr_workspace: 0 for a geometry outside the limits above (host-side check, no device touched).
+ * wsdl_pamr_labels: labels_out (B,H,W) int64 - C >= 2: the index of the first maximum over the channels, ignore_index
+ *   where that maximum is < min_conf; C == 1: 1 where m >= thresh, else 0 (min_conf is not used). */
+size_t wsdl_pamr_workspace(int B, int C, int H, int W, int n_dil);
+int wsdl_pamr_affinity(const float* image, int B, int K, int H, int W, const int* dilations, int n_dil, float* weights,
+                       wsdl_stream_t stream);
+int wsdl_pamr_propagate(const float* weights, const float* mask_in, float* mask_out, int B, int C, int H, int W,
+                        const int* dilations, int n_dil, int n_iter, void* ws, size_t ws_bytes, wsdl_stream_t stream);
+int wsdl_pamr_labels(const float* mask, int B, int C, int H, int W, float thresh, float min_conf, long long ignore_index,
+                     long long* labels_out, wsdl_stream_t stream);
+
 /* ---- refine_pseudo_mask inner step (TraditionalModel/AlternatingDirectionCutLoss.py:736-757) -
  * KL(softmax(X) || S) with log(X+1e-8), reduction 'batchmean', and its gradient wrt softmax(X). */
 int wsdl_kl_div_fwd_bwd(const float* xn, const float* s, float* loss, float* dxn, size_t n, int batch,

@@ -168,16 +168,26 @@ def train_model(model, optimizer, criterion_ce=None, num_epochs=3, *, train_load
 
 
 def refine_dataset(model, dataset, repeats=5, chunk=64, threshold=0.3, lr=1e-4, num_steps=10, lambda_boundary=0.1,
-                   sigma_color=0.1, window_size=5):
+                   sigma_color=0.1, window_size=5, method="ncut", pamr_kwargs=None):
     """Step 2 of an alternation (AlternatingDirectionCutLoss.py:803-810): ``repeats`` passes over the data set, each
     refining every pseudo mask and overwriting it - pass r+1 starts from pass r's thresholded masks, because the
     reference's dataset re-reads the PNG it has just overwritten.  In memory: ``dataset.set_masks``.  The network is
-    frozen during the passes, so its soft prediction is computed once per chunk, not once per pass and image."""
+    frozen during the passes, so its soft prediction is computed once per chunk, not once per pass and image.
+
+    ``method="pamr"`` (the reference has no such step; the default ``"ncut"`` is the reference's): each chunk's masks become
+    ``ops.pamr(imgs, network_soft_prediction(model, imgs), **pamr_kwargs)[:, 1] > threshold``.  The network is frozen and
+    the result does not depend on the old masks, so one pass is all there is: ``repeats`` is ignored, as are ``lr``,
+    ``num_steps``, ``lambda_boundary``, ``sigma_color`` and ``window_size``."""
+    if method not in ("ncut", "pamr"):
+        raise ValueError(f"refine_dataset: method {method!r}: 'ncut' or 'pamr'")
     n = len(dataset)
     for s in range(0, n, chunk):
         idx = torch.arange(s, min(s + chunk, n), device=dataset.images.device)
         imgs = dataset.images[idx]
         S = network_soft_prediction(model, imgs)
+        if method == "pamr":
+            dataset.set_masks(idx, (ops.pamr(imgs, S, **(pamr_kwargs or {}))[:, 1] > threshold).float())
+            continue
         cache = ops.pairwise_cache(imgs, window_size, sigma_color)
         for _ in range(repeats):
             refined = refine_pseudo_masks_batched(model, imgs, dataset.masks[idx], lambda_boundary=lambda_boundary,
@@ -202,7 +212,8 @@ def run_alternating_training(model, optimizer, dataset, num_alternations=10, epo
     initialised, a ``dp.GradBucketReducer`` on the optimizer) every rank must run the same number of optimiser steps:
     the per-epoch step count is the minimum over the ranks; refinement is per-image independent and needs no
     collective.  ``augment``: an ``augment.Augment`` handed to ``dataset.batches`` - the training batches
-    only; refinement reads the stored images and masks (the reference has no augmentation)."""
+    only; refinement reads the stored images and masks (the reference has no augmentation).  ``refine_kwargs`` goes to
+    ``refine_dataset``: ``{"method": "pamr"}`` refines with ``ops.pamr`` instead of the normalised-cut descent."""
     import torch.distributed as dist
     rk = dict(threshold=0.3, lr=1e-4, num_steps=10, lambda_boundary=0.1)
     rk.update(refine_kwargs or {})

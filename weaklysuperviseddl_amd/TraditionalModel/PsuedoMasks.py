@@ -14,6 +14,7 @@ Mirrors reference TraditionalModel/PsuedoMasks.py: ``keep_largest`` (:15-21) and
     (SURVEY.md 8e); image ids stay the global ones, so the union over the ranks is the single-process result;
   * ``streams``: that many of the loader's batches are in flight on the device at once (``LayerCAMGenerator.generate_batches``);
     the masks are the same bit for bit;
+  * ``pamr``: optional pixel-adaptive refinement of the CAM before its threshold (``ops.pamr``; off by default);
   * ``keep_largest(mask)`` is the reference's host function (skimage there; scipy.ndimage here - 8-connectivity, raster
     label order, first label wins area ties, empty mask returned unchanged).  ``generate_pseudo_masks`` itself labels
     the whole batch on the device (``keep_largest_batched`` -> ``ops.keep_largest_batched``, one workgroup per mask, the
@@ -60,7 +61,11 @@ def _to_png_u8(t):
 def generate_pseudo_masks(loader, layercam_gen, cam_thresh=0.3, alpha=1.0, keep_largest_masks=True,
                           run_id="default", out_root="/content", max_images=500, write_png=True,
                           device="cuda", rank=0, world=1, keep_images=False, streams=3, keep_on_device=False,
-                          device_batch=0):
+                          device_batch=0, pamr=None):
+    """``pamr``: None (the default: the masks are the thresholded CAMs, bit for bit as without the argument) or a dict of
+    keyword arguments of ``ops.pamr`` (``{}``: its defaults) - the CAM WITHOUT its threshold is refined against the batch's
+    images as a one-channel score map (pixel-adaptive mask refinement; the reference has no such step), the refined map is
+    thresholded (``>= cam_thresh``) and ``keep_largest`` applies as before.  The images must have the CAM's size."""
     mask_dir = os.path.join(out_root, f"pseudo_masks_{run_id}")
     image_dir = os.path.join(out_root, f"images_{run_id}")
     if write_png:
@@ -92,7 +97,9 @@ def generate_pseudo_masks(loader, layercam_gen, cam_thresh=0.3, alpha=1.0, keep_
             outs = layercam_gen.generate_batches([g[1] for g in group], alpha, [g[2] for g in group], cam_thresh, streams)
         else:
             outs = [layercam_gen.generate_batch(g[1], alpha=alpha, class_idx=g[2], thresh=cam_thresh) for g in group]
-        for (imgs, _d, _l, first_id, take), (_cam, m) in zip(group, outs):
+        for (imgs, imgs_d, _l, first_id, take), (cam, m) in zip(group, outs):
+            if pamr is not None:
+                m = ops.pamr_labels(ops.pamr(imgs_d, cam[:, None], **pamr), thresh=cam_thresh).to(torch.uint8)
             if keep_largest_masks:
                 m = keep_largest_batched(m)
             m_host = m if keep_on_device and not write_png else m.cpu().numpy()

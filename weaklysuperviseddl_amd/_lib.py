@@ -118,6 +118,10 @@ SIGNATURES = {
     "wsdl_mining_weights_workspace": (_sz, [_i]),
     "wsdl_mining_weights": (_i, [_vp, _vp, _vp, _vp, _f, _i, _ll, _i, _vp, _vp, _vp, _sz, _vp]),
     "wsdl_mining_scale_grad": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "wsdl_pamr_workspace": (_sz, [_i] * 5),
+    "wsdl_pamr_affinity": (_i, [_vp, _i, _i, _i, _i, C.POINTER(_i), _i, _vp, _vp]),
+    "wsdl_pamr_propagate": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_i), _i, _i, _vp, _sz, _vp]),
+    "wsdl_pamr_labels": (_i, [_vp, _i, _i, _i, _i, _f, _f, _ll, _vp, _vp]),
     "wsdl_kl_div_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, _sz, _vp]),
     "wsdl_kl_div_per_image_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _sz, _vp, _sz, _vp]),
     "wsdl_refine_combine": (_i, [_vp, _vp, _vp, _vp, _f, _f, _vp, _i, _sz, _vp]),

@@ -360,3 +360,28 @@ class MinedCrossEntropyLoss(nn.Module):
         return (f"mode={self.mode!r}, thresh={self.thresh}, min_kept={self.min_kept}, drop_frac={self.drop_frac}, "
                 f"scope={self.scope!r}, ignore_index={self.ignore_index}, reduction={self.reduction!r}, "
                 f"label_smoothing={self.label_smoothing}, weight={self.weight is not None}")
+
+
+class PAMR(nn.Module):
+    """Pixel-adaptive mask refinement (Araslanov & Roth, CVPR 2020) as a module without parameters: ``forward(images,
+    scores)`` is ``ops.pamr(images, scores, num_iter, dilations)`` - scores (B,C,H,W) propagated ``num_iter`` times over
+    the dilated 3 x 3 rings of every pixel with weights from the local contrast of images (B,K,H,W).  Not differentiable:
+    the result has no ``grad_fn`` (the refiner of single-stage weakly-supervised segmentation sits behind a stop-gradient).
+
+        refine = wnn.PAMR(num_iter=10)
+        masks = ops.pamr_labels(refine(images, probs.detach()), min_conf=0.6)       # int64, 255 where unsure
+        loss = train_step(model, optimizer, images, masks, criterion=wnn.CrossEntropyLoss(ignore_index=255))
+    """
+
+    def __init__(self, num_iter=10, dilations=ops.PAMR_DILATIONS):
+        super().__init__()
+        if isinstance(num_iter, bool) or not isinstance(num_iter, int) or num_iter < 0:
+            raise ValueError(f"PAMR: num_iter {num_iter!r} must be an int >= 0")
+        self.dilations, _ = ops._pamr_dilations(dilations)
+        self.num_iter = num_iter
+
+    def forward(self, images, scores):
+        return ops.pamr(images, scores, self.num_iter, self.dilations)
+
+    def extra_repr(self):
+        return f"num_iter={self.num_iter}, dilations={self.dilations}"

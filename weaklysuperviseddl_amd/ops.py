@@ -2629,6 +2629,110 @@ def dense_crf_filter(images, values, bilateral, sxy, srgb=1.0, n_labels=2):
     return out
 
 
+PAMR_DILATIONS = (1, 2, 4, 8, 12, 24)
+
+
+def _pamr_dilations(dilations):
+    """The dilations as a ctypes int array; ValueError for what is not 1 to 8 ints in [1, 64]."""
+    try:
+        dil = tuple(dilations)
+    except TypeError:
+        raise ValueError(f"pamr: dilations {dilations!r} must be a sequence of ints") from None
+    if not 1 <= len(dil) <= 8 or any(isinstance(d, bool) or not isinstance(d, int) or not 1 <= d <= 64 for d in dil):
+        raise ValueError(f"pamr: dilations {dil!r} must be 1 to 8 ints in [1, 64]")
+    return dil, (C.c_int * len(dil))(*dil)
+
+
+def pamr_workspace(B, K, C_, H, W, dilations=PAMR_DILATIONS):
+    """Bytes of scratch ``pamr`` needs for images (B,K,H,W) and scores (B,C,H,W); 0 for a geometry outside the limits of
+    include/wsdl_hip.h "PAMR" (K in [1,4], C in [1,32], 1 to 8 dilations in [1,64], non-empty planes).  Host-side: no device."""
+    try:
+        dil, _ = _pamr_dilations(dilations)
+    except ValueError:
+        return 0
+    if not 1 <= int(K) <= 4:
+        return 0
+    return int(lib().wsdl_pamr_workspace(int(B), int(C_), int(H), int(W), len(dil)))
+
+
+def _pamr_images(images):
+    if not torch.is_tensor(images) or images.dim() != 4:
+        raise WsdlError("pamr: images must be a (B,K,H,W) tensor")
+    images = _dense(images.detach(), "pamr: images")
+    if not 1 <= images.shape[1] <= 4 or images.numel() == 0:
+        raise WsdlError(f"pamr: images {tuple(images.shape)} must be (B,K,H,W) with 1 <= K <= 4 and no empty dimension")
+    return images
+
+
+def pamr_affinity(images, dilations=PAMR_DILATIONS):
+    """The propagation weights of ``pamr`` for float32 device images (B,K,H,W), 1 <= K <= 4: (B, 8 D, H, W) float32, plane
+    8 i + j = neighbour j (raster order of the 3 x 3 ring without its centre) of dilation ``dilations[i]``, borders
+    replicated; every pixel's weights are a softmax over its 8 D neighbours (include/wsdl_hip.h "PAMR").  They depend on
+    the image only: a caller that refines several score maps against one batch computes them once (``pamr(affinity=)``)."""
+    dil, arr = _pamr_dilations(dilations)
+    images = _pamr_images(images)
+    B, K, H, W = images.shape
+    w = torch.empty(B, 8 * len(dil), H, W, device=images.device, dtype=torch.float32)
+    check(lib().wsdl_pamr_affinity(_p(images), B, K, H, W, arr, len(dil), _p(w), _stream()))
+    return w
+
+
+def pamr(images, scores, num_iter=10, dilations=PAMR_DILATIONS, *, affinity=None, out=None):
+    """Pixel-adaptive mask refinement (Araslanov & Roth, CVPR 2020): ``num_iter`` times ``m'_c(p) = sum_j w(p,j) m_c(q_j)``
+    over the 8 D dilated neighbours of every pixel, ``w = pamr_affinity(images, dilations)``.  images (B,K,H,W), scores
+    (B,C,H,W) with 1 <= C <= 32 on the same H x W, both float32 on the device -> refined scores (B,C,H,W).  Any score map:
+    softmax probabilities, a raw CAM (C = 1), more than two classes.  Every output is a convex combination of inputs, so
+    it stays inside their range; a constant map is a fixed point; ``num_iter=0`` copies.
+
+    Not differentiable: the inputs are detached and the result has no ``grad_fn``.  One launch for the weights and one per
+    iteration (per four score channels), no host read, bitwise reproducible - a launch plan can hold the call.
+    ``affinity``: the weights when the caller already has them; ``out``: a dense float32 (B,C,H,W) device tensor that
+    receives the result (it must not overlap ``scores``)."""
+    if isinstance(num_iter, bool) or not isinstance(num_iter, int) or num_iter < 0:
+        raise ValueError(f"pamr: num_iter {num_iter!r} must be an int >= 0")
+    dil, arr = _pamr_dilations(dilations)
+    images = _pamr_images(images)
+    if not torch.is_tensor(scores) or scores.dim() != 4:
+        raise WsdlError("pamr: scores must be a (B,C,H,W) tensor")
+    scores = _dense(scores.detach(), "pamr: scores")
+    B, K, H, W = images.shape
+    Cc = scores.shape[1]
+    if scores.device != images.device or scores.shape[0] != B or tuple(scores.shape[2:]) != (H, W):
+        raise WsdlError(f"pamr: scores {tuple(scores.shape)} on {scores.device} do not match images {tuple(images.shape)} on "
+                        f"{images.device}: same device, batch, height and width")
+    nbytes = lib().wsdl_pamr_workspace(B, Cc, H, W, len(dil))
+    if nbytes == 0:
+        raise WsdlError(f"pamr: bad geometry, scores {tuple(scores.shape)} (1 <= C <= 32)")
+    if affinity is None:
+        affinity = pamr_affinity(images, dil)
+    else:
+        _req(affinity, "pamr: affinity")
+        if tuple(affinity.shape) != (B, 8 * len(dil), H, W) or affinity.device != images.device or not affinity.is_contiguous():
+            raise WsdlError(f"pamr: affinity must be a dense {(B, 8 * len(dil), H, W)} tensor on {images.device}")
+        affinity = affinity.detach()
+    if out is None:
+        out = torch.empty_like(scores)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.shape == scores.shape
+              and out.device == scores.device and out.is_contiguous() and not out.requires_grad):
+        raise WsdlError(f"pamr: out must be a dense float32 {tuple(scores.shape)} tensor on {scores.device} that needs no gradient")
+    ws = workspace(nbytes, images.device)
+    check(lib().wsdl_pamr_propagate(_p(affinity), _p(scores), _p(out), B, Cc, H, W, arr, len(dil), int(num_iter), _p(ws),
+                                    ws.numel(), _stream()))
+    return out
+
+
+def pamr_labels(scores, thresh=0.5, min_conf=0.0, ignore_index=255):
+    """Refined scores (B,C,H,W) -> int64 labels (B,H,W), what ``train_step`` takes as masks.  C >= 2: the first maximum's
+    index, ``ignore_index`` where that maximum is below ``min_conf``; C == 1: ``scores >= thresh``.  On the device."""
+    if not torch.is_tensor(scores) or scores.dim() != 4:
+        raise WsdlError("pamr_labels: scores must be a (B,C,H,W) tensor")
+    scores = _dense(scores.detach(), "pamr_labels: scores")
+    B, Cc, H, W = scores.shape
+    labels = torch.empty(B, H, W, device=scores.device, dtype=torch.int64)
+    check(lib().wsdl_pamr_labels(_p(scores), B, Cc, H, W, float(thresh), float(min_conf), int(ignore_index), _p(labels), _stream()))
+    return labels
+
+
 def pairwise_affinity_loss(preds, image, window=5, sigma_color=0.1, sigma_space=0.0, apply_softmax=True,
                            normalise=0, cache=None):
     """``cache``: ``pairwise_cache(image, window, sigma_color)`` when the image stays fixed over many evaluations."""
