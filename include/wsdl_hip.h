@@ -785,6 +785,37 @@ int wsdl_pamr_propagate(const float* weights, const float* mask_in, float* mask_
 int wsdl_pamr_labels(const float* mask, int B, int C, int H, int W, float thresh, float min_conf, long long ignore_index,
                      long long* labels_out, wsdl_stream_t stream);
 
+/* ---- distance transforms, Boundary IoU counts, boundary confidence (csrc/edt.hip) - the reference has no such step -
+ * wsdl_edt: the exact squared distance transform of labels (B,H,W) int64.  A pixel p is IN if labels[p] == value and OUT
+ * otherwise (void / ignore labels included).  Two int32 planes (B,H,W):
+ *   d2_out[p] = min over the OUT pixels q of dist2(p,q)     (0 where p is OUT)
+ *   d2_in[p]  = min over the IN pixels q of dist2(p,q)      (0 where p is IN)
+ * Either pointer may be null: that plane is not computed (both null: nothing is launched).
+ *   metric 0  Euclidean: dist2 = dy^2 + dx^2
+ *   metric 1  Chebyshev: dist2 = max(|dy|,|dx|)^2 - what iterated 3 x 3 erosion measures (Boundary IoU, Cheng et al., CVPR 2021)
+ *   border 0  only pixels of the image count
+ *   border 1  everything outside the image is an OUT pixel for d2_out (a pixel in column x is at distance x + 1 from the
+ *             outside); d2_in is the same for both values
+ * Where no site exists - an all-IN image with border 0, d2_in of an image without an IN pixel - the value is the sentinel
+ * WSDL_EDT_FAR.  1 <= H, W <= 8192 and B H W < 2^31: every true squared distance is then below 2^28 and cannot collide with
+ * the sentinel, and no intermediate square leaves int32.  Other values are refused (WSDL_EINVAL) before any launch.
+ * Integer arithmetic only, no atomics: exact, bitwise reproducible, independent of the schedule.  Two launches (columns,
+ * rows); the planes themselves hold the intermediate; every parameter travels by value, so a launch plan may hold the call.
+ * wsdl_band_counts: per image b over its HW pixels, with band X = (0 < d2_X <= limit2): counts[b*2+0] = #(band A and band B),
+ *   counts[b*2+1] = #(band A or band B); int64 (B,2) on the device, overwritten (a memset and one launch).  With A, B the
+ *   d2_out planes of a prediction and a ground truth (metric 1, border 1, limit2 = width^2) these are the intersection and
+ *   union of Boundary IoU.  0 <= limit2 < WSDL_EDT_FAR, so the sentinel is in no band.  Block-local integer counts, one
+ *   atomic per counter and block: exact whatever the schedule.
+ * wsdl_boundary_confidence: w[p] = floor + (1 - floor) (1 - exp(-d2 / (2 sigma^2))) with d2 = d2_out[p] + d2_in[p] (one of
+ *   the two is 0), fp32, n pixels; w = 1 where either plane holds the sentinel (an image without a boundary).
+ *   0 <= floor <= 1, sigma > 0 and finite, 1 <= n < 2^31. */
+#define WSDL_EDT_FAR (1 << 30)
+int wsdl_edt(const int64_t* labels, long long value, int B, int H, int W, int metric, int border, int* d2_out, int* d2_in,
+             wsdl_stream_t stream);
+int wsdl_band_counts(const int* d2_a, const int* d2_b, int limit2, int B, int HW, long long* counts, wsdl_stream_t stream);
+int wsdl_boundary_confidence(const int* d2_out, const int* d2_in, float sigma, float floor, float* w_out, size_t n,
+                             wsdl_stream_t stream);
+
 /* ---- refine_pseudo_mask inner step (TraditionalModel/AlternatingDirectionCutLoss.py:736-757) -
  * KL(softmax(X) || S) with log(X+1e-8), reduction 'batchmean', and its gradient wrt softmax(X). */
 int wsdl_kl_div_fwd_bwd(const float* xn, const float* s, float* loss, float* dxn, size_t n, int batch,

@@ -122,6 +122,9 @@ SIGNATURES = {
     "wsdl_pamr_affinity": (_i, [_vp, _i, _i, _i, _i, C.POINTER(_i), _i, _vp, _vp]),
     "wsdl_pamr_propagate": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_i), _i, _i, _vp, _sz, _vp]),
     "wsdl_pamr_labels": (_i, [_vp, _i, _i, _i, _i, _f, _f, _ll, _vp, _vp]),
+    "wsdl_edt": (_i, [_vp, _ll, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "wsdl_band_counts": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "wsdl_boundary_confidence": (_i, [_vp, _vp, _f, _f, _vp, _sz, _vp]),
     "wsdl_kl_div_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, _sz, _vp]),
     "wsdl_kl_div_per_image_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _sz, _vp, _sz, _vp]),
     "wsdl_refine_combine": (_i, [_vp, _vp, _vp, _vp, _f, _f, _vp, _i, _sz, _vp]),

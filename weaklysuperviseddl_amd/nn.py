@@ -362,6 +362,71 @@ class MinedCrossEntropyLoss(nn.Module):
                 f"label_smoothing={self.label_smoothing}, weight={self.weight is not None}")
 
 
+class BoundaryAwareCrossEntropyLoss(nn.Module):
+    """Cross entropy that trusts a label map less near its own boundary - where the label noise of a CAM-derived pseudo
+    mask sits: every call computes ``ops.boundary_confidence(labels, sigma, floor, value)`` - ``floor + (1 - floor) (1 -
+    exp(-d^2 / (2 sigma^2)))`` with ``d`` the Euclidean distance of a pixel to the contour of ``labels == value``, 1 in an
+    image without a contour - into its own ``pixel_weight`` buffer and hands it to the fused cross entropy
+    (``ops.cross_entropy(..., pixel_weight=)``).  ``floor=1`` is the plain cross entropy with a weight of ones.
+    ``weight`` / ``ignore_index`` / ``reduction`` / ``label_smoothing`` as in ``CrossEntropyLoss``; 'mean' divides by the
+    sum of the weights, so the loss keeps its scale.
+
+    Conventions of ``CrossEntropyLoss``: ``pixel_weight`` (float32) and the two distance planes ``d2_out`` / ``d2_in``
+    (int32; ``ops.edt``) are buffers of this object, filled by every call and allocated anew only when the shape changes,
+    so the addresses a launch plan freezes stay put; every option and every address is a plain attribute, so
+    ``plan.host_scalars`` puts them into the plan key and a changed ``sigma`` records a new plan.  Everything is a launch
+    of the library without a host read: ``train_step`` replays one launch plan.
+
+        crit = wnn.BoundaryAwareCrossEntropyLoss(sigma=3.0, floor=0.2)
+        loss = train_step(model, optimizer, images, pseudo_masks, criterion=crit)
+    """
+
+    def __init__(self, sigma=3.0, floor=0.0, value=1, weight=None, ignore_index=-100, reduction="mean", label_smoothing=0.0):
+        super().__init__()
+        ops.check_cross_entropy_options(reduction, label_smoothing)
+        ops.check_boundary_confidence_options(sigma, floor)
+        if weight is not None and (not torch.is_tensor(weight) or weight.dim() != 1):
+            raise ValueError("BoundaryAwareCrossEntropyLoss: weight must be a (C,) tensor")
+        self.register_buffer("weight", None if weight is None else weight.detach().to(torch.float32).clone())
+        for name in ("pixel_weight", "d2_out", "d2_in"):
+            self.register_buffer(name, None, persistent=False)
+        self.sigma = float(sigma)
+        self.floor = float(floor)
+        self.value = int(value)
+        self.ignore_index = int(ignore_index)
+        self.reduction = reduction
+        self.label_smoothing = float(label_smoothing)
+        self._refresh_pointers()
+
+    def _refresh_pointers(self):
+        for name in ("weight", "pixel_weight", "d2_out", "d2_in"):
+            t = getattr(self, name)
+            setattr(self, name + "_ptr", 0 if t is None else t.data_ptr())
+        self.pixel_weight_shape = "" if self.pixel_weight is None else "x".join(str(d) for d in self.pixel_weight.shape)
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self._refresh_pointers()
+        return out
+
+    def forward(self, logits, labels):
+        # (options may have been assigned since the constructor checked them)
+        ops.check_cross_entropy_options(self.reduction, self.label_smoothing)
+        labels = labels.long()
+        bufs = {"weight": self.pixel_weight, "out": self.d2_out, "in": self.d2_in}
+        ops.boundary_confidence(labels, self.sigma, self.floor, self.value, out=bufs)
+        for k, name in (("weight", "pixel_weight"), ("out", "d2_out"), ("in", "d2_in")):
+            if getattr(self, name) is not bufs[k]:
+                setattr(self, name, bufs[k])
+        self._refresh_pointers()
+        return ops.cross_entropy(logits, labels, self.ignore_index, weight=self.weight, label_smoothing=self.label_smoothing,
+                                 reduction=self.reduction, pixel_weight=self.pixel_weight)
+
+    def extra_repr(self):
+        return (f"sigma={self.sigma}, floor={self.floor}, value={self.value}, ignore_index={self.ignore_index}, "
+                f"reduction={self.reduction!r}, label_smoothing={self.label_smoothing}, weight={self.weight is not None}")
+
+
 class PAMR(nn.Module):
     """Pixel-adaptive mask refinement (Araslanov & Roth, CVPR 2020) as a module without parameters: ``forward(images,
     scores)`` is ``ops.pamr(images, scores, num_iter, dilations)`` - scores (B,C,H,W) propagated ``num_iter`` times over

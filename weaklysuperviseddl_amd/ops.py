@@ -2733,6 +2733,140 @@ def pamr_labels(scores, thresh=0.5, min_conf=0.0, ignore_index=255):
     return labels
 
 
+EDT_FAR = 1 << 30                       # WSDL_EDT_FAR: "no site" in a distance plane
+_EDT_METRICS = {"euclid": 0, "chebyshev": 1}
+
+
+def _edt_labels(labels, name):
+    """(B,H,W) int64 device labels; a bool / uint8 mask is converted."""
+    if not torch.is_tensor(labels) or labels.dim() != 3:
+        raise WsdlError(f"{name}: labels must be a (B,H,W) tensor")
+    if labels.dtype in (torch.bool, torch.uint8):
+        if not labels.is_cuda:
+            raise WsdlError(f"{name}: the HIP path needs a device tensor (got {labels.device}); there is no CPU fallback")
+        labels = labels.to(torch.int64)
+    labels = _req(labels, name + ": labels", torch.int64).detach()
+    return labels if labels.is_contiguous() else labels.contiguous()
+
+
+def _int_option(v, name, lo=None):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or (lo is not None and v < lo):
+        raise ValueError(f"{name} {v!r} must be an int" + ("" if lo is None else f" >= {lo}"))
+    return int(v)
+
+
+def edt(labels, value=1, *, metric="euclid", border=False, want=("out", "in"), out=None):
+    """Exact squared distance transform of int64 device labels (B,H,W) (a bool / uint8 mask is converted): a pixel is IN
+    where ``labels == value`` and OUT elsewhere, void labels included.  Returns ``(d2_out, d2_in)``, int32 (B,H,W):
+    ``d2_out`` the squared distance to the nearest OUT pixel (0 on OUT pixels), ``d2_in`` to the nearest IN pixel (0 on IN
+    pixels); a plane ``want`` does not name is ``None`` and is not computed.  ``metric``: 'euclid' (dy^2 + dx^2) or
+    'chebyshev' (max(|dy|,|dx|)^2, the distance iterated 3 x 3 erosion measures).  ``border=True``: everything outside the
+    image is OUT for ``d2_out``.  ``EDT_FAR`` (2^30) where no site exists.  1 <= H, W <= 8192 (wsdl_edt).
+
+    Two launches, integer arithmetic, no host read, bitwise reproducible: a launch plan can hold the call.  ``out``: a dict
+    whose ``"out"`` / ``"in"`` tensors receive the planes (created there when missing or of another shape)."""
+    if metric not in _EDT_METRICS:
+        raise ValueError(f"edt: metric {metric!r}: 'euclid' or 'chebyshev'")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ("out", "in") for w in want):
+        raise ValueError(f"edt: want {want!r}: 'out', 'in' or both")
+    value = _int_option(value, "edt: value")
+    labels = _edt_labels(labels, "edt")
+    B, H, W = labels.shape
+    planes = [_out_tensor(out, k, (B, H, W), torch.int32, labels.device) if k in want else None for k in ("out", "in")]
+    check(lib().wsdl_edt(_p(labels), value, B, H, W, _EDT_METRICS[metric], int(bool(border)), _p(planes[0]), _p(planes[1]),
+                         _stream()))
+    return tuple(planes)
+
+
+def _band_limit(width):
+    return min(_int_option(width, "boundary band: width", 0) ** 2, 1 << 28)      # every true squared distance is below 2^28
+
+
+def boundary_band(labels, width, value=1, *, metric="chebyshev", border=True):
+    """bool (B,H,W): the IN pixels (``labels == value``) within ``width`` of the contour, ``0 < d2_out <= width^2`` of
+    ``edt``.  With the defaults this is the mask minus its ``width``-times 3 x 3-eroded self, the image padded with
+    background: the boundary region of Boundary IoU."""
+    limit2 = _band_limit(width)
+    d, _ = edt(labels, value, metric=metric, border=border, want=("out",))
+    return (d > 0) & (d <= limit2)
+
+
+def boundary_iou_counts(preds, labels, width, value=1, *, metric="chebyshev", border=True, out=None):
+    """int64 (B,2) on the device: per image [:, 0] = #(pixels in the boundary bands of both ``preds`` and ``labels``),
+    [:, 1] = #(pixels in either) - the bands of ``boundary_band`` (wsdl_band_counts).  No host synchronisation;
+    ``boundary_iou_from_counts`` turns a host copy into the metric.  ``out``: a dense int64 (B,2) device tensor to fill."""
+    limit2 = _band_limit(width)
+    preds, labels = _edt_labels(preds, "boundary_iou_counts"), _edt_labels(labels, "boundary_iou_counts")
+    if preds.shape != labels.shape or preds.device != labels.device:
+        raise WsdlError(f"boundary_iou_counts: preds {tuple(preds.shape)} on {preds.device} / labels {tuple(labels.shape)} on "
+                        f"{labels.device} must match")
+    B, H, W = labels.shape
+    da, _ = edt(preds, value, metric=metric, border=border, want=("out",))
+    db, _ = edt(labels, value, metric=metric, border=border, want=("out",))
+    if out is None:
+        out = torch.empty((B, 2), device=labels.device, dtype=torch.int64)
+    elif not (torch.is_tensor(out) and out.dtype == torch.int64 and tuple(out.shape) == (B, 2) and out.device == labels.device
+              and out.is_contiguous()):
+        raise WsdlError(f"boundary_iou_counts: out must be a dense int64 {(B, 2)} tensor on {labels.device}")
+    check(lib().wsdl_band_counts(_p(da), _p(db), limit2, B, H * W, _p(out), _stream()))
+    return out
+
+
+def boundary_iou_from_counts(counts, EMPTY=1.0):
+    """Host arithmetic on (images, 2) counts (anything ``np.asarray`` takes): intersection / union per image as Python
+    floats, ``EMPTY`` where the union is 0 (neither mask has a boundary pixel), and the mean over the images as a float in
+    [0, 1] (summed in order, as ``iou_from_counts`` does)."""
+    rows = np.asarray(counts).reshape(-1, 2).tolist()
+    if not rows:
+        raise ValueError("boundary_iou_from_counts: no image")
+    per = [float(i) / float(u) if u else EMPTY for i, u in rows]
+    acc = per[0]
+    for v in per[1:]:
+        acc += v
+    return acc if len(per) == 1 else acc / len(per)
+
+
+def boundary_width(H, W, ratio=0.02):
+    """The band width of the published Boundary IoU: ``max(1, round(ratio * sqrt(H^2 + W^2)))`` pixels."""
+    return max(1, int(round(ratio * float(np.sqrt(float(H) ** 2 + float(W) ** 2)))))
+
+
+def boundary_iou(preds, labels, ratio=0.02, width=None, value=1):
+    """Boundary IoU (Cheng et al., CVPR 2021) of int64 (or bool / uint8) device maps (B,H,W), the mean over the images as a
+    Python float: per image |Gd and Pd| / |Gd or Pd| with Gd, Pd the pixels of each mask within ``width`` of its contour
+    (Chebyshev distance, the image padded with background - the published erosion).  ``width``: pixels, default
+    ``boundary_width(H, W, ratio)``.  One host read (the counts)."""
+    if width is None:
+        if not torch.is_tensor(labels) or labels.dim() != 3:
+            raise WsdlError("boundary_iou: labels must be a (B,H,W) tensor")
+        width = boundary_width(labels.shape[1], labels.shape[2], ratio)
+    return boundary_iou_from_counts(boundary_iou_counts(preds, labels, width, value).cpu().numpy())
+
+
+def check_boundary_confidence_options(sigma, floor):
+    """ValueError for a ``sigma`` that is not a finite number > 0 or a ``floor`` outside [0, 1] (no device needed)."""
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)) or not 0.0 < sigma < float("inf"):
+        raise ValueError(f"boundary_confidence: sigma {sigma!r} must be a finite number > 0")
+    if isinstance(floor, bool) or not isinstance(floor, (int, float)) or not 0.0 <= floor <= 1.0:
+        raise ValueError(f"boundary_confidence: floor {floor!r} must be a number in [0, 1]")
+
+
+def boundary_confidence(labels, sigma=3.0, floor=0.0, value=1, *, out=None):
+    """float32 (B,H,W) confidence of a label map in its own labels, low at the contour of ``labels == value`` and 1 far from
+    it: ``w = floor + (1 - floor) (1 - exp(-d^2 / (2 sigma^2)))`` with ``d`` the Euclidean distance of a pixel to the nearest
+    pixel of the other side (``edt`` with ``border=False``: the image edge is no contour); an image without a contour gets
+    1 everywhere.  What ``CrossEntropyLoss.set_pixel_weight`` takes: "trust a pseudo label less near its own boundary".
+    Three launches, no host read.  ``out``: a dict whose ``"weight"`` (float32) and ``"out"`` / ``"in"`` (int32) tensors
+    receive the map and the two distance planes (created there when missing or of another shape)."""
+    check_boundary_confidence_options(sigma, floor)
+    labels = _edt_labels(labels, "boundary_confidence")
+    d_out, d_in = edt(labels, value, out=out if out is not None else {})
+    w = _out_tensor(out, "weight", tuple(labels.shape), torch.float32, labels.device)
+    check(lib().wsdl_boundary_confidence(_p(d_out), _p(d_in), float(sigma), float(floor), _p(w), w.numel(), _stream()))
+    return w
+
+
 def pairwise_affinity_loss(preds, image, window=5, sigma_color=0.1, sigma_space=0.0, apply_softmax=True,
                            normalise=0, cache=None):
     """``cache``: ``pairwise_cache(image, window, sigma_color)`` when the image stays fixed over many evaluations."""
