@@ -816,6 +816,50 @@ int wsdl_band_counts(const int* d2_a, const int* d2_b, int limit2, int B, int HW
 int wsdl_boundary_confidence(const int* d2_out, const int* d2_in, float sigma, float floor, float* w_out, size_t n,
                              wsdl_stream_t stream);
 
+/* ---- signed-distance boundary loss, surface distances (csrc/boundary_loss.hip) - the reference has no counterpart: its
+ * losses act on regions and pixels (cross entropy, Lovasz, the NCut and boundary-constraint terms) and its evaluation
+ * reports region IoU and pixel accuracy.  Kervadec et al., "Boundary loss for highly unbalanced segmentation", MIDL 2019.
+ * wsdl_signed_distance: no counterpart in the reference; the paper's one_hot2dist.  From the two Euclidean planes of wsdl_edt
+ *   (border 0) of one class, per pixel: phi = +sqrt(d2_in) on OUT pixels (d2_out == 0), phi = -(sqrt(d2_out) - 1) on IN
+ *   pixels - the published distance(negmask) * negmask - (distance(posmask) - 1) * posmask - and phi = 0 where either plane
+ *   holds WSDL_EDT_FAR (the class is absent from the image or fills it: the whole image is 0).  The root is taken in double
+ *   and rounded once.  phi[b * phi_batch_stride + p], p < HW; a stride of 0 means HW, K HW writes one plane of a (B,K,H,W) map.
+ * wsdl_boundary_loss_fwd_bwd: no counterpart in the reference; the paper's SurfaceLoss, mean(softmax(logits)_c * phi_c), fused
+ *   with its gradient.  logits (B,C,H,W) fp32, phi (B,K,H,W) fp32, class_list K distinct ints in [0, C) on the HOST (copied
+ *   into the launch by value; 1 <= K <= 32): plane k of phi belongs to class class_list[k].  labels (B,H,W) int64 or null:
+ *   a pixel is valid when labels[p] != ignore_index, every pixel without labels; N = #valid pixels.  With s = softmax over C
+ *   and Phi_c = phi plane of class c, 0 for a class outside the list:
+ *     loss = scale / (K N) * sum over valid p and c of s_c(p) Phi_c(p)
+ *     dlogits[b,c,p] = s_c (Phi_c - sum_j s_j Phi_j), UN-normalised, 0 at invalid pixels (may be null)
+ *     inv = scale / (K N)   (the factor the gradient still lacks; required with dlogits)
+ *   scale = *scale_dev (a device float) or 1 when scale_dev is null.  N == 0: loss = 0 and inv = 0 - the term is an additive
+ *   regulariser, a batch without a valid pixel adds nothing instead of NaN.  The softmax and the products are evaluated in
+ *   double and each output is rounded once.  ws: wsdl_reduce_workspace() bytes (double partials per workgroup, added by a
+ *   finalize launch in fixed order; no atomics).  Two launches.
+ * wsdl_surface_map: no counterpart in the reference.  surf_x[p] = (d2_out_x[p] == 1), int64, for two maps of n pixels: with
+ *   d2_out from wsdl_edt (metric 0, border 1) these are the surface pixels of a mask, mask ^ binary_erosion(mask) with the
+ *   4-neighbour footprint and a background border (medpy's surface), as a label map wsdl_edt takes.
+ * wsdl_surface_stats: no counterpart in the reference; the sets behind the Hausdorff distance, its percentile and the
+ *   average symmetric surface distance.  d2_out_a / d2_out_b: the planes above of masks A (prediction) and B (ground truth);
+ *   to_a / to_b: d2_in of wsdl_edt (metric 0, border 0) of the two surface maps - the squared distance to the nearest surface
+ *   pixel of A resp. B, WSDL_EDT_FAR where that surface is empty.  Direction 0 is A -> B: { to_b[p] : p on the surface of A },
+ *   direction 1 is B -> A.  Per image b and direction d: n[b*2+d] = #surface pixels (int64), max_d2[b*2+d] = the largest
+ *   squared distance (int32, 0 for an empty set), sum_d[b*2+d] = sum of sqrt((double)d2) (double; per-workgroup partials and
+ *   a finalize launch in fixed order).  values (2,B,H,W) fp32 = (float)d2 on the surface, 0 elsewhere, and valid (2,B,H,W)
+ *   uint8 = on the surface: what wsdl_kth_value ranks for a percentile.  H^2 + W^2 < 2^24, so (float)d2 is exact; 2 B H W <
+ *   2^31.  ws: wsdl_surface_stats_workspace(B) bytes.  Two launches, no atomics. */
+int wsdl_signed_distance(const int* d2_out, const int* d2_in, float* phi, int B, int HW, long long phi_batch_stride,
+                         wsdl_stream_t stream);
+int wsdl_boundary_loss_fwd_bwd(const float* logits, const float* phi, const int64_t* labels, const int* class_list, int K,
+                               float* loss, float* dlogits, float* inv, const float* scale_dev, int B, int C, int H, int W,
+                               long long ignore_index, void* ws, size_t ws_bytes, wsdl_stream_t stream);
+int wsdl_surface_map(const int* d2_out_a, const int* d2_out_b, int64_t* surf_a, int64_t* surf_b, size_t n,
+                     wsdl_stream_t stream);
+size_t wsdl_surface_stats_workspace(int B);
+int wsdl_surface_stats(const int* d2_out_a, const int* d2_out_b, const int* to_a, const int* to_b, int B, int H, int W,
+                       long long* n_out, int* max_d2, double* sum_d, float* values, unsigned char* valid, void* ws,
+                       size_t ws_bytes, wsdl_stream_t stream);
+
 /* ---- refine_pseudo_mask inner step (TraditionalModel/AlternatingDirectionCutLoss.py:736-757) -
  * KL(softmax(X) || S) with log(X+1e-8), reduction 'batchmean', and its gradient wrt softmax(X). */
 int wsdl_kl_div_fwd_bwd(const float* xn, const float* s, float* loss, float* dxn, size_t n, int batch,

@@ -502,6 +502,40 @@ def evaluate_boundary_iou(model, loader, device="cuda", binarize="notebook", rat
     return ops.boundary_iou_from_counts(rows[:n].cpu().numpy())
 
 
+@torch.no_grad()
+def evaluate_surface_distances(model, loader, device="cuda", binarize="notebook", percentile=95.0):
+    """Mean Hausdorff distance, its ``percentile`` (HD95) and the average symmetric surface distance of the foreground, in
+    pixels, over the images ``evaluate_boundary_iou`` scores - the first of each batch, the same ground-truth rule
+    (``binarize``) and the same nearest resize of the argmax.  Region IoU and Boundary IoU are overlaps; these say how many
+    pixels a contour is off.  ``ops.surface_distance_stats`` per image; the statistics of every image land in a row of their
+    own on the device and one copy after the loop brings them to the host.  Returns ``(means, n_defined)``: a dict with
+    ``"hd"``, ``"hd95"`` and ``"assd"`` over the ``n_defined`` images where both the prediction and the ground truth have a
+    foreground pixel (``nan`` when there is none) - the conventions of ``ops.surface_distances_from_stats``."""
+    ops.check_percentile(percentile)
+    model.eval()
+    rows = torch.zeros(len(loader), 8, dtype=torch.float64, device=device)
+    n = 0
+    for img, (_label, true_mask) in loader:
+        x = img[0].to(device).unsqueeze(0)
+        tm = true_mask[0].to(device).clone()
+        if binarize == "notebook":
+            tm[tm == 2] = 1
+            tm = 1 - tm
+        elif binarize == "modular":
+            tm = (tm == 1).long()
+        else:
+            raise ValueError(binarize)
+        pred = model(x)["out"].squeeze(0).argmax(dim=0)
+        if pred.shape != tm.shape:
+            idx_h = (torch.arange(tm.shape[-2], device=device) * pred.shape[0] // tm.shape[-2])
+            idx_w = (torch.arange(tm.shape[-1], device=device) * pred.shape[1] // tm.shape[-1])
+            pred = pred[idx_h][:, idx_w]
+        ops.surface_stats_rows(ops.surface_distance_stats(pred[None], tm.long()[None], percentile=percentile), out=rows[n:n + 1])
+        n += 1
+    _per, means, defined = ops.surface_distances_from_stats(ops.surface_stats_from_rows(rows[:n].cpu().numpy()))
+    return means, defined
+
+
 def train_segmentation_model(loss_fn, run_id, lr=1e-4, num_epochs=10, batch_size=4, val_split=0.2, *, out_root="/content",
                              device="cuda", val_loader=None, num_workers=0, seed=None, log=print, model=None,
                              optimizer_kind="adam", optimizer_kwargs=None, criterion=None):

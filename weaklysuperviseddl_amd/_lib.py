@@ -125,6 +125,11 @@ SIGNATURES = {
     "wsdl_edt": (_i, [_vp, _ll, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "wsdl_band_counts": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "wsdl_boundary_confidence": (_i, [_vp, _vp, _f, _f, _vp, _sz, _vp]),
+    "wsdl_signed_distance": (_i, [_vp, _vp, _vp, _i, _i, _ll, _vp]),
+    "wsdl_boundary_loss_fwd_bwd": (_i, [_vp, _vp, _vp, C.POINTER(_i), _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _vp, _sz, _vp]),
+    "wsdl_surface_map": (_i, [_vp, _vp, _vp, _vp, _sz, _vp]),
+    "wsdl_surface_stats_workspace": (_sz, [_i]),
+    "wsdl_surface_stats": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wsdl_kl_div_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, _sz, _vp]),
     "wsdl_kl_div_per_image_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _sz, _vp, _sz, _vp]),
     "wsdl_refine_combine": (_i, [_vp, _vp, _vp, _vp, _f, _f, _vp, _i, _sz, _vp]),

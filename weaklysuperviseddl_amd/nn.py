@@ -427,6 +427,126 @@ class BoundaryAwareCrossEntropyLoss(nn.Module):
                 f"reduction={self.reduction!r}, label_smoothing={self.label_smoothing}, weight={self.weight is not None}")
 
 
+class BoundaryLoss(nn.Module):
+    """The boundary loss of Kervadec et al. ("Boundary loss for highly unbalanced segmentation", MIDL 2019):
+    ``mean(softmax(logits)_c * phi_c)`` over the valid pixels and the listed ``classes``, ``phi_c`` the signed distance map of
+    class ``c`` in ``labels`` (``ops.signed_distance_classes``: negative inside the class, positive outside, 0 for an image
+    the class is absent from or fills).  Every call fills its own ``phi`` buffer from ``labels`` and runs the fused kernel
+    (``ops.boundary_loss``); pixels with ``labels == ignore_index`` do not count.  It is an additive regulariser - see
+    ``CrossEntropyBoundaryLoss``; on its own it is unbounded below.
+
+    Conventions of ``BoundaryAwareCrossEntropyLoss``: ``phi`` (float32 (B,K,H,W)) and the two distance planes ``d2_out`` /
+    ``d2_in`` (int32) are buffers of this object, allocated anew only when the shape changes, so the addresses a launch
+    plan freezes stay put; the options (``classes`` as the string ``classes_key``) and every address are plain attributes,
+    so ``plan.host_scalars`` puts them into the plan key and changed ``classes`` record a new plan.  ``scale_dev``: an
+    optional one-element float32 device tensor that multiplies the loss (``ops.boundary_loss(scale=)``)."""
+
+    def __init__(self, classes=(1,), ignore_index=-100):
+        super().__init__()
+        for name in ("phi", "d2_out", "d2_in", "scale_dev"):
+            self.register_buffer(name, None, persistent=False)
+        self.set_classes(classes)
+        self.ignore_index = int(ignore_index)
+        self._refresh_pointers()
+
+    def set_classes(self, classes):
+        self.classes = ops.check_boundary_classes(classes, type(self).__name__)
+        self.classes_key = ",".join(str(c) for c in self.classes)
+        return self
+
+    def _refresh_pointers(self):
+        for name in ("phi", "d2_out", "d2_in", "scale_dev"):
+            t = getattr(self, name)
+            setattr(self, name + "_ptr", 0 if t is None else t.data_ptr())
+        self.phi_shape = "" if self.phi is None else "x".join(str(d) for d in self.phi.shape)
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self._refresh_pointers()
+        return out
+
+    def forward(self, logits, labels):
+        # (classes may have been assigned since the constructor checked them)
+        self.set_classes(self.classes)
+        labels = labels.long()
+        bufs = {"phi": self.phi, "out": self.d2_out, "in": self.d2_in}
+        ops.signed_distance_classes(labels, self.classes, out=bufs)
+        for k, name in (("phi", "phi"), ("out", "d2_out"), ("in", "d2_in")):
+            if getattr(self, name) is not bufs[k]:
+                setattr(self, name, bufs[k])
+        self._refresh_pointers()
+        return ops.boundary_loss(logits, self.phi, labels, classes=self.classes, ignore_index=self.ignore_index,
+                                 scale=self.scale_dev)
+
+    def extra_repr(self):
+        return f"classes={self.classes}, ignore_index={self.ignore_index}"
+
+
+class CrossEntropyBoundaryLoss(nn.Module):
+    """``cross entropy + alpha * boundary loss`` (Kervadec et al., MIDL 2019, combine a regional loss with the boundary term):
+    ``ops.cross_entropy(logits, labels, weight=, ignore_index=, label_smoothing=)`` plus ``BoundaryLoss(classes,
+    ignore_index)`` scaled by ``alpha``, added by the library's kernels (``ops.fanout`` / ``ops.add_scalars``), so
+    ``train_step`` replays one launch plan.
+
+    ``alpha`` lives in the one-element device buffer ``alpha_dev`` and is read by the kernel: the paper raises it every
+    epoch, and ``set_alpha(a)`` writes the buffer WITHOUT a new plan (a host float would be part of the plan key -
+    ``plan.host_scalars``).  ``alpha = 0`` is the cross entropy bit for bit.  The signed distance maps are rebuilt from
+    ``labels`` on every call (``boundary.phi``).
+
+        crit = wnn.CrossEntropyBoundaryLoss(alpha=0.01, classes=(1,)).to(device)
+        for epoch in range(epochs):
+            crit.set_alpha(min(1.0, 0.01 * (epoch + 1)))
+            loss = train_step(model, optimizer, images, masks, criterion=crit)
+    """
+
+    def __init__(self, alpha=0.01, classes=(1,), weight=None, ignore_index=-100, label_smoothing=0.0):
+        super().__init__()
+        ops.check_cross_entropy_options("mean", label_smoothing)
+        alpha = self._check_alpha(alpha)
+        if weight is not None and (not torch.is_tensor(weight) or weight.dim() != 1):
+            raise ValueError("CrossEntropyBoundaryLoss: weight must be a (C,) tensor")
+        self.register_buffer("weight", None if weight is None else weight.detach().to(torch.float32).clone())
+        self.register_buffer("alpha_dev", torch.tensor([alpha], dtype=torch.float32), persistent=False)
+        self.boundary = BoundaryLoss(classes, ignore_index)
+        self.ignore_index = int(ignore_index)
+        self.label_smoothing = float(label_smoothing)
+        self._refresh_pointers()
+
+    @staticmethod
+    def _check_alpha(alpha):
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 <= alpha < float("inf"):
+            raise ValueError(f"CrossEntropyBoundaryLoss: alpha {alpha!r} must be a finite number >= 0")
+        return float(alpha)
+
+    def set_alpha(self, alpha):
+        """Write ``alpha`` into the device buffer (a stream-ordered fill; the buffer keeps its address)."""
+        self.alpha_dev.fill_(self._check_alpha(alpha))
+        return self
+
+    def _refresh_pointers(self):
+        self.weight_ptr = 0 if self.weight is None else self.weight.data_ptr()
+        self.alpha_dev_ptr = self.alpha_dev.data_ptr()
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self._refresh_pointers()
+        return out
+
+    def forward(self, logits, labels):
+        ops.check_cross_entropy_options("mean", self.label_smoothing)
+        self._refresh_pointers()
+        labels = labels.long()
+        self.boundary.ignore_index = self.ignore_index
+        self.boundary.scale_dev = self.alpha_dev
+        a, b = ops.fanout(logits, 2)
+        ce = ops.cross_entropy(a, labels, self.ignore_index, weight=self.weight, label_smoothing=self.label_smoothing)
+        return ops.add_scalars(ce, self.boundary(b, labels))
+
+    def extra_repr(self):
+        return (f"classes={self.boundary.classes}, ignore_index={self.ignore_index}, label_smoothing={self.label_smoothing}, "
+                f"weight={self.weight is not None}")
+
+
 class PAMR(nn.Module):
     """Pixel-adaptive mask refinement (Araslanov & Roth, CVPR 2020) as a module without parameters: ``forward(images,
     scores)`` is ``ops.pamr(images, scores, num_iter, dilations)`` - scores (B,C,H,W) propagated ``num_iter`` times over

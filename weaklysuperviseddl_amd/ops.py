@@ -2867,6 +2867,247 @@ def boundary_confidence(labels, sigma=3.0, floor=0.0, value=1, *, out=None):
     return w
 
 
+MAX_BOUNDARY_CLASSES = 32              # planes of one signed distance map / classes of one boundary loss
+
+
+def check_boundary_classes(classes, name="boundary_loss"):
+    """ValueError unless ``classes`` is a non-empty tuple (or list) of at most 32 distinct ints >= 0 (no device needed);
+    returns it as a tuple of ints."""
+    if not isinstance(classes, (tuple, list)) or not 1 <= len(classes) <= MAX_BOUNDARY_CLASSES:
+        raise ValueError(f"{name}: classes {classes!r} must be a tuple of 1 to {MAX_BOUNDARY_CLASSES} ints")
+    if any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) or c < 0 for c in classes):
+        raise ValueError(f"{name}: classes {classes!r} must be ints >= 0")
+    classes = tuple(int(c) for c in classes)
+    if len(set(classes)) != len(classes):
+        raise ValueError(f"{name}: classes {classes!r} must be distinct")
+    return classes
+
+
+def signed_distance(labels, value=1, *, out=None):
+    """float32 (B,H,W) signed distance map of the class ``labels == value`` (Kervadec et al., MIDL 2019): with the two
+    Euclidean planes of ``edt(labels, value, border=False)``, ``phi = +sqrt(d2_in)`` on OUT pixels and ``phi = -(sqrt(d2_out)
+    - 1)`` on IN pixels - the published ``distance(negmask) * negmask - (distance(posmask) - 1) * posmask``.  Where the class is
+    absent from an image or fills it (a plane holds ``EDT_FAR``), ``phi = 0`` for the whole image: the published "class absent
+    -> zeros", extended to the full image, where scipy's transform is undefined.  Void labels are OUT (``edt``'s rule).  The
+    root is taken in double and rounded once.  Three launches (wsdl_edt, wsdl_signed_distance), no host read.  ``out``: a dict
+    whose ``"phi"`` (float32) and ``"out"`` / ``"in"`` (int32) tensors receive the map and the two planes (created there when
+    missing or of another shape)."""
+    value = _int_option(value, "signed_distance: value")
+    labels = _edt_labels(labels, "signed_distance")
+    B, H, W = labels.shape
+    d_out, d_in = edt(labels, value, out=out if out is not None else {})
+    phi = _out_tensor(out, "phi", (B, H, W), torch.float32, labels.device)
+    check(lib().wsdl_signed_distance(_p(d_out), _p(d_in), _p(phi), B, H * W, 0, _stream()))
+    return phi
+
+
+def signed_distance_classes(labels, classes, *, out=None):
+    """float32 (B,K,H,W): plane ``k`` is ``signed_distance(labels, classes[k])`` bit for bit - one ``edt`` and one conversion
+    per class, written straight into the plane (a multi-value transform is not built).  ``classes``: a non-empty tuple of at
+    most 32 distinct ints.  ``out``: a dict whose ``"phi"`` (float32 (B,K,H,W)) and ``"out"`` / ``"in"`` (int32 (B,H,W), the
+    planes of the LAST class) tensors are reused."""
+    classes = check_boundary_classes(classes, "signed_distance_classes")
+    labels = _edt_labels(labels, "signed_distance_classes")
+    B, H, W = labels.shape
+    K = len(classes)
+    bufs = out if out is not None else {}
+    phi = _out_tensor(out, "phi", (B, K, H, W), torch.float32, labels.device)
+    for k, c in enumerate(classes):
+        d_out, d_in = edt(labels, c, out=bufs)
+        check(lib().wsdl_signed_distance(_p(d_out), _p(d_in), _p(phi[:, k]), B, H * W, K * H * W, _stream()))
+    return phi
+
+
+class _BoundaryLoss(torch.autograd.Function):
+    """wsdl_boundary_loss_fwd_bwd: the loss and its un-normalised gradient in one kernel; the backward multiplies by the
+    upstream gradient and the factor the kernel left on the device, as ``_SoftmaxCEEx.backward`` does."""
+
+    @staticmethod
+    def forward(ctx, logits, phi, labels, classes, ignore_index, scale):
+        logits = _dense(logits, "logits")
+        B, Cc, H, W = logits.shape
+        K = len(classes)
+        loss = torch.empty((), device=logits.device, dtype=torch.float32)
+        need = logits.requires_grad
+        dl = torch.empty_like(logits) if need else None
+        inv = torch.empty(1, device=logits.device, dtype=torch.float32)
+        ws = workspace(lib().wsdl_reduce_workspace(), logits.device)
+        cls = (C.c_int * K)(*classes)
+        check(lib().wsdl_boundary_loss_fwd_bwd(_p(logits), _p(phi), _p(labels), cls, K, _p(loss), _p(dl), _p(inv), _p(scale),
+                                               B, Cc, H, W, int(ignore_index), _p(ws), ws.numel(), _stream()))
+        ctx.save_for_backward(dl, inv)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dl, inv = ctx.saved_tensors
+        out = torch.empty_like(dl)
+        sc = torch.empty_like(inv)
+        check(lib().wsdl_mul(_p(_dense(g.reshape(1))), _p(inv), _p(sc), 1, _stream()))      # upstream gradient x scale / (K N)
+        check(lib().wsdl_scale_by_device_scalar(_p(dl), _p(sc), _p(out), dl.numel(), _stream()))
+        return out, None, None, None, None, None
+
+
+def boundary_loss(logits, phi, labels=None, *, classes=(1,), ignore_index=-100, scale=None):
+    """The boundary loss of Kervadec et al. ("Boundary loss for highly unbalanced segmentation", MIDL 2019) on (B,C,H,W)
+    logits: ``scale / (K N) * sum over valid pixels p and the K classes c of softmax(logits)_c(p) * phi_c(p)`` - a 0-dim
+    float32 tensor - with its gradient from the same kernel (wsdl_boundary_loss_fwd_bwd).  It moves a contour in proportion to
+    its distance from the label's contour; an additive regulariser (``CrossEntropyBoundaryLoss``), negative where the
+    prediction sits inside the label.
+
+    ``phi``: float32 (B,K,H,W) signed distance maps, plane ``k`` belonging to class ``classes[k]`` (``signed_distance_classes``),
+    or (B,H,W) when ``K == 1`` - a constant, so a caller may compute it once per dataset.  ``labels`` (B,H,W) int64 or None
+    only say which pixels count: those with ``labels != ignore_index`` (None: all), ``N`` of them; ``N == 0`` gives 0 with a zero
+    gradient, not NaN.  ``scale``: a one-element float32 device tensor (a weight that changes without a new launch plan) or
+    None.  A class outside ``classes`` contributes through the softmax only.  The gradient flows into ``logits`` only.  The
+    softmax and the products run in double and every output is rounded once; bitwise reproducible."""
+    classes = check_boundary_classes(classes)
+    if not torch.is_tensor(logits) or logits.dim() != 4:
+        raise WsdlError("boundary_loss: logits must be a (B,C,H,W) tensor")
+    B, Cc, H, W = logits.shape
+    K = len(classes)
+    if max(classes) >= Cc:
+        raise ValueError(f"boundary_loss: classes {classes!r} must be below C = {Cc}")
+    _req(logits, "boundary_loss: logits")
+    if not torch.is_tensor(phi) or phi.dtype != torch.float32 or phi.device != logits.device or \
+            tuple(phi.shape) not in (((B, H, W), (B, 1, H, W)) if K == 1 else ((B, K, H, W),)):
+        raise WsdlError(f"boundary_loss: phi must be a float32 {(B, K, H, W)} tensor on {logits.device}"
+                        + (f" (or {(B, H, W)})" if K == 1 else ""))
+    phi = phi.detach()
+    phi = phi if phi.is_contiguous() else phi.contiguous()
+    if labels is not None:
+        if not torch.is_tensor(labels) or tuple(labels.shape) != (B, H, W) or labels.device != logits.device:
+            raise WsdlError(f"boundary_loss: labels must be a {(B, H, W)} tensor on {logits.device} or None")
+        labels = _req(labels, "boundary_loss: labels", torch.int64).detach().contiguous()
+    if scale is not None:
+        if not torch.is_tensor(scale) or scale.dtype != torch.float32 or scale.numel() != 1 or scale.device != logits.device:
+            raise WsdlError(f"boundary_loss: scale must be a one-element float32 tensor on {logits.device} or None")
+        scale = scale.detach()
+    return _BoundaryLoss.apply(logits, phi, labels, classes, int(ignore_index), scale)
+
+
+def check_percentile(percentile):
+    """ValueError unless ``percentile`` is a number in (0, 100] (no device needed)."""
+    if isinstance(percentile, bool) or not isinstance(percentile, (int, float)) or not 0.0 < percentile <= 100.0:
+        raise ValueError(f"surface distances: percentile {percentile!r} must be a number in (0, 100]")
+    return float(percentile)
+
+
+SURFACE_MAX_DIAG2 = 1 << 24             # H^2 + W^2 below this: every squared distance is an exact float32
+
+
+def surface_distance_stats(preds, labels, value=1, *, percentile=95.0, out=None):
+    """The per-image statistics of the surface distances between ``preds == value`` and ``labels == value`` (int64, bool or
+    uint8 device maps (B,H,W)), as a dict of device tensors - no host read; ``surface_distances_from_stats`` turns a host copy
+    into the Hausdorff distance, its percentile and the average symmetric surface distance.
+
+    The surface ``S(M)`` of a mask is its pixels with a 4-neighbour outside the mask or outside the image (``d2_out == 1``
+    of ``edt(M, value, border=True)``; ``M ^ binary_erosion(M)`` with ``border_value=0``, medpy's surface).  The directed set
+    A -> B is ``{ D_B[p] : p in S(A) }`` with ``D_B`` the Euclidean distance to the nearest pixel of ``S(B)``.  Index 0 of the
+    last axis is pred -> gt, index 1 is gt -> pred:
+
+    ``n`` int64 (B,2) the surface pixel counts; ``max_d2`` int32 (B,2) the largest squared distance, exact; ``sum_d`` float64
+    (B,2) the sum of ``sqrt(d2)`` (partials and a fixed-order finalize: bitwise reproducible); ``pct_d2`` float32 (B,2) the
+    NEAREST-RANK ``percentile`` of ``d2`` - the ``min(n, 1 + floor((1 - percentile / 100) n))``-th largest, by ``kth_value``.
+    Where the other surface is empty every distance is ``EDT_FAR``; where the own surface is empty ``n = 0``, ``max_d2 = 0``,
+    ``sum_d = 0`` and ``pct_d2 = +inf`` (``kth_value``'s empty run).  ``H^2 + W^2 < 2^24`` so that ``float(d2)`` is exact.
+    ``out``: a dict whose tensors (the four results and the intermediates) are reused.  The last step, the (2,B) -> (B,2) copy of
+    the percentiles, is a kernel of the tensor library: the call serves evaluation, a launch plan would not see that copy."""
+    percentile = check_percentile(percentile)
+    value = _int_option(value, "surface_distance_stats: value")
+    preds, labels = _edt_labels(preds, "surface_distance_stats"), _edt_labels(labels, "surface_distance_stats")
+    if preds.shape != labels.shape or preds.device != labels.device:
+        raise WsdlError(f"surface_distance_stats: preds {tuple(preds.shape)} on {preds.device} / labels {tuple(labels.shape)} on "
+                        f"{labels.device} must match")
+    B, H, W = labels.shape
+    if H * H + W * W >= SURFACE_MAX_DIAG2:
+        raise WsdlError(f"surface_distance_stats: H^2 + W^2 = {H * H + W * W} must be below 2^24 (float(d2) must be exact)")
+    dev = labels.device
+    bufs = out if out is not None else {}
+
+    def buf(key, shape, dtype):
+        return _out_tensor(bufs, key, shape, dtype, dev)
+
+    da, _ = edt(preds, value, border=True, want=("out",), out={"out": buf("d2_pred", (B, H, W), torch.int32)})
+    db, _ = edt(labels, value, border=True, want=("out",), out={"out": buf("d2_gt", (B, H, W), torch.int32)})
+    sa, sb = buf("surf_pred", (B, H, W), torch.int64), buf("surf_gt", (B, H, W), torch.int64)
+    check(lib().wsdl_surface_map(_p(da), _p(db), _p(sa), _p(sb), sa.numel(), _stream()))
+    _, to_a = edt(sa, 1, want=("in",), out={"in": buf("to_pred", (B, H, W), torch.int32)})
+    _, to_b = edt(sb, 1, want=("in",), out={"in": buf("to_gt", (B, H, W), torch.int32)})
+    n = buf("n", (B, 2), torch.int64)
+    max_d2 = buf("max_d2", (B, 2), torch.int32)
+    sum_d = buf("sum_d", (B, 2), torch.float64)
+    pct = buf("pct_d2", (B, 2), torch.float32)
+    vals, valid = buf("values", (2, B, H, W), torch.float32), buf("valid", (2, B, H, W), torch.uint8)
+    ws = workspace(lib().wsdl_surface_stats_workspace(B), dev)
+    check(lib().wsdl_surface_stats(_p(da), _p(db), _p(to_a), _p(to_b), B, H, W, _p(n), _p(max_d2), _p(sum_d), _p(vals),
+                                   _p(valid), _p(ws), ws.numel(), _stream()))
+    kth = buf("pct_rows", (2, B), torch.float32)
+    kn = buf("pct_n", (2, B), torch.int64)
+    for d in range(2):
+        kth_value(vals[d], k=1, frac=1.0 - percentile / 100.0, largest=True, valid=valid[d], segments=B,
+                  out={"value": kth[d], "n_valid": kn[d]})
+    pct.copy_(kth.t())
+    return {"n": n, "max_d2": max_d2, "sum_d": sum_d, "pct_d2": pct}
+
+
+def surface_distances_from_stats(stats):
+    """Host arithmetic on a host copy of ``surface_distance_stats`` (a dict of anything ``np.asarray`` takes, (images, 2)
+    each).  Per image: ``hd = sqrt(max(max_d2))``, the Hausdorff distance; ``hd95 = sqrt(max(pct_d2))``, the maximum of the
+    two directed percentiles - MONAI's convention, with the nearest-rank percentile instead of its linear interpolation;
+    ``assd = (sum_d[0] + sum_d[1]) / (n[0] + n[1])``, the average symmetric surface distance in its POOLED form - medpy
+    averages the two directed means instead.  An image where either surface is empty gets ``nan`` for all three and is left
+    out of the means.  Returns ``(per_image, means, n_defined)``: a list of dicts, a dict (``nan`` when no image is
+    defined) and the number of images the means are taken over."""
+    n = np.asarray(stats["n"]).reshape(-1, 2)
+    max_d2 = np.asarray(stats["max_d2"]).reshape(-1, 2).astype(np.float64)
+    sum_d = np.asarray(stats["sum_d"]).reshape(-1, 2).astype(np.float64)
+    pct = np.asarray(stats["pct_d2"]).reshape(-1, 2).astype(np.float64)
+    if not (len(n) == len(max_d2) == len(sum_d) == len(pct)) or len(n) == 0:
+        raise ValueError("surface_distances_from_stats: the four entries must hold the same, non-zero number of images")
+    nan = float("nan")
+    per = []
+    for i in range(len(n)):
+        if n[i, 0] == 0 or n[i, 1] == 0:
+            per.append({"hd": nan, "hd95": nan, "assd": nan})
+        else:
+            per.append({"hd": float(np.sqrt(max_d2[i].max())), "hd95": float(np.sqrt(pct[i].max())),
+                        "assd": float((sum_d[i, 0] + sum_d[i, 1]) / float(n[i, 0] + n[i, 1]))})
+    defined = [p for p in per if p["hd"] == p["hd"]]
+    means = {}
+    for key in ("hd", "hd95", "assd"):
+        acc = 0.0
+        for p in defined:
+            acc += p[key]
+        means[key] = acc / len(defined) if defined else nan
+    return per, means, len(defined)
+
+
+def surface_distances(preds, labels, value=1, *, percentile=95.0):
+    """``surface_distances_from_stats`` of ``surface_distance_stats(preds, labels, value, percentile=)``: Hausdorff distance,
+    its nearest-rank percentile and the pooled average symmetric surface distance, per image and as means - one host read."""
+    rows = surface_stats_rows(surface_distance_stats(preds, labels, value, percentile=percentile))
+    return surface_distances_from_stats(surface_stats_from_rows(rows.cpu().numpy()))
+
+
+def surface_stats_rows(stats, out=None):
+    """The four entries of ``surface_distance_stats`` as one float64 (B,8) device tensor - [n, max_d2, sum_d, pct_d2], two
+    columns each, every value exact in a double - so that one copy brings them to the host.  ``out``: a float64 (B,8) tensor
+    (e.g. rows of a preallocated table) to fill."""
+    row = torch.cat([stats[k].to(torch.float64) for k in ("n", "max_d2", "sum_d", "pct_d2")], dim=1)
+    if out is None:
+        return row
+    out.copy_(row)
+    return out
+
+
+def surface_stats_from_rows(rows):
+    """The inverse of ``surface_stats_rows`` on a host copy (images, 8): the dict ``surface_distances_from_stats`` takes."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 8)
+    return {"n": rows[:, 0:2].astype(np.int64), "max_d2": rows[:, 2:4].astype(np.int64), "sum_d": rows[:, 4:6],
+            "pct_d2": rows[:, 6:8]}
+
+
 def pairwise_affinity_loss(preds, image, window=5, sigma_color=0.1, sigma_space=0.0, apply_softmax=True,
                            normalise=0, cache=None):
     """``cache``: ``pairwise_cache(image, window, sigma_color)`` when the image stays fixed over many evaluations."""
