@@ -860,6 +860,52 @@ int wsdl_surface_stats(const int* d2_out_a, const int* d2_out_b, const int* to_a
                        long long* n_out, int* max_d2, double* sum_d, float* values, unsigned char* valid, void* ws,
                        size_t ws_bytes, wsdl_stream_t stream);
 
+/* ---- overlap and focal losses (csrc/overlap_loss.hip) - no counterpart in the reference: its region losses are the two
+ * Lovasz surrogates, and its pixel loss is the cross entropy.  Milletari et al., "V-Net", 3DV 2016 (soft Dice); Salehi et al.,
+ * "Tversky loss function for image segmentation", MLMI 2017; Abraham & Khan, "A novel focal Tversky loss function", ISBI 2019;
+ * Lin et al., "Focal loss for dense object detection", ICCV 2017.
+ * Common: logits (B,C,H,W) fp32, labels (B,H,W) int64, s = softmax over C.  A pixel is valid when labels[p] != ignore_index.
+ * Segments: the B images with per_image, else the whole batch is one segment (per_image: B <= 65535).  class_list: K distinct
+ * ints in [0, C) on the HOST (copied into the launch by value; 1 <= K <= 32).  y_c(p) = 1 where p is valid and labels[p] == c;
+ * a valid pixel whose label is not listed is background for every listed class.  The softmax and every product run in double
+ * and each output is rounded once; per-workgroup double partials are added by a finalize launch in fixed order - no atomics,
+ * bitwise reproducible.  With H W a multiple of 4 and 16-byte aligned pointers an item is four pixels, else one.
+ * wsdl_overlap_workspace(segments, K): bytes of ws for the two calls below (0 for arguments out of range).
+ * wsdl_overlap_sums: no counterpart in the reference.  sums[(segment * K + j) * 3 + {0, 1, 2}] (doubles) = for class
+ *   c = class_list[j]:  I = sum_p s_c(p) y_c(p),  P = sum over valid p of s_c(p),  Y = sum_p y_c(p) (exact).  Two launches.
+ * wsdl_tversky_fwd_bwd: no counterpart in the reference.  Per (segment, class), with N = I + smooth and
+ *   D = I + alpha (P - I) + beta (Y - I) + smooth:  T = N / D, T = 1 where D == 0; the term is (1 - T)^gamma, exactly 0 with a
+ *   zero gradient where 1 - T <= 0.  present_only drops the terms of classes with Y == 0 in their segment.
+ *     loss = scale * mean over the kept (segment, class) terms, 0 when none is kept
+ *     dlogits[b,j,p] = s_j (g_j - sum_c s_c g_c), g_c = a_c y_c(p) + b_c for a listed class, 0 for the others; exactly 0 at
+ *       invalid pixels (may be null).  a, b per (segment, class) come from the finalize launch:
+ *       d loss / d s_c(p) = -w [y D - N (alpha + y (1 - alpha - beta))] / D^2, w = scale gamma (1 - T)^(gamma - 1) / #terms;
+ *       0 for dropped terms.  This is the COMPLETE gradient: the backward multiplies it by the upstream scalar only
+ *       (wsdl_scale_by_device_scalar).
+ *   scale = *scale_dev (a device float) or 1 when scale_dev is null.  alpha, beta, smooth >= 0, gamma > 0, all finite.
+ *   alpha = beta = 1/2, gamma = 1 is the soft Dice loss 1 - (2 I + 2 smooth) / (P + Y + 2 smooth); gamma = 1 / (the paper's
+ *   gamma) is the focal Tversky loss.  sums (optional, S K 3 doubles) receives the sums above.  No valid pixel: loss 0,
+ *   gradient 0.  Three launches (two without dlogits), no host read.
+ * wsdl_focal_fwd_bwd: no counterpart in the reference.  The contract of wsdl_softmax_ce_ex_fwd_bwd without smoothing: for pixel
+ *   i with label y, class weights w (or null: 1), pixel weight p (or null: 1; p == 0 is an ignored pixel), q = 1 - s_y:
+ *     l_i = p_i w[y] q^gamma (-log s_y)                                              (0 where y == ignore_index)
+ *   reduction 0 (mean): *loss = sum_i l_i / sum_i p_i w[y_i] (gamma == 0 is the weighted cross entropy; 0/0 = NaN),
+ *   *inv_count = 1 / that denominator; 1 (sum): *loss = sum_i l_i, *inv_count = 1; 2 (none): loss points at B*H*W floats,
+ *   inv_count is not written.  dlogits (optional) = d l_i / d logits, UN-normalised, as there.  q is formed as the sum of the
+ *   other classes' exponentials over the denominator, and the gradient factor gamma s_y q^(gamma-1) log s_y - q^gamma as
+ *   q^gamma (gamma s_y (log s_y / q) - 1) with log s_y / q = -1 at q == 0: finite for every finite logit.  A label outside [0,C)
+ *   that is not ignore_index: NaN.  gamma >= 0, finite.  ws: wsdl_reduce_workspace() bytes.  Two launches (one for reduction 2). */
+size_t wsdl_overlap_workspace(int segments, int K);
+int wsdl_overlap_sums(const float* logits, const int64_t* labels, const int* class_list, int K, double* sums, int B, int C,
+                      int H, int W, int per_image, long long ignore_index, void* ws, size_t ws_bytes, wsdl_stream_t stream);
+int wsdl_tversky_fwd_bwd(const float* logits, const int64_t* labels, const int* class_list, int K, float* loss, float* dlogits,
+                         double* sums, const float* scale_dev, double alpha, double beta, double gamma, double smooth,
+                         int per_image, int present_only, int B, int C, int H, int W, long long ignore_index, void* ws,
+                         size_t ws_bytes, wsdl_stream_t stream);
+int wsdl_focal_fwd_bwd(const float* logits, const int64_t* labels, float* loss, float* dlogits, float* inv_count, int B, int C,
+                       int H, int W, double gamma, long long ignore_index, const float* class_weight,
+                       const float* pixel_weight, int reduction, void* ws, size_t ws_bytes, wsdl_stream_t stream);
+
 /* ---- refine_pseudo_mask inner step (TraditionalModel/AlternatingDirectionCutLoss.py:736-757) -
  * KL(softmax(X) || S) with log(X+1e-8), reduction 'batchmean', and its gradient wrt softmax(X). */
 int wsdl_kl_div_fwd_bwd(const float* xn, const float* s, float* loss, float* dxn, size_t n, int batch,

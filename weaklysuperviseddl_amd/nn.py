@@ -547,6 +547,188 @@ class CrossEntropyBoundaryLoss(nn.Module):
                 f"weight={self.weight is not None}")
 
 
+class TverskyLoss(nn.Module):
+    """The Tversky loss (Salehi et al., MLMI 2017) of ``ops.tversky_loss``: the mean over segments (the images with
+    ``per_image``, else the batch) and listed ``classes`` (None: all) of ``(1 - T) ** gamma``, ``T = (I + smooth) / (I + alpha
+    FP + beta FN + smooth)`` from the soft intersection, false positives and false negatives of ``softmax(logits)`` against
+    ``labels``.  ``alpha = beta = 0.5`` is soft Dice (``DiceLoss``); ``gamma = 1 / gamma_paper`` is the focal Tversky loss of
+    Abraham & Khan (ISBI 2019).  ``present_only`` leaves out the classes a segment has no pixel of.
+
+    Conventions of ``BoundaryLoss``: the options (``classes`` as the string ``classes_key``) are plain attributes, so
+    ``plan.host_scalars`` puts them into the plan key and a changed ``alpha`` records a new plan.  ``scale_dev``: an optional
+    one-element float32 device tensor that multiplies the loss (``ops.tversky_loss(scale=)``) and may change under a plan.
+
+        loss = train_step(model, optimizer, images, masks, criterion=wnn.TverskyLoss(alpha=0.3, beta=0.7, gamma=0.75))
+    """
+
+    def __init__(self, alpha=0.5, beta=0.5, gamma=1.0, smooth=1.0, classes=None, per_image=False, present_only=False,
+                 ignore_index=-100):
+        super().__init__()
+        self._check(alpha, beta, gamma, smooth)
+        self.register_buffer("scale_dev", None, persistent=False)
+        self.alpha, self.beta, self.gamma, self.smooth = float(alpha), float(beta), float(gamma), float(smooth)
+        self.set_classes(classes)
+        self.per_image = bool(per_image)
+        self.present_only = bool(present_only)
+        self.ignore_index = int(ignore_index)
+        self._refresh_pointers()
+
+    def _check(self, alpha, beta, gamma, smooth):
+        ops.check_tversky_options(alpha, beta, gamma, smooth, type(self).__name__)
+
+    def set_classes(self, classes):
+        self.classes = ops.check_overlap_classes(classes, None, type(self).__name__)
+        self.classes_key = "all" if self.classes is None else ",".join(str(c) for c in self.classes)
+        return self
+
+    def _refresh_pointers(self):
+        self.scale_dev_ptr = 0 if self.scale_dev is None else self.scale_dev.data_ptr()
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self._refresh_pointers()
+        return out
+
+    def forward(self, logits, labels):
+        # (options may have been assigned since the constructor checked them)
+        self._check(self.alpha, self.beta, self.gamma, self.smooth)
+        self.set_classes(self.classes)
+        self._refresh_pointers()
+        return ops.tversky_loss(logits, labels.long(), alpha=self.alpha, beta=self.beta, gamma=self.gamma, smooth=self.smooth,
+                                classes=self.classes, per_image=self.per_image, present_only=self.present_only,
+                                ignore_index=self.ignore_index, scale=self.scale_dev)
+
+    def extra_repr(self):
+        return (f"alpha={self.alpha}, beta={self.beta}, gamma={self.gamma}, smooth={self.smooth}, classes={self.classes}, "
+                f"per_image={self.per_image}, present_only={self.present_only}, ignore_index={self.ignore_index}")
+
+
+class DiceLoss(TverskyLoss):
+    """The soft Dice loss ``1 - (2 I + smooth) / (P + Y + smooth)`` averaged over segments and classes (``ops.dice_loss``):
+    ``TverskyLoss(alpha=0.5, beta=0.5, gamma=1, smooth=smooth / 2)`` bit for bit, with its other options."""
+
+    def __init__(self, smooth=1.0, classes=None, per_image=False, present_only=False, ignore_index=-100):
+        ops.check_tversky_options(0.5, 0.5, 1.0, smooth, "DiceLoss")
+        super().__init__(0.5, 0.5, 1.0, smooth / 2.0, classes, per_image, present_only, ignore_index)
+
+    def extra_repr(self):
+        return (f"smooth={2.0 * self.smooth}, classes={self.classes}, per_image={self.per_image}, "
+                f"present_only={self.present_only}, ignore_index={self.ignore_index}")
+
+
+class FocalLoss(nn.Module):
+    """The focal loss of Lin et al. (ICCV 2017) in its softmax form (``ops.focal_loss``): per pixel ``weight[y] (1 - s_y) **
+    gamma (-log s_y)``, with the class weights, the ``ignore_index``, the reductions and the per-pixel confidence weight of
+    ``CrossEntropyLoss`` (``set_pixel_weight``); ``gamma = 0`` is that cross entropy.  Conventions of ``CrossEntropyLoss``:
+    the buffers keep their addresses and every option is a plain attribute (``plan.host_scalars``)."""
+
+    def __init__(self, gamma=2.0, weight=None, ignore_index=-100, reduction="mean"):
+        super().__init__()
+        ops.check_focal_options(gamma, reduction, "FocalLoss")
+        if weight is not None and (not torch.is_tensor(weight) or weight.dim() != 1):
+            raise ValueError("FocalLoss: weight must be a (C,) tensor")
+        self.register_buffer("weight", None if weight is None else weight.detach().to(torch.float32).clone())
+        self.register_buffer("pixel_weight", None, persistent=False)
+        self.gamma = float(gamma)
+        self.ignore_index = int(ignore_index)
+        self.reduction = reduction
+        self._refresh_pointers()
+
+    def _refresh_pointers(self):
+        self.weight_ptr = 0 if self.weight is None else self.weight.data_ptr()
+        self.pixel_weight_ptr = 0 if self.pixel_weight is None else self.pixel_weight.data_ptr()
+        self.pixel_weight_shape = "" if self.pixel_weight is None else "x".join(str(d) for d in self.pixel_weight.shape)
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self._refresh_pointers()
+        return out
+
+    def set_pixel_weight(self, t):
+        if t is None:
+            self.pixel_weight = None
+        else:
+            if not torch.is_tensor(t) or t.dim() != 3:
+                raise ValueError("FocalLoss.set_pixel_weight: a (B,H,W) tensor or None")
+            cur = self.pixel_weight
+            if cur is None or cur.shape != t.shape or cur.device != t.device:
+                self.pixel_weight = torch.empty(t.shape, device=t.device, dtype=torch.float32)
+            self.pixel_weight.copy_(t.detach())
+        self._refresh_pointers()
+        return self
+
+    def forward(self, logits, labels):
+        ops.check_focal_options(self.gamma, self.reduction, "FocalLoss")
+        self._refresh_pointers()
+        return ops.focal_loss(logits, labels.long(), gamma=self.gamma, weight=self.weight, ignore_index=self.ignore_index,
+                              reduction=self.reduction, pixel_weight=self.pixel_weight)
+
+    def extra_repr(self):
+        return (f"gamma={self.gamma}, ignore_index={self.ignore_index}, reduction={self.reduction!r}, "
+                f"weight={self.weight is not None}")
+
+
+class CrossEntropyTverskyLoss(nn.Module):
+    """``cross entropy + lam * Tversky loss`` - the usual pairing of a pixel loss with a region-overlap loss for imbalanced
+    masks: ``ops.cross_entropy(logits, labels, weight=, ignore_index=, label_smoothing=)`` plus ``TverskyLoss(alpha, beta,
+    gamma, smooth, classes, per_image, present_only, ignore_index)`` scaled by ``lam``, added by the library's kernels
+    (``ops.fanout`` / ``ops.add_scalars``), so ``train_step`` replays one launch plan.  Built like
+    ``CrossEntropyBoundaryLoss``: ``lam`` lives in the one-element device buffer ``lam_dev`` and is read by the kernel;
+    ``set_lam(v)`` writes the buffer WITHOUT a new plan.  ``lam = 0`` is the cross entropy bit for bit.  The Tversky
+    options are attributes of ``self.tversky``; a changed ``alpha`` records a new plan.
+
+        crit = wnn.CrossEntropyTverskyLoss(lam=1.0, alpha=0.3, beta=0.7, classes=(1,)).to(device)
+        loss = train_step(model, optimizer, images, masks, criterion=crit)
+    """
+
+    def __init__(self, lam=1.0, alpha=0.5, beta=0.5, gamma=1.0, smooth=1.0, classes=None, per_image=False, present_only=False,
+                 weight=None, ignore_index=-100, label_smoothing=0.0):
+        super().__init__()
+        ops.check_cross_entropy_options("mean", label_smoothing)
+        lam = self._check_lam(lam)
+        if weight is not None and (not torch.is_tensor(weight) or weight.dim() != 1):
+            raise ValueError("CrossEntropyTverskyLoss: weight must be a (C,) tensor")
+        self.register_buffer("weight", None if weight is None else weight.detach().to(torch.float32).clone())
+        self.register_buffer("lam_dev", torch.tensor([lam], dtype=torch.float32), persistent=False)
+        self.tversky = TverskyLoss(alpha, beta, gamma, smooth, classes, per_image, present_only, ignore_index)
+        self.ignore_index = int(ignore_index)
+        self.label_smoothing = float(label_smoothing)
+        self._refresh_pointers()
+
+    @staticmethod
+    def _check_lam(lam):
+        if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not 0.0 <= lam < float("inf"):
+            raise ValueError(f"CrossEntropyTverskyLoss: lam {lam!r} must be a finite number >= 0")
+        return float(lam)
+
+    def set_lam(self, lam):
+        """Write ``lam`` into the device buffer (a stream-ordered fill; the buffer keeps its address)."""
+        self.lam_dev.fill_(self._check_lam(lam))
+        return self
+
+    def _refresh_pointers(self):
+        self.weight_ptr = 0 if self.weight is None else self.weight.data_ptr()
+        self.lam_dev_ptr = self.lam_dev.data_ptr()
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self._refresh_pointers()
+        return out
+
+    def forward(self, logits, labels):
+        ops.check_cross_entropy_options("mean", self.label_smoothing)
+        self._refresh_pointers()
+        labels = labels.long()
+        self.tversky.ignore_index = self.ignore_index
+        self.tversky.scale_dev = self.lam_dev
+        a, b = ops.fanout(logits, 2)
+        ce = ops.cross_entropy(a, labels, self.ignore_index, weight=self.weight, label_smoothing=self.label_smoothing)
+        return ops.add_scalars(ce, self.tversky(b, labels))
+
+    def extra_repr(self):
+        return (f"{self.tversky.extra_repr()}, label_smoothing={self.label_smoothing}, weight={self.weight is not None}")
+
+
 class PAMR(nn.Module):
     """Pixel-adaptive mask refinement (Araslanov & Roth, CVPR 2020) as a module without parameters: ``forward(images,
     scores)`` is ``ops.pamr(images, scores, num_iter, dilations)`` - scores (B,C,H,W) propagated ``num_iter`` times over

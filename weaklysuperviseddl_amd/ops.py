@@ -2512,6 +2512,24 @@ def iou_from_counts(counts, EMPTY=1.0, ignore=None):
     return 100 * np.array(ious)
 
 
+def dice_from_counts(counts, EMPTY=1.0, ignore=None):
+    """The hard Dice score from the (images, C, 2) counts of ``iou_counts`` (intersection i, union u), by the averaging rule
+    of ``iou_from_counts``: per class - the ``ignore`` class left out - the mean over the images of ``2 i / (i + u)`` (i + u
+    is |prediction| + |label|) as Python floats, ``EMPTY`` where the union is 0; returns 100 x that as a float64 array.
+    Host arithmetic only."""
+    counts = np.asarray(counts)
+    dices = []
+    for c in range(counts.shape[1]):
+        if ignore is not None and c == ignore:
+            continue
+        per = [2.0 * float(i) / float(i + u) if u else EMPTY for i, u in counts[:, c].tolist()]
+        acc = per[0]
+        for v in per[1:]:
+            acc += v
+        dices.append(acc if len(per) == 1 else acc / len(per))
+    return 100 * np.array(dices)
+
+
 class _BinaryXLoss(torch.autograd.Function):
     """binary_xloss / StableBCELoss (reference Lovasz-Softmax_Loss.py:122-140) with a void label; forward and gradient in
     one kernel.  ``labels``: int64 labels, or float32 targets (no void label then)."""
@@ -2984,6 +3002,200 @@ def boundary_loss(logits, phi, labels=None, *, classes=(1,), ignore_index=-100, 
             raise WsdlError(f"boundary_loss: scale must be a one-element float32 tensor on {logits.device} or None")
         scale = scale.detach()
     return _BoundaryLoss.apply(logits, phi, labels, classes, int(ignore_index), scale)
+
+
+# ---- overlap and focal losses (csrc/overlap_loss.hip; include/wsdl_hip.h "overlap and focal losses") ------------------------
+def _finite_number(v):
+    return not isinstance(v, bool) and isinstance(v, (int, float)) and v == v and abs(v) != float("inf")
+
+
+def check_tversky_options(alpha, beta, gamma, smooth, name="tversky_loss"):
+    """ValueError unless ``alpha``, ``beta``, ``smooth`` are finite numbers >= 0 and ``gamma`` a finite number > 0 (no device
+    needed)."""
+    for v, what in ((alpha, "alpha"), (beta, "beta"), (smooth, "smooth")):
+        if not _finite_number(v) or v < 0:
+            raise ValueError(f"{name}: {what} {v!r} must be a finite number >= 0")
+    if not _finite_number(gamma) or gamma <= 0:
+        raise ValueError(f"{name}: gamma {gamma!r} must be a finite number > 0")
+
+
+def check_focal_options(gamma, reduction, name="focal_loss"):
+    """ValueError unless ``gamma`` is a finite number >= 0 and ``reduction`` 'mean', 'sum' or 'none' (no device needed)."""
+    if not _finite_number(gamma) or gamma < 0:
+        raise ValueError(f"{name}: gamma {gamma!r} must be a finite number >= 0")
+    if reduction not in _CE_REDUCTIONS:
+        raise ValueError(f"{name}: reduction {reduction!r}: 'mean', 'sum' or 'none'")
+
+
+def check_overlap_classes(classes, C=None, name="tversky_loss"):
+    """``classes`` as a tuple of ints: None means all ``C`` classes; otherwise the rules of ``check_boundary_classes`` and,
+    with ``C``, every class below it.  ValueError otherwise (no device needed)."""
+    if classes is None:
+        if C is None:
+            return None
+        if not 1 <= int(C) <= MAX_BOUNDARY_CLASSES:
+            raise ValueError(f"{name}: classes=None lists all C = {C} classes, supported up to {MAX_BOUNDARY_CLASSES}; pass a list")
+        return tuple(range(int(C)))
+    classes = check_boundary_classes(classes, name)
+    if C is not None and max(classes) >= C:
+        raise ValueError(f"{name}: classes {classes!r} must be below C = {C}")
+    return classes
+
+
+def _overlap_inputs(logits, labels, classes, name):
+    if not torch.is_tensor(logits) or logits.dim() != 4:
+        raise WsdlError(f"{name}: logits must be a (B,C,H,W) tensor")
+    B, Cc, H, W = logits.shape
+    classes = check_overlap_classes(classes, Cc, name)
+    _req(logits, f"{name}: logits")
+    if not torch.is_tensor(labels) or tuple(labels.shape) != (B, H, W) or labels.device != logits.device:
+        raise WsdlError(f"{name}: labels must be a {(B, H, W)} tensor on {logits.device}")
+    labels = _req(labels, f"{name}: labels", torch.int64).detach().contiguous()
+    return labels, classes
+
+
+def overlap_sums(logits, labels, *, classes=None, ignore_index=-100, per_image=False, out=None):
+    """float64 (segments, K, 3) on the device - segments = B with ``per_image``, else 1: for the listed class ``c`` and
+    ``s = softmax(logits)``, ``[..., 0] = I = sum s_c y_c``, ``[..., 1] = P = sum over valid pixels of s_c`` and ``[..., 2] =
+    Y = sum y_c`` (exact), with ``y_c = 1`` where ``labels == c`` and the pixel is valid (``labels != ignore_index``) - what
+    soft Dice, Tversky and their relatives are made of (wsdl_overlap_sums: two launches, double accumulation in fixed order,
+    bitwise reproducible, no host read).  ``classes``: None for all C, or up to 32 distinct ints.  ``out``: a dict whose
+    ``"sums"`` tensor is reused."""
+    labels, classes = _overlap_inputs(logits, labels, classes, "overlap_sums")
+    logits = _dense(logits.detach(), "logits")
+    B, Cc, H, W = logits.shape
+    K, S = len(classes), B if per_image else 1
+    sums = _out_tensor(out, "sums", (S, K, 3), torch.float64, logits.device)
+    ws = workspace(_ws_bytes("wsdl_overlap_workspace", S, K), logits.device)
+    cls = (C.c_int * K)(*classes)
+    check(lib().wsdl_overlap_sums(_p(logits), _p(labels), cls, K, _p(sums), B, Cc, H, W, int(bool(per_image)), int(ignore_index),
+                                  _p(ws), ws.numel(), _stream()))
+    return sums
+
+
+class _TverskyLoss(torch.autograd.Function):
+    """wsdl_tversky_fwd_bwd: the loss and its COMPLETE gradient in three launches; the backward multiplies by the upstream
+    gradient only."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, classes, alpha, beta, gamma, smooth, per_image, present_only, ignore_index, scale):
+        logits = _dense(logits, "logits")
+        B, Cc, H, W = logits.shape
+        K, S = len(classes), B if per_image else 1
+        loss = torch.empty((), device=logits.device, dtype=torch.float32)
+        dl = torch.empty_like(logits) if logits.requires_grad else None
+        ws = workspace(_ws_bytes("wsdl_overlap_workspace", S, K), logits.device)
+        cls = (C.c_int * K)(*classes)
+        check(lib().wsdl_tversky_fwd_bwd(_p(logits), _p(labels), cls, K, _p(loss), _p(dl), None, _p(scale), alpha, beta, gamma,
+                                         smooth, int(per_image), int(present_only), B, Cc, H, W, int(ignore_index), _p(ws),
+                                         ws.numel(), _stream()))
+        ctx.save_for_backward(dl)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dl,) = ctx.saved_tensors
+        out = torch.empty_like(dl)
+        check(lib().wsdl_scale_by_device_scalar(_p(dl), _p(_dense(g.reshape(1))), _p(out), dl.numel(), _stream()))
+        return (out,) + (None,) * 10
+
+
+def tversky_loss(logits, labels, *, alpha=0.5, beta=0.5, gamma=1.0, smooth=1.0, classes=None, per_image=False,
+                 present_only=False, ignore_index=-100, scale=None):
+    """The Tversky loss (Salehi et al., MLMI 2017) on (B,C,H,W) logits and int64 (B,H,W) labels, a 0-dim float32 tensor with
+    its gradient (wsdl_tversky_fwd_bwd).  With the sums of ``overlap_sums`` per segment and listed class, ``N = I + smooth`` and
+    ``D = I + alpha (P - I) + beta (Y - I) + smooth``: ``T = N / D`` (1 where ``D == 0``), the term is ``(1 - T) ** gamma``
+    (exactly 0 with a zero gradient where ``1 - T <= 0``), and the loss is ``scale`` x the mean of the terms over segments and
+    classes; ``present_only`` leaves out the classes without a pixel in their segment (``Y == 0``); without a term the loss is
+    0.  ``alpha`` weighs false positives and ``beta`` false negatives; ``alpha = beta = 0.5`` is soft Dice (``dice_loss``),
+    ``alpha = beta = 1`` the soft Jaccard index.  The focal Tversky loss of Abraham & Khan (ISBI 2019), ``(1 - T) ** (1 /
+    gamma_paper)``, is ``gamma = 1 / gamma_paper`` (their 4/3: ``gamma=0.75``).
+
+    ``classes``: None for all C classes, or up to 32 distinct ints; a valid pixel of a class that is not listed is
+    background for every listed class.  Pixels with ``labels == ignore_index`` count nowhere and get a gradient of exactly
+    0; a batch without a valid pixel gives 0, not NaN.  ``scale``: a one-element float32 device tensor (a weight that changes
+    without a new launch plan) or None.  The gradient flows into ``logits`` only.  Everything runs in double and is rounded
+    once; three launches, bitwise reproducible, no host read."""
+    check_tversky_options(alpha, beta, gamma, smooth)
+    labels, classes = _overlap_inputs(logits, labels, classes, "tversky_loss")
+    if scale is not None:
+        if not torch.is_tensor(scale) or scale.dtype != torch.float32 or scale.numel() != 1 or scale.device != logits.device:
+            raise WsdlError(f"tversky_loss: scale must be a one-element float32 tensor on {logits.device} or None")
+        scale = scale.detach()
+    return _TverskyLoss.apply(logits, labels, classes, float(alpha), float(beta), float(gamma), float(smooth), bool(per_image),
+                              bool(present_only), int(ignore_index), scale)
+
+
+def dice_loss(logits, labels, *, smooth=1.0, classes=None, per_image=False, present_only=False, ignore_index=-100, scale=None):
+    """The soft Dice loss ``1 - (2 I + smooth) / (P + Y + smooth)``, averaged over segments and classes: it IS
+    ``tversky_loss(alpha=0.5, beta=0.5, gamma=1, smooth=smooth / 2)`` - with ``alpha = beta = 1/2`` the Tversky index is
+    ``(I + smooth / 2) / ((P + Y) / 2 + smooth / 2)``, the same number - bit for bit, and takes its other options."""
+    check_tversky_options(0.5, 0.5, 1.0, smooth, "dice_loss")
+    return tversky_loss(logits, labels, alpha=0.5, beta=0.5, gamma=1.0, smooth=smooth / 2.0, classes=classes,
+                        per_image=per_image, present_only=present_only, ignore_index=ignore_index, scale=scale)
+
+
+class _FocalLoss(torch.autograd.Function):
+    """wsdl_focal_fwd_bwd: the loss and its un-normalised gradient in one kernel; the backward is ``_SoftmaxCEEx.backward``'s."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, gamma, ignore_index, weight, pixel_weight, reduction):
+        logits = _dense(logits, "logits")
+        B, Cc, H, W = logits.shape
+        none = reduction == 2
+        loss = torch.empty((B, H, W) if none else (), device=logits.device, dtype=torch.float32)
+        dl = torch.empty_like(logits) if logits.requires_grad else None
+        inv = None if none else torch.empty(1, device=logits.device, dtype=torch.float32)
+        ws = workspace(lib().wsdl_reduce_workspace(), logits.device)
+        check(lib().wsdl_focal_fwd_bwd(_p(logits), _p(labels), _p(loss), _p(dl), _p(inv), B, Cc, H, W, gamma, int(ignore_index),
+                                       _p(weight), _p(pixel_weight), int(reduction), _p(ws), ws.numel(), _stream()))
+        ctx.none = none
+        ctx.save_for_backward(dl, inv)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dl, inv = ctx.saved_tensors
+        out = torch.empty_like(dl)
+        if ctx.none:
+            B, Cc, H, W = dl.shape
+            check(lib().wsdl_scale_by_pixel(_p(dl), _p(_dense(g, "upstream gradient")), _p(out), B, Cc, H, W, _stream()))
+        else:
+            sc = torch.empty_like(inv)
+            check(lib().wsdl_mul(_p(_dense(g.reshape(1))), _p(inv), _p(sc), 1, _stream()))      # upstream gradient x 1 / denominator
+            check(lib().wsdl_scale_by_device_scalar(_p(dl), _p(sc), _p(out), dl.numel(), _stream()))
+        return out, None, None, None, None, None, None
+
+
+def focal_loss(logits, labels, *, gamma=2.0, weight=None, ignore_index=-100, reduction="mean", pixel_weight=None):
+    """The focal loss of Lin et al. (ICCV 2017) in its softmax form on (B,C,H,W) logits and int64 (B,H,W) labels: per pixel
+    ``pixel_weight * weight[y] * (1 - s_y) ** gamma * (-log s_y)`` with ``s = softmax(logits)``, forward and gradient in one
+    kernel (wsdl_focal_fwd_bwd).  The options are those of ``cross_entropy`` without smoothing: ``weight`` (C,) float32
+    (the paper's alpha_t), ``pixel_weight`` (B,H,W) float32 >= 0 (0 = ignore the pixel), ``reduction`` 'mean' | 'sum' |
+    'none'; 'mean' divides by the sum of ``pixel_weight * weight[label]`` over the pixels that are not ignored, so ``gamma=0``
+    is the weighted cross entropy (0 / 0 gives NaN).  A label outside [0, C) other than ``ignore_index`` gives NaN.
+    ``gamma`` >= 0.  ``1 - s_y`` is formed as the sum of the other classes' probabilities and the result is finite for every
+    finite logit; everything runs in double and is rounded once.  The gradient flows into ``logits`` only."""
+    check_focal_options(gamma, reduction)
+    if not torch.is_tensor(logits) or logits.dim() != 4:
+        raise WsdlError("focal_loss: logits must be a (B,C,H,W) tensor")
+    B, Cc, H, W = logits.shape
+    _req(logits, "focal_loss: logits")
+    if not torch.is_tensor(labels) or tuple(labels.shape) != (B, H, W) or labels.device != logits.device:
+        raise WsdlError(f"focal_loss: labels must be a {(B, H, W)} tensor on {logits.device}")
+    labels = _req(labels, "focal_loss: labels", torch.int64).detach().contiguous()
+    for t, name, shape in ((weight, "weight", (Cc,)), (pixel_weight, "pixel_weight", (B, H, W))):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise WsdlError(f"focal_loss: {name} must be a float32 tensor")
+        if tuple(t.shape) != shape:
+            raise WsdlError(f"focal_loss: {name} {tuple(t.shape)} must be {shape}")
+        if t.device != logits.device:
+            raise WsdlError(f"focal_loss: {name} is on {t.device}, the logits on {logits.device}")
+    weight = None if weight is None else weight.detach().contiguous()
+    pixel_weight = None if pixel_weight is None else pixel_weight.detach().contiguous()
+    return _FocalLoss.apply(logits, labels, float(gamma), int(ignore_index), weight, pixel_weight, _CE_REDUCTIONS[reduction])
 
 
 def check_percentile(percentile):
