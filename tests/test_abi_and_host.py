@@ -442,6 +442,89 @@ def test_plan_key_sees_the_host_scalars_of_loss_objects():
     hash(plan.host_scalars(f1)), hash(plan.host_scalars(m)), hash(plan.loss_tag(f1))
 
 
+def test_the_nine_criteria_keep_their_plan_key_state_dict_and_repr():
+    """The loss criteria share one base class (``wnn._Criterion``); what a launch plan keys them on - ``plan.host_scalars``:
+    the class name, the scalar attributes of ``__dict__`` and of the sub-modules - is behaviour, and so are the ``state_dict``
+    keys and the ``repr``.  The literals are what the commit before the base class gave for default options and
+    ``weight=None`` on the CPU: every ``*_ptr`` is 0 except the address of the one-element ``alpha_dev`` / ``lam_dev`` buffer,
+    DEV below."""
+    import torch
+    from weaklysuperviseddl_amd import nn as wnn, plan
+    DEV = "the address of the object's own one-element buffer"
+    want = {
+        "CrossEntropyLoss": (
+         ('CrossEntropyLoss', (('_is_full_backward_hook', None), ('ignore_index', -100), ('label_smoothing', 0.0),
+         ('pixel_weight_ptr', 0), ('pixel_weight_shape', ''), ('reduction', 'mean'), ('training', True),
+         ('weight_ptr', 0))),
+         [],
+         "CrossEntropyLoss(ignore_index=-100, reduction='mean', label_smoothing=0.0, weight=False, pixel_weight=None)"),
+        "MinedCrossEntropyLoss": (
+         ('MinedCrossEntropyLoss', (('_is_full_backward_hook', None), ('drop_frac', 0.0), ('ignore_index', -100),
+         ('kept_ptr', 0), ('label_smoothing', 0.0), ('min_kept', 0), ('mode', 'hard'), ('pixel_weight_ptr', 0),
+         ('pixel_weight_shape', ''), ('reduction', 'mean'), ('scope', 'batch'), ('selection_ptr', 0), ('thresh', 0.7),
+         ('threshold_ptr', 0), ('training', True), ('valid_ptr', 0), ('weight_ptr', 0))),
+         [],
+         "MinedCrossEntropyLoss(mode='hard', thresh=0.7, min_kept=0, drop_frac=0.0, scope='batch', ignore_index=-100, reduction='mean', label_smoothing=0.0, weight=False)"),
+        "BoundaryAwareCrossEntropyLoss": (
+         ('BoundaryAwareCrossEntropyLoss', (('_is_full_backward_hook', None), ('d2_in_ptr', 0), ('d2_out_ptr', 0),
+         ('floor', 0.0), ('ignore_index', -100), ('label_smoothing', 0.0), ('pixel_weight_ptr', 0),
+         ('pixel_weight_shape', ''), ('reduction', 'mean'), ('sigma', 3.0), ('training', True), ('value', 1),
+         ('weight_ptr', 0))),
+         [],
+         "BoundaryAwareCrossEntropyLoss(sigma=3.0, floor=0.0, value=1, ignore_index=-100, reduction='mean', label_smoothing=0.0, weight=False)"),
+        "BoundaryLoss": (
+         ('BoundaryLoss', (('_is_full_backward_hook', None), ('classes_key', '1'), ('d2_in_ptr', 0), ('d2_out_ptr',
+         0), ('ignore_index', -100), ('phi_ptr', 0), ('phi_shape', ''), ('scale_dev_ptr', 0), ('training', True))),
+         [],
+         'BoundaryLoss(classes=(1,), ignore_index=-100)'),
+        "CrossEntropyBoundaryLoss": (
+         ('CrossEntropyBoundaryLoss', (('_is_full_backward_hook', None), ('alpha_dev_ptr', DEV), ('ignore_index',
+         -100), ('label_smoothing', 0.0), ('training', True), ('weight_ptr', 0), ('BoundaryLoss',
+         (('_is_full_backward_hook', None), ('classes_key', '1'), ('d2_in_ptr', 0), ('d2_out_ptr', 0),
+         ('ignore_index', -100), ('phi_ptr', 0), ('phi_shape', ''), ('scale_dev_ptr', 0), ('training', True))))),
+         [],
+         'CrossEntropyBoundaryLoss(\n  classes=(1,), ignore_index=-100, label_smoothing=0.0, weight=False\n  (boundary): BoundaryLoss(classes=(1,), ignore_index=-100)\n)'),
+        "TverskyLoss": (
+         ('TverskyLoss', (('_is_full_backward_hook', None), ('alpha', 0.5), ('beta', 0.5), ('classes', None),
+         ('classes_key', 'all'), ('gamma', 1.0), ('ignore_index', -100), ('per_image', False), ('present_only',
+         False), ('scale_dev_ptr', 0), ('smooth', 1.0), ('training', True))),
+         [],
+         'TverskyLoss(alpha=0.5, beta=0.5, gamma=1.0, smooth=1.0, classes=None, per_image=False, present_only=False, ignore_index=-100)'),
+        "DiceLoss": (
+         ('DiceLoss', (('_is_full_backward_hook', None), ('alpha', 0.5), ('beta', 0.5), ('classes', None),
+         ('classes_key', 'all'), ('gamma', 1.0), ('ignore_index', -100), ('per_image', False), ('present_only',
+         False), ('scale_dev_ptr', 0), ('smooth', 0.5), ('training', True))),
+         [],
+         'DiceLoss(smooth=1.0, classes=None, per_image=False, present_only=False, ignore_index=-100)'),
+        "FocalLoss": (
+         ('FocalLoss', (('_is_full_backward_hook', None), ('gamma', 2.0), ('ignore_index', -100), ('pixel_weight_ptr',
+         0), ('pixel_weight_shape', ''), ('reduction', 'mean'), ('training', True), ('weight_ptr', 0))),
+         [],
+         "FocalLoss(gamma=2.0, ignore_index=-100, reduction='mean', weight=False)"),
+        "CrossEntropyTverskyLoss": (
+         ('CrossEntropyTverskyLoss', (('_is_full_backward_hook', None), ('ignore_index', -100), ('label_smoothing',
+         0.0), ('lam_dev_ptr', DEV), ('training', True), ('weight_ptr', 0), ('TverskyLoss',
+         (('_is_full_backward_hook', None), ('alpha', 0.5), ('beta', 0.5), ('classes', None), ('classes_key', 'all'),
+         ('gamma', 1.0), ('ignore_index', -100), ('per_image', False), ('present_only', False), ('scale_dev_ptr', 0),
+         ('smooth', 1.0), ('training', True))))),
+         [],
+         'CrossEntropyTverskyLoss(\n  alpha=0.5, beta=0.5, gamma=1.0, smooth=1.0, classes=None, per_image=False, present_only=False, ignore_index=-100, label_smoothing=0.0, weight=False\n  (tversky): TverskyLoss(alpha=0.5, beta=0.5, gamma=1.0, smooth=1.0, classes=None, per_image=False, present_only=False, ignore_index=-100)\n)'),
+    }
+    assert len(want) == 9
+    for name, (key, state, text) in want.items():
+        crit = getattr(wnn, name)()
+        assert isinstance(crit, wnn._Criterion) and "_apply" not in vars(type(crit)) and "_refresh_pointers" not in vars(type(crit))
+        dev = {"CrossEntropyBoundaryLoss": "alpha_dev", "CrossEntropyTverskyLoss": "lam_dev"}.get(name)
+        if dev is not None:
+            key = (key[0], tuple((k[0], getattr(crit, dev).data_ptr()) if isinstance(k, tuple) and k[1:] == (DEV,) else k for k in key[1]))
+        assert plan.host_scalars(crit) == key, name
+        assert sorted(crit.state_dict()) == state, name
+        assert repr(crit) == text, name
+        hash(plan.host_scalars(crit))
+    w = wnn.FocalLoss(weight=torch.tensor([1.0, 2.0], dtype=torch.float64))
+    assert sorted(w.state_dict()) == ["weight"] and w.weight.dtype == torch.float32 and w.weight_ptr == w.weight.data_ptr()
+
+
 def test_the_range_guard_acts_by_default():
     """the sentinel must ACT in the default configuration (the reference's fp32 has no range floor), not
     only warn.  The product default is "auto"; tests/conftest.py pins "warn" inside tests (bit-for-bit comparisons need one

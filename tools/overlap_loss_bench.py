@@ -15,7 +15,8 @@ in the same run, the variants alternating inside a round.
                one-hot, softmax, three sums and a mean; the focal loss as log_softmax, gather, exp, pow and a mean
 Device-event times over back-to-back calls, three rounds, min .. max beside the mean.  The first section of the output is the
 register use of every kernel instantiation (hipcc -Rpass-analysis=kernel-resource-usage on csrc/overlap_loss.hip; needs no
-GPU: ``--resources-only`` writes just that section, ``--resources-from FILE`` takes it from such a file instead of compiling).
+GPU: ``--resources-only`` writes just that section - of ``--resources-source`` another file of csrc/, e.g. boundary_loss.hip -
+and ``--resources-from FILE`` takes it from such a file instead of compiling).
 Writes profiles/overlap_loss_bench.txt (``--out`` elsewhere)."""
 import argparse
 import ctypes as C
@@ -42,17 +43,18 @@ def kernel_name(mangled):
     return name + ("<" + ", ".join(re.findall(r"Li(\d+)E", t.group(1))) + ">" if t else "")
 
 
-def resource_lines():
-    """One line per kernel instantiation of csrc/overlap_loss.hip: VGPRs, AGPRs, SGPRs, scratch, occupancy."""
+def resource_lines(source="overlap_loss.hip"):
+    """One line per kernel instantiation of csrc/<source> (or of the file at an absolute path): VGPRs, AGPRs, SGPRs, scratch,
+    occupancy, LDS."""
     from weaklysuperviseddl_amd import _build
-    src = os.path.join(_build.CSRC, "overlap_loss.hip")
+    src = os.path.join(_build.CSRC, source)
     with tempfile.TemporaryDirectory() as tmp:
         cmd = [_build._hipcc()] + _build.FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.path.join(tmp, "o.o")]
         r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
-        raise SystemExit("overlap_loss_bench: hipcc failed:\n" + r.stderr[-2000:])
+        raise SystemExit(f"overlap_loss_bench: hipcc failed for {source}:\n" + r.stderr[-2000:])
     text = r.stderr
-    lines = [f"register use of csrc/overlap_loss.hip ({' '.join(_build.FLAGS)} -Rpass-analysis=kernel-resource-usage):"]
+    lines = [f"register use of csrc/{os.path.basename(source)} ({' '.join(_build.FLAGS)} -Rpass-analysis=kernel-resource-usage):"]
     cur, spills = None, 0
     for ln in text.splitlines():
         m = re.search(r"remark: +Function Name: (.*?) \[-Rpass", ln)
@@ -91,11 +93,12 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--resources-only", action="store_true")
     ap.add_argument("--resources-from", default=None)
+    ap.add_argument("--resources-source", default="overlap_loss.hip", help="the file of csrc/ the register table is made of")
     args = ap.parse_args()
     if args.resources_from:
         res = open(args.resources_from).read().splitlines()
     else:
-        res = resource_lines()
+        res = resource_lines(args.resources_source)
     if args.resources_only:
         text = "\n".join(res) + "\n"
         print(text, end="")

@@ -7,15 +7,12 @@
 //                            contour (either plane holds WSDL_EDT_FAR).  The planes are integers: the root is taken in double
 //                            and rounded once, so phi is float32(the float64 formula).  A batch stride on the output writes
 //                            plane k of a (B,K,H,W) map.
-//   boundary_loss_kernel     one pass over the logits: softmax, sum_c s_c Phi_c, and dlogits = s_c (Phi_c - sum_j s_j Phi_j).
-//                            The shape of softmax_ce_kernel (resample_loss.hip): a grid-stride loop, C = 2 and 3 held in
-//                            registers, any other C re-read per pass; per-workgroup partials in the reduce workspace and a
-//                            finalize launch that adds them in fixed order.  With H W a multiple of 4 (and 16-byte aligned
-//                            pointers) an item is four neighbouring pixels of one image - one 16-byte load per plane and
-//                            lane, two for the int64 labels; otherwise an item is one pixel.  The signed terms of the loss
-//                            cancel (phi < 0 inside, > 0 outside), so the softmax and the products are evaluated in double
-//                            and every output is rounded ONCE: the loss and the un-normalised gradient are the float32
-//                            neighbours of the exact values of the float32 inputs.  The partials are doubles.
+//   boundary_loss_kernel     one pass over the logits: softmax, sum_c s_c Phi_c, and dlogits = s_c (Phi_c - sum_j s_j Phi_j),
+//                            on the frame of softmax_item.h (items of four pixels or one, C = 2 and 3 in registers,
+//                            per-workgroup double partials in the reduce workspace and a finalize launch).  The signed terms
+//                            of the loss cancel (phi < 0 inside, > 0 outside), so the softmax and the products are evaluated
+//                            in double and every output is rounded ONCE: the loss and the un-normalised gradient are the
+//                            float32 neighbours of the exact values of the float32 inputs.
 //   surface_map_kernel       labels of the two surfaces (d2_out == 1 under border = 1) for the second transform.
 //   surface_stats_kernel     per image and direction: #surface pixels, max d2, sum sqrt(d2) over the surface of one mask of
 //                            the distance to the surface of the other; the float plane and validity plane wsdl_kth_value
@@ -27,18 +24,22 @@
 #include <cstdint>
 
 #include "common.h"
+#include "softmax_item.h"
 
 namespace {
 
+using wsdl::aligned16;
+using wsdl::ClassList;
+using wsdl::Item;
+using wsdl::load_f;
+using wsdl::load_l;
+using wsdl::slot_of;
+using wsdl::store_f;
+
 constexpr int kFar = WSDL_EDT_FAR;
 constexpr int kThreads = 256;
-constexpr int kMaxClasses = 32;
 constexpr int kLossBlocks = wsdl::kReduceSlots / 4;      // two double partials per workgroup in kReduceSlots floats
 constexpr int kStatGroups = 64;                          // workgroups per image of surface_stats_kernel
-
-struct ClassList {
-    int k[kMaxClasses];                                  // k[j] = the class whose signed distance map is plane j of phi
-};
 
 __global__ void __launch_bounds__(kThreads)
 signed_distance_kernel(const int* __restrict__ d2_out, const int* __restrict__ d2_in, float* __restrict__ phi, int HW,
@@ -52,33 +53,7 @@ signed_distance_kernel(const int* __restrict__ d2_out, const int* __restrict__ d
     }
 }
 
-template <int V>
-__device__ __forceinline__ void load_f(const float* __restrict__ p, float (&o)[V]) {
-    if (V == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        o[0] = t.x; o[V > 1 ? 1 : 0] = t.y; o[V > 2 ? 2 : 0] = t.z; o[V > 3 ? 3 : 0] = t.w;
-    } else {
-        o[0] = *p;
-    }
-}
-template <int V>
-__device__ __forceinline__ void store_f(float* __restrict__ p, const float (&o)[V]) {
-    if (V == 4)
-        *reinterpret_cast<float4*>(p) = make_float4(o[0], o[V > 1 ? 1 : 0], o[V > 2 ? 2 : 0], o[V > 3 ? 3 : 0]);
-    else
-        *p = o[0];
-}
-
-// the plane of phi that belongs to class c, -1 for a class outside the list (uniform: scalar compares)
-__device__ __forceinline__ int plane_of(const ClassList& cls, int K, int c) {
-    int kk = -1;
-    for (int j = 0; j < K; ++j)
-        if (cls.k[j] == c) kk = j;
-    return kk;
-}
-
-// NC: the C logits of an item stay in registers (NC == C, 2 or 3); NC == 0 re-reads them per pass (any C).
-// V: pixels per item (4: H W is a multiple of 4, so the four pixels lie in one image and every plane offset is 16-byte aligned).
+// <NC, V>: softmax_item.h.  Plane j of phi belongs to class cls.k[j].
 template <int NC, int V>
 __global__ void __launch_bounds__(kThreads)
 boundary_loss_kernel(const float* __restrict__ logits, const float* __restrict__ phi, const long long* __restrict__ labels,
@@ -90,72 +65,44 @@ boundary_loss_kernel(const float* __restrict__ logits, const float* __restrict__
     int kof[NR];                                          // (NC > 0) the plane of each class, found once
     if (NC > 0) {
 #pragma unroll
-        for (int c = 0; c < NC; ++c) kof[c] = plane_of(cls, K, c);
+        for (int c = 0; c < NC; ++c) kof[c] = slot_of(cls, K, c);
     }
     double acc = 0.0;
     unsigned cnt = 0u;
     for (long long it = blockIdx.x * (long long)blockDim.x + threadIdx.x; it < nitems;
          it += (long long)gridDim.x * blockDim.x) {
-        const long long i = it * V;                       // the first pixel of the item
-        const long long b = i / HW;
-        const int r = (int)(i - b * HW);
-        const float* lp = logits + b * C * HW + r;
-        const float* pp = phi + b * K * HW + r;
+        Item<NC, V> px(logits, it * V, C, HW, false);
+        const float* pp = phi + px.b * K * HW + px.r;
         bool valid[V];
 #pragma unroll
         for (int v = 0; v < V; ++v) valid[v] = true;
         if (labels) {
-            if (V == 4) {
-                const longlong2 a = *reinterpret_cast<const longlong2*>(labels + i);
-                const longlong2 c = *reinterpret_cast<const longlong2*>(labels + i + 2);
-                valid[0] = a.x != ignore_index; valid[V > 1 ? 1 : 0] = a.y != ignore_index;
-                valid[V > 2 ? 2 : 0] = c.x != ignore_index; valid[V > 3 ? 3 : 0] = c.y != ignore_index;
-            } else {
-                valid[0] = labels[i] != ignore_index;
-            }
-        }
-        float reg[NR][V];
-        if (NC > 0) {
+            long long lab[V];
+            load_l<V>(labels + px.i, lab);
 #pragma unroll
-            for (int c = 0; c < NC; ++c) load_f<V>(lp + (long long)c * HW, reg[c]);
+            for (int v = 0; v < V; ++v) valid[v] = lab[v] != ignore_index;
         }
-        auto logit = [&](int c, float (&o)[V]) {
-            if (NC > 0) {
-#pragma unroll
-                for (int v = 0; v < V; ++v) o[v] = reg[NC > 0 ? c : 0][v];
-            } else {
-                load_f<V>(lp + (long long)c * HW, o);
-            }
-        };
+        px.load_planes();
         // Phi_c of the item: plane kof(c) of phi, 0 for a class outside the list
         auto big_phi = [&](int c, float (&o)[V]) {
-            const int kk = NC > 0 ? kof[NC > 0 ? c : 0] : plane_of(cls, K, c);
+            const int kk = NC > 0 ? kof[NC > 0 ? c : 0] : slot_of(cls, K, c);
 #pragma unroll
             for (int v = 0; v < V; ++v) o[v] = 0.f;
             if (kk >= 0) load_f<V>(pp + (long long)kk * HW, o);
             return kk >= 0;
         };
-        float m[V];
-#pragma unroll
-        for (int v = 0; v < V; ++v) m[v] = -INFINITY;
-#pragma unroll NR
-        for (int c = 0; c < CC; ++c) {
-            float l[V];
-            logit(c, l);
-#pragma unroll
-            for (int v = 0; v < V; ++v) m[v] = fmaxf(m[v], l[v]);
-        }
+        px.max_pass(C);
         double se[V], dot[V];
 #pragma unroll
         for (int v = 0; v < V; ++v) se[v] = dot[v] = 0.0;
 #pragma unroll NR
         for (int c = 0; c < CC; ++c) {
             float l[V], ph[V];
-            logit(c, l);
+            px.logit(c, l);
             const bool listed = big_phi(c, ph);
 #pragma unroll
             for (int v = 0; v < V; ++v) {
-                const double e = exp((double)l[v] - (double)m[v]);
+                const double e = exp((double)l[v] - (double)px.m[v]);
                 se[v] += e;
                 if (listed) dot[v] += e * (double)ph[v];
             }
@@ -171,27 +118,22 @@ boundary_loss_kernel(const float* __restrict__ logits, const float* __restrict__
             }
         }
         if (dlogits) {
-            float* dp = dlogits + b * C * HW + r;
+            float* dp = dlogits + px.b * C * HW + px.r;
 #pragma unroll NR
             for (int c = 0; c < CC; ++c) {
                 float l[V], ph[V], g[V];
-                logit(c, l);
+                px.logit(c, l);
                 big_phi(c, ph);
 #pragma unroll
                 for (int v = 0; v < V; ++v) {
-                    const double s = exp((double)l[v] - (double)m[v]) * inv[v];
+                    const double s = exp((double)l[v] - (double)px.m[v]) * inv[v];
                     g[v] = valid[v] ? (float)(s * ((double)ph[v] - dot[v])) : 0.f;
                 }
                 store_f<V>(dp + (long long)c * HW, g);
             }
         }
     }
-    acc = block_sum_d(acc, sm);
-    const double n = block_sum_d((double)cnt, sm);
-    if (threadIdx.x == 0) {
-        part[blockIdx.x] = acc;
-        part[gridDim.x + blockIdx.x] = n;
-    }
+    wsdl::store_partials(acc, (double)cnt, part, sm);
 }
 
 // loss = scale / (K N) * sum, inv = scale / (K N); N == 0: both 0 (an additive regulariser without a pixel adds nothing)
@@ -199,13 +141,8 @@ __global__ void boundary_loss_finalize_kernel(const double* __restrict__ part, i
                                               const float* __restrict__ scale_dev, float* __restrict__ loss,
                                               float* __restrict__ inv) {
     __shared__ double sm[16];
-    double s = 0.0, c = 0.0;
-    for (int i = threadIdx.x; i < blocks; i += blockDim.x) {
-        s += part[i];
-        c += part[blocks + i];
-    }
-    s = block_sum_d(s, sm);
-    c = block_sum_d(c, sm);
+    double s, c;
+    wsdl::sum_partials(part, blocks, sm, s, c);
     if (threadIdx.x == 0) {
         const double scale = scale_dev ? (double)*scale_dev : 1.0;
         const double f = c > 0.0 ? scale / ((double)K * c) : 0.0;
@@ -295,18 +232,6 @@ surface_stats_finalize_kernel(const double* __restrict__ part, int G, long long*
 }
 
 inline int flat_grid(long long n, int cap) { return (int)std::min<long long>((n + kThreads - 1) / kThreads, cap); }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-template <int NC>
-void loss_launch(bool vec, int blocks, hipStream_t s, const float* logits, const float* phi, const long long* labels,
-                 const ClassList& cls, int K, double* part, float* dlogits, int C, int HW, long long nitems, long long ignore) {
-    if (vec)
-        hipLaunchKernelGGL((boundary_loss_kernel<NC, 4>), dim3(blocks), dim3(kThreads), 0, s, logits, phi, labels, cls, K, part,
-                           dlogits, C, HW, nitems, ignore);
-    else
-        hipLaunchKernelGGL((boundary_loss_kernel<NC, 1>), dim3(blocks), dim3(kThreads), 0, s, logits, phi, labels, cls, K, part,
-                           dlogits, C, HW, nitems, ignore);
-}
 
 }  // namespace
 
@@ -331,14 +256,9 @@ int wsdl_boundary_loss_fwd_bwd(const float* logits, const float* phi, const int6
                                long long ignore_index, void* ws, size_t ws_bytes, wsdl_stream_t stream) {
     WSDL_REQUIRE(logits && phi && class_list && loss && ws, "boundary_loss: null pointer");
     WSDL_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "boundary_loss: bad shape");
-    WSDL_REQUIRE(K >= 1 && K <= kMaxClasses, "boundary_loss: K = %d classes, supported 1..%d", K, kMaxClasses);
     WSDL_REQUIRE(!dlogits || inv, "boundary_loss: the gradient needs inv (it is left unnormalised)");
     ClassList cls{};
-    for (int j = 0; j < K; ++j) {
-        WSDL_REQUIRE(class_list[j] >= 0 && class_list[j] < C, "boundary_loss: class %d is outside [0, %d)", class_list[j], C);
-        for (int i = 0; i < j; ++i) WSDL_REQUIRE(class_list[i] != class_list[j], "boundary_loss: class %d is listed twice", class_list[j]);
-        cls.k[j] = class_list[j];
-    }
+    if (int rc = wsdl::fill_class_list("boundary_loss", class_list, K, C, cls)) return rc;
     if (ws_bytes < wsdl_reduce_workspace()) {
         wsdl::set_error("boundary_loss: workspace too small");
         return WSDL_EWORKSPACE;
@@ -351,9 +271,10 @@ int wsdl_boundary_loss_fwd_bwd(const float* logits, const float* phi, const int6
     hipStream_t s = wsdl::as_stream(stream);
     double* part = static_cast<double*>(ws);
     const auto* y = reinterpret_cast<const long long*>(labels);
-    if (C == 2) loss_launch<2>(vec, blocks, s, logits, phi, y, cls, K, part, dlogits, C, HW, nitems, ignore_index);
-    else if (C == 3) loss_launch<3>(vec, blocks, s, logits, phi, y, cls, K, part, dlogits, C, HW, nitems, ignore_index);
-    else loss_launch<0>(vec, blocks, s, logits, phi, y, cls, K, part, dlogits, C, HW, nitems, ignore_index);
+    wsdl::dispatch_item(C, vec, [&](auto nc, auto v) {
+        hipLaunchKernelGGL((boundary_loss_kernel<decltype(nc)::value, decltype(v)::value>), dim3(blocks), dim3(kThreads), 0, s, logits,
+                           phi, y, cls, K, part, dlogits, C, HW, nitems, ignore_index);
+    });
     WSDL_LAUNCH_CHECK();
     hipLaunchKernelGGL(boundary_loss_finalize_kernel, dim3(1), dim3(kThreads), 0, s, part, blocks, K, scale_dev, loss, inv);
     WSDL_LAUNCH_CHECK();

@@ -2,10 +2,8 @@
 // int64 (B,H,W) labels.  The reference has none of this; contract: include/wsdl_hip.h "overlap and focal losses".
 //
 //   overlap_sums_kernel      one pass over the logits: softmax, and per segment (an image with per_image, else the batch) and
-//                            listed class c the three sums I = sum s_c y_c, P = sum_valid s_c, Y = sum y_c.  The shape of
-//                            boundary_loss_kernel: C = 2 and 3 held in registers, any other C re-read per pass; an item is four
-//                            neighbouring pixels of one image where H W is a multiple of 4 and every pointer is 16-byte
-//                            aligned, else one pixel.  gridDim.y is the segment, so no pixel straddles two of them.  Every lane
+//                            listed class c the three sums I = sum s_c y_c, P = sum_valid s_c, Y = sum y_c.  Items and <NC, V>
+//                            as in softmax_item.h.  gridDim.y is the segment, so no pixel straddles two of them.  Every lane
 //                            keeps 2 double sums and a count per class (the generic form: per LISTED class, up to 32 - fully
 //                            unrolled, static register indices), a workgroup adds its four waves in fixed order and writes
 //                            one partial per (segment, workgroup, class, sum).
@@ -29,18 +27,23 @@
 #include <cstdint>
 
 #include "common.h"
+#include "softmax_item.h"
 
 namespace {
 
+using wsdl::aligned16;
+using wsdl::ClassList;
+using wsdl::Item;
+using wsdl::kMaxClasses;
+using wsdl::load_f;
+using wsdl::load_l;
+using wsdl::slot_of;
+using wsdl::store_f;
+
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr int kMaxClasses = 32;
 constexpr int kMaxSegments = 65535;                      // gridDim.y
 constexpr int kFocalBlocks = wsdl::kReduceSlots / 4;     // two double partials per workgroup in kReduceSlots floats
-
-struct ClassList {
-    int k[kMaxClasses];                                  // k[j] = the j-th listed class
-};
 
 struct TverskyArgs {
     int on;                                              // 0: the sums only
@@ -48,49 +51,12 @@ struct TverskyArgs {
     double alpha, beta, gamma, smooth;
 };
 
-template <int V>
-__device__ __forceinline__ void load_f(const float* __restrict__ p, float (&o)[V]) {
-    if (V == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        o[0] = t.x; o[V > 1 ? 1 : 0] = t.y; o[V > 2 ? 2 : 0] = t.z; o[V > 3 ? 3 : 0] = t.w;
-    } else {
-        o[0] = *p;
-    }
-}
-template <int V>
-__device__ __forceinline__ void store_f(float* __restrict__ p, const float (&o)[V]) {
-    if (V == 4)
-        *reinterpret_cast<float4*>(p) = make_float4(o[0], o[V > 1 ? 1 : 0], o[V > 2 ? 2 : 0], o[V > 3 ? 3 : 0]);
-    else
-        *p = o[0];
-}
-template <int V>
-__device__ __forceinline__ void load_l(const long long* __restrict__ p, long long (&o)[V]) {
-    if (V == 4) {
-        const longlong2 a = *reinterpret_cast<const longlong2*>(p);
-        const longlong2 c = *reinterpret_cast<const longlong2*>(p + 2);
-        o[0] = a.x; o[V > 1 ? 1 : 0] = a.y; o[V > 2 ? 2 : 0] = c.x; o[V > 3 ? 3 : 0] = c.y;
-    } else {
-        o[0] = *p;
-    }
-}
-
-// the position of class c in the list, -1 for a class outside it (uniform: scalar compares)
-__device__ __forceinline__ int slot_of(const ClassList& cls, int K, int c) {
-    int kk = -1;
-    for (int j = 0; j < K; ++j)
-        if (cls.k[j] == c) kk = j;
-    return kk;
-}
-
-// NC: the C logits of an item stay in registers (NC == C, 2 or 3) and the accumulators are per CLASS; NC == 0 re-reads the
-// logits per pass (any C) and the accumulators are per LISTED class.  V: pixels per item.
+// <NC, V>: softmax_item.h.  With NC > 0 the accumulators are per CLASS, with NC == 0 per LISTED class.
 // part[((segment * gridDim.x + workgroup) * K + j) * 3 + {0: I, 1: P, 2: Y}]
 template <int NC, int V>
 __global__ void __launch_bounds__(kThreads)
 overlap_sums_kernel(const float* __restrict__ logits, const long long* __restrict__ labels, ClassList cls, int K,
                     double* __restrict__ part, int C, int HW, long long seg_items, long long seg_pix, long long ignore_index) {
-    constexpr int NR = NC > 0 ? NC : 1;
     constexpr int NA = NC > 0 ? NC : kMaxClasses;
     __shared__ double sm[kWaves][NA * 3];
     double accI[NA], accP[NA];
@@ -103,34 +69,22 @@ overlap_sums_kernel(const float* __restrict__ logits, const long long* __restric
     const long long base = blockIdx.y * seg_pix;
     for (long long it = blockIdx.x * (long long)blockDim.x + threadIdx.x; it < seg_items;
          it += (long long)gridDim.x * blockDim.x) {
-        const long long i = base + it * V;                // the first pixel of the item
-        const long long b = i / HW;
-        const int r = (int)(i - b * HW);
-        const float* lp = logits + b * C * HW + r;
+        Item<NC, V> px(logits, base + it * V, C, HW);
         long long lab[V];
-        load_l<V>(labels + i, lab);
+        load_l<V>(labels + px.i, lab);
         bool valid[V];
 #pragma unroll
         for (int v = 0; v < V; ++v) valid[v] = lab[v] != ignore_index;
-        float m[V];
-#pragma unroll
-        for (int v = 0; v < V; ++v) m[v] = -INFINITY;
+        px.max_pass(C);
         if (NC > 0) {
-            float reg[NR][V];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) load_f<V>(lp + (long long)c * HW, reg[c]);
-#pragma unroll
-            for (int c = 0; c < NC; ++c)
-#pragma unroll
-                for (int v = 0; v < V; ++v) m[v] = fmaxf(m[v], reg[c][v]);
-            double e[NR][V], se[V];
+            double e[Item<NC, V>::NR][V], se[V];
 #pragma unroll
             for (int v = 0; v < V; ++v) se[v] = 0.0;
 #pragma unroll
             for (int c = 0; c < NC; ++c)
 #pragma unroll
                 for (int v = 0; v < V; ++v) {
-                    e[c][v] = exp((double)reg[c][v] - (double)m[v]);
+                    e[c][v] = exp((double)px.reg[c][v] - (double)px.m[v]);
                     se[v] += e[c][v];
                 }
 #pragma unroll
@@ -149,20 +103,14 @@ overlap_sums_kernel(const float* __restrict__ logits, const long long* __restric
                 }
             }
         } else {
-            for (int c = 0; c < C; ++c) {
-                float l[V];
-                load_f<V>(lp + (long long)c * HW, l);
-#pragma unroll
-                for (int v = 0; v < V; ++v) m[v] = fmaxf(m[v], l[v]);
-            }
             double se[V];
 #pragma unroll
             for (int v = 0; v < V; ++v) se[v] = 0.0;
             for (int c = 0; c < C; ++c) {
                 float l[V];
-                load_f<V>(lp + (long long)c * HW, l);
+                px.logit(c, l);
 #pragma unroll
-                for (int v = 0; v < V; ++v) se[v] += exp((double)l[v] - (double)m[v]);
+                for (int v = 0; v < V; ++v) se[v] += exp((double)l[v] - (double)px.m[v]);
             }
             double inv[V];
 #pragma unroll
@@ -172,10 +120,10 @@ overlap_sums_kernel(const float* __restrict__ logits, const long long* __restric
                 if (j < K) {                              // (uniform)
                     const int c = cls.k[j];
                     float l[V];
-                    load_f<V>(lp + (long long)c * HW, l);
+                    px.logit(c, l);
 #pragma unroll
                     for (int v = 0; v < V; ++v) {
-                        const double s = exp((double)l[v] - (double)m[v]) * inv[v];
+                        const double s = exp((double)l[v] - (double)px.m[v]) * inv[v];
                         if (valid[v]) {
                             accP[j] += s;
                             if (lab[v] == c) {
@@ -301,27 +249,11 @@ tversky_grad_kernel(const float* __restrict__ logits, const long long* __restric
     }
     for (long long it = blockIdx.x * (long long)blockDim.x + threadIdx.x; it < nitems;
          it += (long long)gridDim.x * blockDim.x) {
-        const long long i = it * V;
-        const long long b = i / HW;
-        const int r = (int)(i - b * HW);
-        const float* lp = logits + b * C * HW + r;
-        float* dp = dlogits + b * C * HW + r;
-        const double* cf = coef + (per_image ? b * K * 2 : 0);
+        Item<NC, V> px(logits, it * V, C, HW);
+        float* dp = dlogits + px.b * C * HW + px.r;
+        const double* cf = coef + (per_image ? px.b * K * 2 : 0);
         long long lab[V];
-        load_l<V>(labels + i, lab);
-        float reg[NR][V];
-        if (NC > 0) {
-#pragma unroll
-            for (int c = 0; c < NC; ++c) load_f<V>(lp + (long long)c * HW, reg[c]);
-        }
-        auto logit = [&](int c, float (&o)[V]) {
-            if (NC > 0) {
-#pragma unroll
-                for (int v = 0; v < V; ++v) o[v] = reg[NC > 0 ? c : 0][v];
-            } else {
-                load_f<V>(lp + (long long)c * HW, o);
-            }
-        };
+        load_l<V>(labels + px.i, lab);
         // g_c of the item: a y_c + b for a listed class, 0 for the others
         auto big_g = [&](int c, double (&o)[V]) {
             const int kk = NC > 0 ? kof[NC > 0 ? c : 0] : slot_of(cls, K, c);
@@ -333,16 +265,7 @@ tversky_grad_kernel(const float* __restrict__ logits, const long long* __restric
                 for (int v = 0; v < V; ++v) o[v] = lab[v] == c ? a + bb : bb;
             }
         };
-        float m[V];
-#pragma unroll
-        for (int v = 0; v < V; ++v) m[v] = -INFINITY;
-#pragma unroll NR
-        for (int c = 0; c < CC; ++c) {
-            float l[V];
-            logit(c, l);
-#pragma unroll
-            for (int v = 0; v < V; ++v) m[v] = fmaxf(m[v], l[v]);
-        }
+        px.max_pass(C);
         double se[V], dot[V];
 #pragma unroll
         for (int v = 0; v < V; ++v) se[v] = dot[v] = 0.0;
@@ -350,11 +273,11 @@ tversky_grad_kernel(const float* __restrict__ logits, const long long* __restric
         for (int c = 0; c < CC; ++c) {
             float l[V];
             double g[V];
-            logit(c, l);
+            px.logit(c, l);
             big_g(c, g);
 #pragma unroll
             for (int v = 0; v < V; ++v) {
-                const double e = exp((double)l[v] - (double)m[v]);
+                const double e = exp((double)l[v] - (double)px.m[v]);
                 se[v] += e;
                 dot[v] += e * g[v];
             }
@@ -369,11 +292,11 @@ tversky_grad_kernel(const float* __restrict__ logits, const long long* __restric
         for (int c = 0; c < CC; ++c) {
             float l[V], o[V];
             double g[V];
-            logit(c, l);
+            px.logit(c, l);
             big_g(c, g);
 #pragma unroll
             for (int v = 0; v < V; ++v) {
-                const double s = exp((double)l[v] - (double)m[v]) * inv[v];
+                const double s = exp((double)l[v] - (double)px.m[v]) * inv[v];
                 o[v] = lab[v] != ignore_index ? (float)(s * (g[v] - dot[v])) : 0.f;
             }
             store_f<V>(dp + (long long)c * HW, o);
@@ -394,45 +317,20 @@ focal_kernel(const float* __restrict__ logits, const long long* __restrict__ lab
     double acc = 0.0, den = 0.0;
     for (long long it = blockIdx.x * (long long)blockDim.x + threadIdx.x; it < nitems;
          it += (long long)gridDim.x * blockDim.x) {
-        const long long i = it * V;
-        const long long b = i / HW;
-        const int r = (int)(i - b * HW);
-        const float* lp = logits + b * C * HW + r;
+        Item<NC, V> px(logits, it * V, C, HW);
         long long lab[V];
-        load_l<V>(labels + i, lab);
+        load_l<V>(labels + px.i, lab);
         float pw[V];
 #pragma unroll
         for (int v = 0; v < V; ++v) pw[v] = 1.f;
-        if (pweight) load_f<V>(pweight + i, pw);
+        if (pweight) load_f<V>(pweight + px.i, pw);
         bool ignored[V], bad[V];
 #pragma unroll
         for (int v = 0; v < V; ++v) {
             ignored[v] = lab[v] == ignore_index || pw[v] == 0.f;
             bad[v] = !ignored[v] && (lab[v] < 0 || lab[v] >= C);
         }
-        float reg[NR][V];
-        if (NC > 0) {
-#pragma unroll
-            for (int c = 0; c < NC; ++c) load_f<V>(lp + (long long)c * HW, reg[c]);
-        }
-        auto logit = [&](int c, float (&o)[V]) {
-            if (NC > 0) {
-#pragma unroll
-                for (int v = 0; v < V; ++v) o[v] = reg[NC > 0 ? c : 0][v];
-            } else {
-                load_f<V>(lp + (long long)c * HW, o);
-            }
-        };
-        float m[V];
-#pragma unroll
-        for (int v = 0; v < V; ++v) m[v] = -INFINITY;
-#pragma unroll NR
-        for (int c = 0; c < CC; ++c) {
-            float l[V];
-            logit(c, l);
-#pragma unroll
-            for (int v = 0; v < V; ++v) m[v] = fmaxf(m[v], l[v]);
-        }
+        px.max_pass(C);
         // so: the exponentials of the classes other than the label; ey, dy: the label's exponential and l_y - m
         double so[V], ey[V], dy[V];
 #pragma unroll
@@ -443,10 +341,10 @@ focal_kernel(const float* __restrict__ logits, const long long* __restrict__ lab
 #pragma unroll NR
         for (int c = 0; c < CC; ++c) {
             float l[V];
-            logit(c, l);
+            px.logit(c, l);
 #pragma unroll
             for (int v = 0; v < V; ++v) {
-                const double d = (double)l[v] - (double)m[v];
+                const double d = (double)l[v] - (double)px.m[v];
                 const double e = exp(d);
                 if (lab[v] == c) {
                     ey[v] = e;
@@ -487,16 +385,16 @@ focal_kernel(const float* __restrict__ logits, const long long* __restrict__ lab
             }
             so[v] = q;                                    // (the gradient below needs q, not the sum)
         }
-        if (map) store_f<V>(map + i, li);
+        if (map) store_f<V>(map + px.i, li);
         if (dlogits) {
-            float* dp = dlogits + b * C * HW + r;
+            float* dp = dlogits + px.b * C * HW + px.r;
 #pragma unroll NR
             for (int c = 0; c < CC; ++c) {
                 float l[V], o[V];
-                logit(c, l);
+                px.logit(c, l);
 #pragma unroll
                 for (int v = 0; v < V; ++v) {
-                    const double s = exp((double)l[v] - (double)m[v]) * inv[v];
+                    const double s = exp((double)l[v] - (double)px.m[v]) * inv[v];
                     const double g = lab[v] == c ? -coefv[v] * so[v] : coefv[v] * s;
                     o[v] = ignored[v] ? 0.f : (float)g;
                 }
@@ -505,12 +403,7 @@ focal_kernel(const float* __restrict__ logits, const long long* __restrict__ lab
         }
     }
     if (map) return;
-    acc = block_sum_d(acc, sm);
-    den = block_sum_d(den, sm);
-    if (threadIdx.x == 0) {
-        part[blockIdx.x] = acc;
-        part[gridDim.x + blockIdx.x] = den;
-    }
+    wsdl::store_partials(acc, den, part, sm);
 }
 
 // reduction 0 (mean): loss = sum / denominator (0 / 0 = NaN, as the cross entropy), inv_count = 1 / denominator;
@@ -518,13 +411,8 @@ focal_kernel(const float* __restrict__ logits, const long long* __restrict__ lab
 __global__ void focal_finalize_kernel(const double* __restrict__ part, int blocks, float* __restrict__ loss,
                                       float* __restrict__ inv_count, int reduction) {
     __shared__ double sm[16];
-    double s = 0.0, c = 0.0;
-    for (int i = threadIdx.x; i < blocks; i += blockDim.x) {
-        s += part[i];
-        c += part[blocks + i];
-    }
-    s = block_sum_d(s, sm);
-    c = block_sum_d(c, sm);
+    double s, c;
+    wsdl::sum_partials(part, blocks, sm, s, c);
     if (threadIdx.x == 0) {
         if (reduction == 1) {
             *loss = (float)s;
@@ -536,7 +424,6 @@ __global__ void focal_finalize_kernel(const double* __restrict__ part, int block
     }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 // workgroups per segment: enough to fill the device from one segment, fewer each when there are many
 inline int group_cap(int segments) { return std::max(16, 2048 / std::max(segments, 1)); }
 
@@ -562,61 +449,22 @@ inline size_t sums_bytes(int S, int K) { return (size_t)S * K * 3 * sizeof(doubl
 inline size_t coef_bytes(int S, int K) { return (size_t)S * K * 2 * sizeof(double); }
 inline size_t part_bytes(int S, int K) { return (size_t)S * group_cap(S) * K * 3 * sizeof(double); }
 
-template <int NC>
-void sums_launch(const Geometry& g, hipStream_t s, const float* logits, const long long* labels, const ClassList& cls, int K,
-                 double* part, int C, long long ignore) {
-    if (g.vec)
-        hipLaunchKernelGGL((overlap_sums_kernel<NC, 4>), dim3(g.G, g.S), dim3(kThreads), 0, s, logits, labels, cls, K, part, C,
-                           g.HW, g.seg_items, g.seg_pix, ignore);
-    else
-        hipLaunchKernelGGL((overlap_sums_kernel<NC, 1>), dim3(g.G, g.S), dim3(kThreads), 0, s, logits, labels, cls, K, part, C,
-                           g.HW, g.seg_items, g.seg_pix, ignore);
-}
-
-template <int NC>
-void grad_launch(const Geometry& g, int blocks, hipStream_t s, const float* logits, const long long* labels,
-                 const ClassList& cls, int K, const double* coef, float* dlogits, int C, int per_image, long long ignore) {
-    if (g.vec)
-        hipLaunchKernelGGL((tversky_grad_kernel<NC, 4>), dim3(blocks), dim3(kThreads), 0, s, logits, labels, cls, K, coef,
-                           dlogits, C, g.HW, g.nitems, per_image, ignore);
-    else
-        hipLaunchKernelGGL((tversky_grad_kernel<NC, 1>), dim3(blocks), dim3(kThreads), 0, s, logits, labels, cls, K, coef,
-                           dlogits, C, g.HW, g.nitems, per_image, ignore);
-}
-
-template <int NC>
-void focal_launch(bool vec, int blocks, hipStream_t s, const float* logits, const long long* labels, double* part,
-                  float* dlogits, int C, int HW, long long nitems, double gamma, long long ignore, const float* cw,
-                  const float* pw, float* map) {
-    if (vec)
-        hipLaunchKernelGGL((focal_kernel<NC, 4>), dim3(blocks), dim3(kThreads), 0, s, logits, labels, part, dlogits, C, HW,
-                           nitems, gamma, ignore, cw, pw, map);
-    else
-        hipLaunchKernelGGL((focal_kernel<NC, 1>), dim3(blocks), dim3(kThreads), 0, s, logits, labels, part, dlogits, C, HW,
-                           nitems, gamma, ignore, cw, pw, map);
-}
-
 // the shared front of wsdl_overlap_sums and wsdl_tversky_fwd_bwd: argument checks and the class list
 int check_common(const char* who, const float* logits, const int64_t* labels, const int* class_list, int K, int B, int C, int H,
                  int W, int per_image, ClassList& cls) {
     WSDL_REQUIRE(logits && labels && class_list, "%s: null pointer", who);
     WSDL_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && (long long)H * W < (1LL << 31), "%s: bad shape", who);
     WSDL_REQUIRE(!per_image || B <= kMaxSegments, "%s: B = %d images, supported up to %d with per_image", who, B, kMaxSegments);
-    WSDL_REQUIRE(K >= 1 && K <= kMaxClasses, "%s: K = %d classes, supported 1..%d", who, K, kMaxClasses);
-    for (int j = 0; j < K; ++j) {
-        WSDL_REQUIRE(class_list[j] >= 0 && class_list[j] < C, "%s: class %d is outside [0, %d)", who, class_list[j], C);
-        for (int i = 0; i < j; ++i) WSDL_REQUIRE(class_list[i] != class_list[j], "%s: class %d is listed twice", who, class_list[j]);
-        cls.k[j] = class_list[j];
-    }
-    return WSDL_OK;
+    return wsdl::fill_class_list(who, class_list, K, C, cls);
 }
 
 void launch_sums(const Geometry& g, hipStream_t s, const float* logits, const int64_t* labels, const ClassList& cls, int K,
                  double* part, int C, long long ignore_index) {
     const auto* y = reinterpret_cast<const long long*>(labels);
-    if (C == 2) sums_launch<2>(g, s, logits, y, cls, K, part, C, ignore_index);
-    else if (C == 3) sums_launch<3>(g, s, logits, y, cls, K, part, C, ignore_index);
-    else sums_launch<0>(g, s, logits, y, cls, K, part, C, ignore_index);
+    wsdl::dispatch_item(C, g.vec, [&](auto nc, auto v) {
+        hipLaunchKernelGGL((overlap_sums_kernel<decltype(nc)::value, decltype(v)::value>), dim3(g.G, g.S), dim3(kThreads), 0, s, logits,
+                           y, cls, K, part, C, g.HW, g.seg_items, g.seg_pix, ignore_index);
+    });
 }
 
 }  // namespace
@@ -679,9 +527,10 @@ int wsdl_tversky_fwd_bwd(const float* logits, const int64_t* labels, const int* 
     if (dlogits) {
         const int blocks = (int)std::min<long long>((g.nitems + kThreads - 1) / kThreads, 4096);
         const auto* y = reinterpret_cast<const long long*>(labels);
-        if (C == 2) grad_launch<2>(g, blocks, s, logits, y, cls, K, coef, dlogits, C, per_image, ignore_index);
-        else if (C == 3) grad_launch<3>(g, blocks, s, logits, y, cls, K, coef, dlogits, C, per_image, ignore_index);
-        else grad_launch<0>(g, blocks, s, logits, y, cls, K, coef, dlogits, C, per_image, ignore_index);
+        wsdl::dispatch_item(C, g.vec, [&](auto nc, auto v) {
+            hipLaunchKernelGGL((tversky_grad_kernel<decltype(nc)::value, decltype(v)::value>), dim3(blocks), dim3(kThreads), 0, s,
+                               logits, y, cls, K, coef, dlogits, C, g.HW, g.nitems, per_image, ignore_index);
+        });
         WSDL_LAUNCH_CHECK();
     }
     return WSDL_OK;
@@ -710,9 +559,10 @@ int wsdl_focal_fwd_bwd(const float* logits, const int64_t* labels, float* loss, 
     double* part = static_cast<double*>(ws);
     const auto* y = reinterpret_cast<const long long*>(labels);
     float* map = none ? loss : nullptr;
-    if (C == 2) focal_launch<2>(vec, blocks, s, logits, y, part, dlogits, C, HW, nitems, gamma, ignore_index, class_weight, pixel_weight, map);
-    else if (C == 3) focal_launch<3>(vec, blocks, s, logits, y, part, dlogits, C, HW, nitems, gamma, ignore_index, class_weight, pixel_weight, map);
-    else focal_launch<0>(vec, blocks, s, logits, y, part, dlogits, C, HW, nitems, gamma, ignore_index, class_weight, pixel_weight, map);
+    wsdl::dispatch_item(C, vec, [&](auto nc, auto v) {
+        hipLaunchKernelGGL((focal_kernel<decltype(nc)::value, decltype(v)::value>), dim3(blocks), dim3(kThreads), 0, s, logits, y, part,
+                           dlogits, C, HW, nitems, gamma, ignore_index, class_weight, pixel_weight, map);
+    });
     WSDL_LAUNCH_CHECK();
     if (!none) {
         hipLaunchKernelGGL(focal_finalize_kernel, dim3(1), dim3(kThreads), 0, s, part, blocks, loss, inv_count, reduction);

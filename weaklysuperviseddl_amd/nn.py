@@ -209,7 +209,60 @@ def make_resnet50_stages(replace_stride_with_dilation):
     return conv1, bn1, layers
 
 
-class CrossEntropyLoss(nn.Module):
+class _Criterion(nn.Module):
+    """What the loss criteria below share, so that a launch plan (``plan.host_scalars``) sees them alike.  Every option is a
+    plain attribute and so part of the plan key: changing one records a new plan instead of replaying a stale one; a value that
+    is to change WITHOUT a new plan lives in a one-element device buffer.  Buffers the object fills are allocated anew only
+    when the shape changes, so their addresses - which a plan freezes - stay put; the address of every buffer named in
+    ``_pointers`` is kept in the attribute ``<name>_ptr`` (0 while there is none) and the shape of every one in ``_shapes`` in
+    the string ``<name>_shape`` ("" while there is none), refreshed by ``_refresh_pointers`` - after ``.to(device)``, after a
+    call that may have replaced a buffer (``_adopt``) and before the loss is taken."""
+
+    _pointers = ()
+    _shapes = ()
+
+    def _class_weight(self, weight):
+        """``weight`` (None or a (C,) tensor) as this object's own float32 copy."""
+        if weight is not None and (not torch.is_tensor(weight) or weight.dim() != 1):
+            raise ValueError(f"{type(self).__name__}: weight must be a (C,) tensor")
+        return None if weight is None else weight.detach().to(torch.float32).clone()
+
+    def _refresh_pointers(self):
+        for name in self._pointers:
+            t = getattr(self, name)
+            setattr(self, name + "_ptr", 0 if t is None else t.data_ptr())
+        for name in self._shapes:
+            t = getattr(self, name)
+            setattr(self, name + "_shape", "" if t is None else "x".join(str(d) for d in t.shape))
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)      # .to(device) / .cuda() move the buffers
+        self._refresh_pointers()
+        return out
+
+    def _adopt(self, bufs, names):
+        """After an ``out=bufs`` call of ``ops``: the tensors it created become this object's buffers (``names``: key -> buffer)."""
+        for k, name in names.items():
+            if getattr(self, name) is not bufs[k]:
+                setattr(self, name, bufs[k])
+        self._refresh_pointers()
+
+    def _set_pixel_weight(self, t):
+        """Copy a float32 (B,H,W) map into the ``pixel_weight`` buffer (allocated anew only when the shape changes); None drops it."""
+        if t is None:
+            self.pixel_weight = None
+        else:
+            if not torch.is_tensor(t) or t.dim() != 3:
+                raise ValueError(f"{type(self).__name__}.set_pixel_weight: a (B,H,W) tensor or None")
+            cur = self.pixel_weight
+            if cur is None or cur.shape != t.shape or cur.device != t.device:
+                self.pixel_weight = torch.empty(t.shape, device=t.device, dtype=torch.float32)
+            self.pixel_weight.copy_(t.detach())
+        self._refresh_pointers()
+        return self
+
+
+class CrossEntropyLoss(_Criterion):
     """``torch.nn.CrossEntropyLoss(weight, ignore_index, reduction, label_smoothing)`` on (B,C,H,W) logits and (B,H,W)
     labels, run by the fused cross-entropy kernel (``ops.cross_entropy``), plus a per-pixel confidence weight that lives
     on the device.
@@ -228,40 +281,20 @@ class CrossEntropyLoss(nn.Module):
         loss = train_step(model, optimizer, images, refined, criterion=crit)
     """
 
+    _pointers = ("weight", "pixel_weight")
+    _shapes = ("pixel_weight",)
+
     def __init__(self, weight=None, ignore_index=-100, reduction="mean", label_smoothing=0.0):
         super().__init__()
         ops.check_cross_entropy_options(reduction, label_smoothing)
-        if weight is not None and (not torch.is_tensor(weight) or weight.dim() != 1):
-            raise ValueError("CrossEntropyLoss: weight must be a (C,) tensor")
-        self.register_buffer("weight", None if weight is None else weight.detach().to(torch.float32).clone())
+        self.register_buffer("weight", self._class_weight(weight))
         self.register_buffer("pixel_weight", None, persistent=False)
         self.ignore_index = int(ignore_index)
         self.reduction = reduction
         self.label_smoothing = float(label_smoothing)
         self._refresh_pointers()
 
-    def _refresh_pointers(self):
-        self.weight_ptr = 0 if self.weight is None else self.weight.data_ptr()
-        self.pixel_weight_ptr = 0 if self.pixel_weight is None else self.pixel_weight.data_ptr()
-        self.pixel_weight_shape = "" if self.pixel_weight is None else "x".join(str(d) for d in self.pixel_weight.shape)
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)      # .to(device) / .cuda() move the buffers
-        self._refresh_pointers()
-        return out
-
-    def set_pixel_weight(self, t):
-        if t is None:
-            self.pixel_weight = None
-        else:
-            if not torch.is_tensor(t) or t.dim() != 3:
-                raise ValueError("CrossEntropyLoss.set_pixel_weight: a (B,H,W) tensor or None")
-            cur = self.pixel_weight
-            if cur is None or cur.shape != t.shape or cur.device != t.device:
-                self.pixel_weight = torch.empty(t.shape, device=t.device, dtype=torch.float32)
-            self.pixel_weight.copy_(t.detach())
-        self._refresh_pointers()
-        return self
+    set_pixel_weight = _Criterion._set_pixel_weight
 
     def forward(self, logits, labels):
         self._refresh_pointers()
@@ -274,7 +307,7 @@ class CrossEntropyLoss(nn.Module):
                 f"weight={self.weight is not None}, pixel_weight={None if self.pixel_weight is None else tuple(self.pixel_weight.shape)}")
 
 
-class MinedCrossEntropyLoss(nn.Module):
+class MinedCrossEntropyLoss(_Criterion):
     """Cross entropy over the pixels their own loss selects (``ops.cross_entropy_mined``): ``mode="hard"`` is online hard
     example mining / bootstrapped cross entropy - the pixels whose true-class probability is at most ``thresh``, at least
     ``min_kept`` per image - and ``mode="trim"`` drops the fraction ``drop_frac`` of largest loss, the guard against the
@@ -298,13 +331,14 @@ class MinedCrossEntropyLoss(nn.Module):
         loss = train_step(model, optimizer, images, pseudo_masks, criterion=crit)
     """
 
+    _pointers = ("weight", "pixel_weight", "threshold", "kept", "valid", "selection")
+    _shapes = ("pixel_weight",)
+
     def __init__(self, mode="hard", thresh=0.7, min_kept=0, drop_frac=0.0, scope="batch", weight=None, ignore_index=-100,
                  reduction="mean", label_smoothing=0.0):
         super().__init__()
         ops.check_mining_options(mode, thresh, min_kept, drop_frac, scope, reduction, label_smoothing)
-        if weight is not None and (not torch.is_tensor(weight) or weight.dim() != 1):
-            raise ValueError("MinedCrossEntropyLoss: weight must be a (C,) tensor")
-        self.register_buffer("weight", None if weight is None else weight.detach().to(torch.float32).clone())
+        self.register_buffer("weight", self._class_weight(weight))
         for name in ("pixel_weight", "threshold", "kept", "valid", "selection"):
             self.register_buffer(name, None, persistent=False)
         self.mode = mode
@@ -317,29 +351,7 @@ class MinedCrossEntropyLoss(nn.Module):
         self.label_smoothing = float(label_smoothing)
         self._refresh_pointers()
 
-    def _refresh_pointers(self):
-        for name in ("weight", "pixel_weight", "threshold", "kept", "valid", "selection"):
-            t = getattr(self, name)
-            setattr(self, name + "_ptr", 0 if t is None else t.data_ptr())
-        self.pixel_weight_shape = "" if self.pixel_weight is None else "x".join(str(d) for d in self.pixel_weight.shape)
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        self._refresh_pointers()
-        return out
-
-    def set_pixel_weight(self, t):
-        if t is None:
-            self.pixel_weight = None
-        else:
-            if not torch.is_tensor(t) or t.dim() != 3:
-                raise ValueError("MinedCrossEntropyLoss.set_pixel_weight: a (B,H,W) tensor or None")
-            cur = self.pixel_weight
-            if cur is None or cur.shape != t.shape or cur.device != t.device:
-                self.pixel_weight = torch.empty(t.shape, device=t.device, dtype=torch.float32)
-            self.pixel_weight.copy_(t.detach())
-        self._refresh_pointers()
-        return self
+    set_pixel_weight = _Criterion._set_pixel_weight
 
     def forward(self, logits, labels):
         # (options may have been assigned since the constructor checked them)
@@ -350,10 +362,7 @@ class MinedCrossEntropyLoss(nn.Module):
                                        min_kept=self.min_kept, drop_frac=self.drop_frac, scope=self.scope, weight=self.weight,
                                        label_smoothing=self.label_smoothing, pixel_weight=self.pixel_weight,
                                        reduction=self.reduction, stats=stats)
-        for k, t in stats.items():
-            if getattr(self, k) is not t:
-                setattr(self, k, t)
-        self._refresh_pointers()
+        self._adopt(stats, {k: k for k in stats})
         return loss
 
     def extra_repr(self):
@@ -362,7 +371,7 @@ class MinedCrossEntropyLoss(nn.Module):
                 f"label_smoothing={self.label_smoothing}, weight={self.weight is not None}")
 
 
-class BoundaryAwareCrossEntropyLoss(nn.Module):
+class BoundaryAwareCrossEntropyLoss(_Criterion):
     """Cross entropy that trusts a label map less near its own boundary - where the label noise of a CAM-derived pseudo
     mask sits: every call computes ``ops.boundary_confidence(labels, sigma, floor, value)`` - ``floor + (1 - floor) (1 -
     exp(-d^2 / (2 sigma^2)))`` with ``d`` the Euclidean distance of a pixel to the contour of ``labels == value``, 1 in an
@@ -381,13 +390,14 @@ class BoundaryAwareCrossEntropyLoss(nn.Module):
         loss = train_step(model, optimizer, images, pseudo_masks, criterion=crit)
     """
 
+    _pointers = ("weight", "pixel_weight", "d2_out", "d2_in")
+    _shapes = ("pixel_weight",)
+
     def __init__(self, sigma=3.0, floor=0.0, value=1, weight=None, ignore_index=-100, reduction="mean", label_smoothing=0.0):
         super().__init__()
         ops.check_cross_entropy_options(reduction, label_smoothing)
         ops.check_boundary_confidence_options(sigma, floor)
-        if weight is not None and (not torch.is_tensor(weight) or weight.dim() != 1):
-            raise ValueError("BoundaryAwareCrossEntropyLoss: weight must be a (C,) tensor")
-        self.register_buffer("weight", None if weight is None else weight.detach().to(torch.float32).clone())
+        self.register_buffer("weight", self._class_weight(weight))
         for name in ("pixel_weight", "d2_out", "d2_in"):
             self.register_buffer(name, None, persistent=False)
         self.sigma = float(sigma)
@@ -398,27 +408,13 @@ class BoundaryAwareCrossEntropyLoss(nn.Module):
         self.label_smoothing = float(label_smoothing)
         self._refresh_pointers()
 
-    def _refresh_pointers(self):
-        for name in ("weight", "pixel_weight", "d2_out", "d2_in"):
-            t = getattr(self, name)
-            setattr(self, name + "_ptr", 0 if t is None else t.data_ptr())
-        self.pixel_weight_shape = "" if self.pixel_weight is None else "x".join(str(d) for d in self.pixel_weight.shape)
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        self._refresh_pointers()
-        return out
-
     def forward(self, logits, labels):
         # (options may have been assigned since the constructor checked them)
         ops.check_cross_entropy_options(self.reduction, self.label_smoothing)
         labels = labels.long()
         bufs = {"weight": self.pixel_weight, "out": self.d2_out, "in": self.d2_in}
         ops.boundary_confidence(labels, self.sigma, self.floor, self.value, out=bufs)
-        for k, name in (("weight", "pixel_weight"), ("out", "d2_out"), ("in", "d2_in")):
-            if getattr(self, name) is not bufs[k]:
-                setattr(self, name, bufs[k])
-        self._refresh_pointers()
+        self._adopt(bufs, {"weight": "pixel_weight", "out": "d2_out", "in": "d2_in"})
         return ops.cross_entropy(logits, labels, self.ignore_index, weight=self.weight, label_smoothing=self.label_smoothing,
                                  reduction=self.reduction, pixel_weight=self.pixel_weight)
 
@@ -427,7 +423,7 @@ class BoundaryAwareCrossEntropyLoss(nn.Module):
                 f"reduction={self.reduction!r}, label_smoothing={self.label_smoothing}, weight={self.weight is not None}")
 
 
-class BoundaryLoss(nn.Module):
+class BoundaryLoss(_Criterion):
     """The boundary loss of Kervadec et al. ("Boundary loss for highly unbalanced segmentation", MIDL 2019):
     ``mean(softmax(logits)_c * phi_c)`` over the valid pixels and the listed ``classes``, ``phi_c`` the signed distance map of
     class ``c`` in ``labels`` (``ops.signed_distance_classes``: negative inside the class, positive outside, 0 for an image
@@ -440,6 +436,9 @@ class BoundaryLoss(nn.Module):
     plan freezes stay put; the options (``classes`` as the string ``classes_key``) and every address are plain attributes,
     so ``plan.host_scalars`` puts them into the plan key and changed ``classes`` record a new plan.  ``scale_dev``: an
     optional one-element float32 device tensor that multiplies the loss (``ops.boundary_loss(scale=)``)."""
+
+    _pointers = ("phi", "d2_out", "d2_in", "scale_dev")
+    _shapes = ("phi",)
 
     def __init__(self, classes=(1,), ignore_index=-100):
         super().__init__()
@@ -454,27 +453,13 @@ class BoundaryLoss(nn.Module):
         self.classes_key = ",".join(str(c) for c in self.classes)
         return self
 
-    def _refresh_pointers(self):
-        for name in ("phi", "d2_out", "d2_in", "scale_dev"):
-            t = getattr(self, name)
-            setattr(self, name + "_ptr", 0 if t is None else t.data_ptr())
-        self.phi_shape = "" if self.phi is None else "x".join(str(d) for d in self.phi.shape)
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        self._refresh_pointers()
-        return out
-
     def forward(self, logits, labels):
         # (classes may have been assigned since the constructor checked them)
         self.set_classes(self.classes)
         labels = labels.long()
         bufs = {"phi": self.phi, "out": self.d2_out, "in": self.d2_in}
         ops.signed_distance_classes(labels, self.classes, out=bufs)
-        for k, name in (("phi", "phi"), ("out", "d2_out"), ("in", "d2_in")):
-            if getattr(self, name) is not bufs[k]:
-                setattr(self, name, bufs[k])
-        self._refresh_pointers()
+        self._adopt(bufs, {"phi": "phi", "out": "d2_out", "in": "d2_in"})
         return ops.boundary_loss(logits, self.phi, labels, classes=self.classes, ignore_index=self.ignore_index,
                                  scale=self.scale_dev)
 
@@ -482,7 +467,7 @@ class BoundaryLoss(nn.Module):
         return f"classes={self.classes}, ignore_index={self.ignore_index}"
 
 
-class CrossEntropyBoundaryLoss(nn.Module):
+class CrossEntropyBoundaryLoss(_Criterion):
     """``cross entropy + alpha * boundary loss`` (Kervadec et al., MIDL 2019, combine a regional loss with the boundary term):
     ``ops.cross_entropy(logits, labels, weight=, ignore_index=, label_smoothing=)`` plus ``BoundaryLoss(classes,
     ignore_index)`` scaled by ``alpha``, added by the library's kernels (``ops.fanout`` / ``ops.add_scalars``), so
@@ -499,13 +484,13 @@ class CrossEntropyBoundaryLoss(nn.Module):
             loss = train_step(model, optimizer, images, masks, criterion=crit)
     """
 
+    _pointers = ("weight", "alpha_dev")
+
     def __init__(self, alpha=0.01, classes=(1,), weight=None, ignore_index=-100, label_smoothing=0.0):
         super().__init__()
         ops.check_cross_entropy_options("mean", label_smoothing)
         alpha = self._check_alpha(alpha)
-        if weight is not None and (not torch.is_tensor(weight) or weight.dim() != 1):
-            raise ValueError("CrossEntropyBoundaryLoss: weight must be a (C,) tensor")
-        self.register_buffer("weight", None if weight is None else weight.detach().to(torch.float32).clone())
+        self.register_buffer("weight", self._class_weight(weight))
         self.register_buffer("alpha_dev", torch.tensor([alpha], dtype=torch.float32), persistent=False)
         self.boundary = BoundaryLoss(classes, ignore_index)
         self.ignore_index = int(ignore_index)
@@ -523,15 +508,6 @@ class CrossEntropyBoundaryLoss(nn.Module):
         self.alpha_dev.fill_(self._check_alpha(alpha))
         return self
 
-    def _refresh_pointers(self):
-        self.weight_ptr = 0 if self.weight is None else self.weight.data_ptr()
-        self.alpha_dev_ptr = self.alpha_dev.data_ptr()
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        self._refresh_pointers()
-        return out
-
     def forward(self, logits, labels):
         ops.check_cross_entropy_options("mean", self.label_smoothing)
         self._refresh_pointers()
@@ -547,7 +523,7 @@ class CrossEntropyBoundaryLoss(nn.Module):
                 f"weight={self.weight is not None}")
 
 
-class TverskyLoss(nn.Module):
+class TverskyLoss(_Criterion):
     """The Tversky loss (Salehi et al., MLMI 2017) of ``ops.tversky_loss``: the mean over segments (the images with
     ``per_image``, else the batch) and listed ``classes`` (None: all) of ``(1 - T) ** gamma``, ``T = (I + smooth) / (I + alpha
     FP + beta FN + smooth)`` from the soft intersection, false positives and false negatives of ``softmax(logits)`` against
@@ -560,6 +536,8 @@ class TverskyLoss(nn.Module):
 
         loss = train_step(model, optimizer, images, masks, criterion=wnn.TverskyLoss(alpha=0.3, beta=0.7, gamma=0.75))
     """
+
+    _pointers = ("scale_dev",)
 
     def __init__(self, alpha=0.5, beta=0.5, gamma=1.0, smooth=1.0, classes=None, per_image=False, present_only=False,
                  ignore_index=-100):
@@ -580,14 +558,6 @@ class TverskyLoss(nn.Module):
         self.classes = ops.check_overlap_classes(classes, None, type(self).__name__)
         self.classes_key = "all" if self.classes is None else ",".join(str(c) for c in self.classes)
         return self
-
-    def _refresh_pointers(self):
-        self.scale_dev_ptr = 0 if self.scale_dev is None else self.scale_dev.data_ptr()
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        self._refresh_pointers()
-        return out
 
     def forward(self, logits, labels):
         # (options may have been assigned since the constructor checked them)
@@ -616,46 +586,26 @@ class DiceLoss(TverskyLoss):
                 f"present_only={self.present_only}, ignore_index={self.ignore_index}")
 
 
-class FocalLoss(nn.Module):
+class FocalLoss(_Criterion):
     """The focal loss of Lin et al. (ICCV 2017) in its softmax form (``ops.focal_loss``): per pixel ``weight[y] (1 - s_y) **
     gamma (-log s_y)``, with the class weights, the ``ignore_index``, the reductions and the per-pixel confidence weight of
     ``CrossEntropyLoss`` (``set_pixel_weight``); ``gamma = 0`` is that cross entropy.  Conventions of ``CrossEntropyLoss``:
     the buffers keep their addresses and every option is a plain attribute (``plan.host_scalars``)."""
 
+    _pointers = ("weight", "pixel_weight")
+    _shapes = ("pixel_weight",)
+
     def __init__(self, gamma=2.0, weight=None, ignore_index=-100, reduction="mean"):
         super().__init__()
         ops.check_focal_options(gamma, reduction, "FocalLoss")
-        if weight is not None and (not torch.is_tensor(weight) or weight.dim() != 1):
-            raise ValueError("FocalLoss: weight must be a (C,) tensor")
-        self.register_buffer("weight", None if weight is None else weight.detach().to(torch.float32).clone())
+        self.register_buffer("weight", self._class_weight(weight))
         self.register_buffer("pixel_weight", None, persistent=False)
         self.gamma = float(gamma)
         self.ignore_index = int(ignore_index)
         self.reduction = reduction
         self._refresh_pointers()
 
-    def _refresh_pointers(self):
-        self.weight_ptr = 0 if self.weight is None else self.weight.data_ptr()
-        self.pixel_weight_ptr = 0 if self.pixel_weight is None else self.pixel_weight.data_ptr()
-        self.pixel_weight_shape = "" if self.pixel_weight is None else "x".join(str(d) for d in self.pixel_weight.shape)
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        self._refresh_pointers()
-        return out
-
-    def set_pixel_weight(self, t):
-        if t is None:
-            self.pixel_weight = None
-        else:
-            if not torch.is_tensor(t) or t.dim() != 3:
-                raise ValueError("FocalLoss.set_pixel_weight: a (B,H,W) tensor or None")
-            cur = self.pixel_weight
-            if cur is None or cur.shape != t.shape or cur.device != t.device:
-                self.pixel_weight = torch.empty(t.shape, device=t.device, dtype=torch.float32)
-            self.pixel_weight.copy_(t.detach())
-        self._refresh_pointers()
-        return self
+    set_pixel_weight = _Criterion._set_pixel_weight
 
     def forward(self, logits, labels):
         ops.check_focal_options(self.gamma, self.reduction, "FocalLoss")
@@ -668,7 +618,7 @@ class FocalLoss(nn.Module):
                 f"weight={self.weight is not None}")
 
 
-class CrossEntropyTverskyLoss(nn.Module):
+class CrossEntropyTverskyLoss(_Criterion):
     """``cross entropy + lam * Tversky loss`` - the usual pairing of a pixel loss with a region-overlap loss for imbalanced
     masks: ``ops.cross_entropy(logits, labels, weight=, ignore_index=, label_smoothing=)`` plus ``TverskyLoss(alpha, beta,
     gamma, smooth, classes, per_image, present_only, ignore_index)`` scaled by ``lam``, added by the library's kernels
@@ -681,14 +631,14 @@ class CrossEntropyTverskyLoss(nn.Module):
         loss = train_step(model, optimizer, images, masks, criterion=crit)
     """
 
+    _pointers = ("weight", "lam_dev")
+
     def __init__(self, lam=1.0, alpha=0.5, beta=0.5, gamma=1.0, smooth=1.0, classes=None, per_image=False, present_only=False,
                  weight=None, ignore_index=-100, label_smoothing=0.0):
         super().__init__()
         ops.check_cross_entropy_options("mean", label_smoothing)
         lam = self._check_lam(lam)
-        if weight is not None and (not torch.is_tensor(weight) or weight.dim() != 1):
-            raise ValueError("CrossEntropyTverskyLoss: weight must be a (C,) tensor")
-        self.register_buffer("weight", None if weight is None else weight.detach().to(torch.float32).clone())
+        self.register_buffer("weight", self._class_weight(weight))
         self.register_buffer("lam_dev", torch.tensor([lam], dtype=torch.float32), persistent=False)
         self.tversky = TverskyLoss(alpha, beta, gamma, smooth, classes, per_image, present_only, ignore_index)
         self.ignore_index = int(ignore_index)
@@ -705,15 +655,6 @@ class CrossEntropyTverskyLoss(nn.Module):
         """Write ``lam`` into the device buffer (a stream-ordered fill; the buffer keeps its address)."""
         self.lam_dev.fill_(self._check_lam(lam))
         return self
-
-    def _refresh_pointers(self):
-        self.weight_ptr = 0 if self.weight is None else self.weight.data_ptr()
-        self.lam_dev_ptr = self.lam_dev.data_ptr()
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        self._refresh_pointers()
-        return out
 
     def forward(self, logits, labels):
         ops.check_cross_entropy_options("mean", self.label_smoothing)

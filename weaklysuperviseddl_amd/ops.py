@@ -1710,18 +1710,30 @@ class _SoftmaxCEEx(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         dl, inv = ctx.saved_tensors
+        if not ctx.none and not ctx.keep_zeros:
+            return (_scaled_grad(dl, g, inv),) + (None,) * 7       # upstream gradient x 1 / denominator
         out = torch.empty_like(dl)
         if ctx.none:
             B, Cc, H, W = dl.shape
             check(lib().wsdl_scale_by_pixel(_p(dl), _p(_dense(g, "upstream gradient")), _p(out), B, Cc, H, W, _stream()))
-        else:
+        else:       # cross_entropy_mined: a pixel that is not selected has gradient 0 also when NOTHING is selected (sc = inf)
             sc = torch.empty_like(inv)
-            check(lib().wsdl_mul(_p(_dense(g.reshape(1))), _p(inv), _p(sc), 1, _stream()))      # upstream gradient x 1 / denominator
-            if ctx.keep_zeros:      # cross_entropy_mined: a pixel that is not selected has gradient 0 also when NOTHING is selected (sc = inf)
-                check(lib().wsdl_mining_scale_grad(_p(dl), _p(sc), _p(out), dl.numel(), _stream()))
-            else:
-                check(lib().wsdl_scale_by_device_scalar(_p(dl), _p(sc), _p(out), dl.numel(), _stream()))
+            check(lib().wsdl_mul(_p(_dense(g.reshape(1))), _p(inv), _p(sc), 1, _stream()))
+            check(lib().wsdl_mining_scale_grad(_p(dl), _p(sc), _p(out), dl.numel(), _stream()))
         return out, None, None, None, None, None, None, None
+
+
+def _scaled_grad(dl, g, inv=None):
+    """The backward of a 0-dim loss whose kernel left its gradient ``dl`` on the device: ``dl`` x the upstream gradient ``g``
+    (x ``inv``, the one-element factor a fused kernel left un-applied) - wsdl_mul where there is an ``inv``, then
+    wsdl_scale_by_device_scalar; no host read."""
+    out = torch.empty_like(dl)
+    sc = _dense(g.reshape(1))
+    if inv is not None:
+        g, sc = sc, torch.empty_like(inv)
+        check(lib().wsdl_mul(_p(g), _p(inv), _p(sc), 1, _stream()))
+    check(lib().wsdl_scale_by_device_scalar(_p(dl), _p(sc), _p(out), dl.numel(), _stream()))
+    return out
 
 
 class _PairwiseAffinityLoss(torch.autograd.Function):
@@ -2901,6 +2913,36 @@ def check_boundary_classes(classes, name="boundary_loss"):
     return classes
 
 
+_NO_CLASSES = object()
+
+
+def _logits_labels(name, logits, labels, optional=False, classes=_NO_CLASSES):
+    """The front of the losses on (B,C,H,W) logits and (B,H,W) labels -> (labels, classes): logits a 4-d float32 device tensor,
+    ``classes`` (where the loss has a list; None = all) against C by ``check_overlap_classes`` - a ValueError, raised before
+    anything asks for a device - and labels a (B,H,W) tensor on the logits' device (``optional``: or None), returned detached,
+    contiguous and int64."""
+    if not torch.is_tensor(logits) or logits.dim() != 4:
+        raise WsdlError(f"{name}: logits must be a (B,C,H,W) tensor")
+    B, Cc, H, W = logits.shape
+    if classes is not _NO_CLASSES:
+        classes = check_overlap_classes(classes, Cc, name)
+    _req(logits, f"{name}: logits")
+    if labels is not None or not optional:
+        if not torch.is_tensor(labels) or tuple(labels.shape) != (B, H, W) or labels.device != logits.device:
+            raise WsdlError(f"{name}: labels must be a {(B, H, W)} tensor on {logits.device}" + (" or None" if optional else ""))
+        labels = _req(labels, f"{name}: labels", torch.int64).detach().contiguous()
+    return labels, classes
+
+
+def _device_scalar(name, scale, device):
+    """``scale`` of a loss: None, or a one-element float32 tensor on ``device`` (returned detached)."""
+    if scale is None:
+        return None
+    if not torch.is_tensor(scale) or scale.dtype != torch.float32 or scale.numel() != 1 or scale.device != device:
+        raise WsdlError(f"{name}: scale must be a one-element float32 tensor on {device} or None")
+    return scale.detach()
+
+
 def signed_distance(labels, value=1, *, out=None):
     """float32 (B,H,W) signed distance map of the class ``labels == value`` (Kervadec et al., MIDL 2019): with the two
     Euclidean planes of ``edt(labels, value, border=False)``, ``phi = +sqrt(d2_in)`` on OUT pixels and ``phi = -(sqrt(d2_out)
@@ -2938,7 +2980,7 @@ def signed_distance_classes(labels, classes, *, out=None):
 
 class _BoundaryLoss(torch.autograd.Function):
     """wsdl_boundary_loss_fwd_bwd: the loss and its un-normalised gradient in one kernel; the backward multiplies by the
-    upstream gradient and the factor the kernel left on the device, as ``_SoftmaxCEEx.backward`` does."""
+    upstream gradient and the factor scale / (K N) the kernel left on the device (``_scaled_grad``)."""
 
     @staticmethod
     def forward(ctx, logits, phi, labels, classes, ignore_index, scale):
@@ -2959,11 +3001,7 @@ class _BoundaryLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         dl, inv = ctx.saved_tensors
-        out = torch.empty_like(dl)
-        sc = torch.empty_like(inv)
-        check(lib().wsdl_mul(_p(_dense(g.reshape(1))), _p(inv), _p(sc), 1, _stream()))      # upstream gradient x scale / (K N)
-        check(lib().wsdl_scale_by_device_scalar(_p(dl), _p(sc), _p(out), dl.numel(), _stream()))
-        return out, None, None, None, None, None
+        return _scaled_grad(dl, g, inv), None, None, None, None, None
 
 
 def boundary_loss(logits, phi, labels=None, *, classes=(1,), ignore_index=-100, scale=None):
@@ -2980,27 +3018,16 @@ def boundary_loss(logits, phi, labels=None, *, classes=(1,), ignore_index=-100, 
     None.  A class outside ``classes`` contributes through the softmax only.  The gradient flows into ``logits`` only.  The
     softmax and the products run in double and every output is rounded once; bitwise reproducible."""
     classes = check_boundary_classes(classes)
-    if not torch.is_tensor(logits) or logits.dim() != 4:
-        raise WsdlError("boundary_loss: logits must be a (B,C,H,W) tensor")
+    labels, classes = _logits_labels("boundary_loss", logits, labels, optional=True, classes=classes)
     B, Cc, H, W = logits.shape
     K = len(classes)
-    if max(classes) >= Cc:
-        raise ValueError(f"boundary_loss: classes {classes!r} must be below C = {Cc}")
-    _req(logits, "boundary_loss: logits")
     if not torch.is_tensor(phi) or phi.dtype != torch.float32 or phi.device != logits.device or \
             tuple(phi.shape) not in (((B, H, W), (B, 1, H, W)) if K == 1 else ((B, K, H, W),)):
         raise WsdlError(f"boundary_loss: phi must be a float32 {(B, K, H, W)} tensor on {logits.device}"
                         + (f" (or {(B, H, W)})" if K == 1 else ""))
     phi = phi.detach()
     phi = phi if phi.is_contiguous() else phi.contiguous()
-    if labels is not None:
-        if not torch.is_tensor(labels) or tuple(labels.shape) != (B, H, W) or labels.device != logits.device:
-            raise WsdlError(f"boundary_loss: labels must be a {(B, H, W)} tensor on {logits.device} or None")
-        labels = _req(labels, "boundary_loss: labels", torch.int64).detach().contiguous()
-    if scale is not None:
-        if not torch.is_tensor(scale) or scale.dtype != torch.float32 or scale.numel() != 1 or scale.device != logits.device:
-            raise WsdlError(f"boundary_loss: scale must be a one-element float32 tensor on {logits.device} or None")
-        scale = scale.detach()
+    scale = _device_scalar("boundary_loss", scale, logits.device)
     return _BoundaryLoss.apply(logits, phi, labels, classes, int(ignore_index), scale)
 
 
@@ -3042,18 +3069,6 @@ def check_overlap_classes(classes, C=None, name="tversky_loss"):
     return classes
 
 
-def _overlap_inputs(logits, labels, classes, name):
-    if not torch.is_tensor(logits) or logits.dim() != 4:
-        raise WsdlError(f"{name}: logits must be a (B,C,H,W) tensor")
-    B, Cc, H, W = logits.shape
-    classes = check_overlap_classes(classes, Cc, name)
-    _req(logits, f"{name}: logits")
-    if not torch.is_tensor(labels) or tuple(labels.shape) != (B, H, W) or labels.device != logits.device:
-        raise WsdlError(f"{name}: labels must be a {(B, H, W)} tensor on {logits.device}")
-    labels = _req(labels, f"{name}: labels", torch.int64).detach().contiguous()
-    return labels, classes
-
-
 def overlap_sums(logits, labels, *, classes=None, ignore_index=-100, per_image=False, out=None):
     """float64 (segments, K, 3) on the device - segments = B with ``per_image``, else 1: for the listed class ``c`` and
     ``s = softmax(logits)``, ``[..., 0] = I = sum s_c y_c``, ``[..., 1] = P = sum over valid pixels of s_c`` and ``[..., 2] =
@@ -3061,7 +3076,7 @@ def overlap_sums(logits, labels, *, classes=None, ignore_index=-100, per_image=F
     soft Dice, Tversky and their relatives are made of (wsdl_overlap_sums: two launches, double accumulation in fixed order,
     bitwise reproducible, no host read).  ``classes``: None for all C, or up to 32 distinct ints.  ``out``: a dict whose
     ``"sums"`` tensor is reused."""
-    labels, classes = _overlap_inputs(logits, labels, classes, "overlap_sums")
+    labels, classes = _logits_labels("overlap_sums", logits, labels, classes=classes)
     logits = _dense(logits.detach(), "logits")
     B, Cc, H, W = logits.shape
     K, S = len(classes), B if per_image else 1
@@ -3095,9 +3110,7 @@ class _TverskyLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (dl,) = ctx.saved_tensors
-        out = torch.empty_like(dl)
-        check(lib().wsdl_scale_by_device_scalar(_p(dl), _p(_dense(g.reshape(1))), _p(out), dl.numel(), _stream()))
-        return (out,) + (None,) * 10
+        return (_scaled_grad(dl, g),) + (None,) * 10
 
 
 def tversky_loss(logits, labels, *, alpha=0.5, beta=0.5, gamma=1.0, smooth=1.0, classes=None, per_image=False,
@@ -3117,11 +3130,8 @@ def tversky_loss(logits, labels, *, alpha=0.5, beta=0.5, gamma=1.0, smooth=1.0, 
     without a new launch plan) or None.  The gradient flows into ``logits`` only.  Everything runs in double and is rounded
     once; three launches, bitwise reproducible, no host read."""
     check_tversky_options(alpha, beta, gamma, smooth)
-    labels, classes = _overlap_inputs(logits, labels, classes, "tversky_loss")
-    if scale is not None:
-        if not torch.is_tensor(scale) or scale.dtype != torch.float32 or scale.numel() != 1 or scale.device != logits.device:
-            raise WsdlError(f"tversky_loss: scale must be a one-element float32 tensor on {logits.device} or None")
-        scale = scale.detach()
+    labels, classes = _logits_labels("tversky_loss", logits, labels, classes=classes)
+    scale = _device_scalar("tversky_loss", scale, logits.device)
     return _TverskyLoss.apply(logits, labels, classes, float(alpha), float(beta), float(gamma), float(smooth), bool(per_image),
                               bool(present_only), int(ignore_index), scale)
 
@@ -3136,7 +3146,7 @@ def dice_loss(logits, labels, *, smooth=1.0, classes=None, per_image=False, pres
 
 
 class _FocalLoss(torch.autograd.Function):
-    """wsdl_focal_fwd_bwd: the loss and its un-normalised gradient in one kernel; the backward is ``_SoftmaxCEEx.backward``'s."""
+    """wsdl_focal_fwd_bwd: the loss and its un-normalised gradient in one kernel; the backward as in ``_SoftmaxCEEx``."""
 
     @staticmethod
     def forward(ctx, logits, labels, gamma, ignore_index, weight, pixel_weight, reduction):
@@ -3156,14 +3166,11 @@ class _FocalLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         dl, inv = ctx.saved_tensors
+        if not ctx.none:
+            return (_scaled_grad(dl, g, inv),) + (None,) * 6       # upstream gradient x 1 / denominator
         out = torch.empty_like(dl)
-        if ctx.none:
-            B, Cc, H, W = dl.shape
-            check(lib().wsdl_scale_by_pixel(_p(dl), _p(_dense(g, "upstream gradient")), _p(out), B, Cc, H, W, _stream()))
-        else:
-            sc = torch.empty_like(inv)
-            check(lib().wsdl_mul(_p(_dense(g.reshape(1))), _p(inv), _p(sc), 1, _stream()))      # upstream gradient x 1 / denominator
-            check(lib().wsdl_scale_by_device_scalar(_p(dl), _p(sc), _p(out), dl.numel(), _stream()))
+        B, Cc, H, W = dl.shape
+        check(lib().wsdl_scale_by_pixel(_p(dl), _p(_dense(g, "upstream gradient")), _p(out), B, Cc, H, W, _stream()))
         return out, None, None, None, None, None, None
 
 
@@ -3177,13 +3184,8 @@ def focal_loss(logits, labels, *, gamma=2.0, weight=None, ignore_index=-100, red
     ``gamma`` >= 0.  ``1 - s_y`` is formed as the sum of the other classes' probabilities and the result is finite for every
     finite logit; everything runs in double and is rounded once.  The gradient flows into ``logits`` only."""
     check_focal_options(gamma, reduction)
-    if not torch.is_tensor(logits) or logits.dim() != 4:
-        raise WsdlError("focal_loss: logits must be a (B,C,H,W) tensor")
+    labels, _ = _logits_labels("focal_loss", logits, labels)
     B, Cc, H, W = logits.shape
-    _req(logits, "focal_loss: logits")
-    if not torch.is_tensor(labels) or tuple(labels.shape) != (B, H, W) or labels.device != logits.device:
-        raise WsdlError(f"focal_loss: labels must be a {(B, H, W)} tensor on {logits.device}")
-    labels = _req(labels, "focal_loss: labels", torch.int64).detach().contiguous()
     for t, name, shape in ((weight, "weight", (Cc,)), (pixel_weight, "pixel_weight", (B, H, W))):
         if t is None:
             continue
