@@ -906,6 +906,51 @@ int wsdl_focal_fwd_bwd(const float* logits, const int64_t* labels, float* loss, 
                        int H, int W, double gamma, long long ignore_index, const float* class_weight,
                        const float* pixel_weight, int reduction, void* ws, size_t ws_bytes, wsdl_stream_t stream);
 
+/* ---- connected components of label maps, seeded region growing (csrc/components_grid.hip) - the reference has no such step -
+ * wsdl_label_components: no counterpart in the reference (its only labelling is keep_largest's, one binary mask at a time).
+ *   labels (B,H,W) int64, never written; comp (B,H,W) int32.  Two pixels of one image belong together if they are connected
+ *   through pixels of the SAME label value, connectivity 8 or 4.  comp[p] = the raster index y W + x, within the image, of the
+ *   first pixel of p's component in raster order (scipy.ndimage.label's order made position-independent); -1 where
+ *   has_background is 1 and labels[p] == background (has_background 0: every value forms components).  area (optional,
+ *   (B,H,W) int32, not comp): the pixel count of p's component at every pixel, 0 on background.
+ *   Tiles of 64 x 32 pixels are labelled in LDS by one workgroup each, a second launch unites across the tile seams with a
+ *   lock-free union (integer compare-and-swap: the larger root under the smaller, so parents only decrease and a component's
+ *   root is its smallest raster index whatever the interleaving), a third replaces every parent by its root and a fourth
+ *   spreads the areas.  No workgroup waits for another one, no host read, every parameter by value (a launch plan may hold
+ *   the call), integer atomics only: bitwise reproducible.  ws: wsdl_label_components_workspace bytes, 4-byte aligned; its first
+ *   int32 is the ERROR WORD: 0 after a complete run, 1 if a union gave up after 2^20 lost races (comp is then not valid) - the
+ *   union loop is bounded instead of trusted.  Refused before any launch, without touching a device: non-positive sizes,
+ *   B H W > 2^31 - 1 (the workspace query returns 0 for them), a connectivity other than 4 or 8.
+ * wsdl_seeded_region_growing: no counterpart in the reference.  Deep seeded region growing (Huang et al., CVPR 2018) with a
+ *   single-label seed map.  scores (B,C,H,W) fp32 (only compared), seeds (B,H,W) int64 (a value in [0,C) is a seed of that
+ *   class, anything else is unseeded), thresh (C) fp32 either on the host (thresh_host: copied into the launch by value,
+ *   C <= WSDL_SRG_THRESH_BY_VALUE) or in a device buffer (thresh_dev) - exactly one of the two; present (optional, (B,C) uint8):
+ *   0 = a class the image cannot contain (null: all present).
+ *     a(p)  = the first index of the largest score over the present classes
+ *     p is a CANDIDATE of class a(p) iff scores[a(p)] > thresh[a(p)] (float32, strict); a NaN among the present scores of p, or
+ *             no present class: a candidate of nothing
+ *     the candidate map is labelled as above (8-connected, same class, non-candidates as background); a component GROWS iff
+ *     one of its pixels carries a seed of the component's own class (candidates conduct also under a foreign seed)
+ *     grown[p] (int64) = the seed where there is one (never overwritten), else the class of a grown component, else ignore_index
+ *     counts[b,c] (int64 (B,C), on the device) = the pixels of image b with grown == c
+ *   The seed flag per root is a plain byte store of 1 by every writer; counts are integer atomics: bitwise reproducible.  Six
+ *   launches and a memset (one launch fewer for an image of one tile), no host read.  ws: wsdl_seeded_region_growing_workspace
+ *   bytes, 16-byte aligned; its first int32 is the error word of the labelling.  Inputs are never written.
+ * wsdl_balanced_seed_weights: no counterpart in the reference.  weights (B,H,W) fp32 from grown and counts: a pixel with a
+ *   label l in [0,C) gets float(1.0 / double(B n)) - the division in double, rounded once - with n = counts[b,g] summed over
+ *   the pixel's group g: balance 0 (fg_bg) the groups are {0} and {1..C-1}, 1 (class) every class by itself; 2 (none) the
+ *   weight is 1.  Any other label: 0; a group without a pixel: 0 (the paper divides by zero there).  One launch. */
+#define WSDL_SRG_THRESH_BY_VALUE 32
+size_t wsdl_label_components_workspace(int B, int H, int W);
+int wsdl_label_components(const int64_t* labels, int B, int H, int W, int connectivity, int has_background, long long background,
+                          int* comp, int* area, void* ws, size_t ws_bytes, wsdl_stream_t stream);
+size_t wsdl_seeded_region_growing_workspace(int B, int C, int H, int W);
+int wsdl_seeded_region_growing(const float* scores, const int64_t* seeds, const float* thresh_host, const float* thresh_dev,
+                               const uint8_t* present, int B, int C, int H, int W, long long ignore_index, int64_t* grown,
+                               long long* counts, void* ws, size_t ws_bytes, wsdl_stream_t stream);
+int wsdl_balanced_seed_weights(const int64_t* grown, const long long* counts, int B, int C, int H, int W, int balance, float* weights,
+                               wsdl_stream_t stream);
+
 /* ---- refine_pseudo_mask inner step (TraditionalModel/AlternatingDirectionCutLoss.py:736-757) -
  * KL(softmax(X) || S) with log(X+1e-8), reduction 'batchmean', and its gradient wrt softmax(X). */
 int wsdl_kl_div_fwd_bwd(const float* xn, const float* s, float* loss, float* dxn, size_t n, int batch,

@@ -53,6 +53,19 @@ def keep_largest_batched(masks):
     return ops.keep_largest_batched(masks)
 
 
+def seeds_from_cam(cam, lo, hi, ignore_index=255):
+    """Seeds for ``nn.SeededRegionGrowingLoss`` from a CAM in [0, 1] (the reference has no such step): int64, 1 where
+    ``cam >= hi`` (sure foreground), 0 where ``cam <= lo`` (sure background), ``ignore_index`` between - and at a NaN.
+    Plain tensor operations on the CAM's device.  Seeds that go through ``train_step`` need a negative ``ignore_index``
+    (it clamps its masks to at most 1, as the reference does)."""
+    if not lo < hi:
+        raise ValueError(f"seeds_from_cam: lo {lo!r} must be below hi {hi!r}")
+    cam = torch.as_tensor(cam)
+    seeds = torch.full(cam.shape, int(ignore_index), dtype=torch.int64, device=cam.device)
+    seeds = torch.where(cam <= lo, torch.zeros_like(seeds), seeds)
+    return torch.where(cam >= hi, torch.ones_like(seeds), seeds)
+
+
 def _to_png_u8(t):
     """torchvision.utils.save_image's quantisation: mul(255).add_(0.5).clamp_(0, 255) -> uint8, HWC."""
     return t.mul(255).add(0.5).clamp(0, 255).permute(1, 2, 0).to(torch.uint8).cpu().numpy()

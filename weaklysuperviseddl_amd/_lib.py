@@ -134,6 +134,11 @@ SIGNATURES = {
     "wsdl_overlap_sums": (_i, [_vp, _vp, C.POINTER(_i), _i, _vp, _i, _i, _i, _i, _i, _ll, _vp, _sz, _vp]),
     "wsdl_tversky_fwd_bwd": (_i, [_vp, _vp, C.POINTER(_i), _i, _vp, _vp, _vp, _vp] + [C.c_double] * 4 + [_i] * 6 + [_ll, _vp, _sz, _vp]),
     "wsdl_focal_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, _ll, _vp, _vp, _i, _vp, _sz, _vp]),
+    "wsdl_label_components_workspace": (_sz, [_i, _i, _i]),
+    "wsdl_label_components": (_i, [_vp, _i, _i, _i, _i, _i, _ll, _vp, _vp, _vp, _sz, _vp]),
+    "wsdl_seeded_region_growing_workspace": (_sz, [_i, _i, _i, _i]),
+    "wsdl_seeded_region_growing": (_i, [_vp, _vp, C.POINTER(_f), _vp, _vp, _i, _i, _i, _i, _ll, _vp, _vp, _vp, _sz, _vp]),
+    "wsdl_balanced_seed_weights": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "wsdl_kl_div_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, _sz, _vp]),
     "wsdl_kl_div_per_image_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _sz, _vp, _sz, _vp]),
     "wsdl_refine_combine": (_i, [_vp, _vp, _vp, _vp, _f, _f, _vp, _i, _sz, _vp]),

@@ -670,6 +670,89 @@ class CrossEntropyTverskyLoss(_Criterion):
         return (f"{self.tversky.extra_repr()}, label_smoothing={self.label_smoothing}, weight={self.weight is not None}")
 
 
+class SeededRegionGrowingLoss(_Criterion):
+    """The seeding loss of deep seeded region growing (DSRG; Huang et al., CVPR 2018): the ``labels`` of a call are SEEDS - the
+    few pixels a CAM is sure of, a value in [0,C) per seeded pixel and anything else where there is none
+    (``PsuedoMasks.seeds_from_cam``) - and on every call the network's own prediction grows them: ``ops.softmax_channels`` of
+    the detached logits, ``ops.seeded_region_growing`` with the thresholds ``thresh`` (a number, a ``(bg, fg)`` pair - the
+    paper's 0.99 / 0.85 - or one number per class), ``ops.balanced_seed_weights`` and then the fused cross entropy against the
+    grown labels, ``ops.cross_entropy(logits, grown, ignore_index, reduction="sum", pixel_weight=)`` (``balance="none"``:
+    ``reduction="mean"`` with weights of one).  ``balance="fg_bg"`` is the paper's ``-1/|S_bg| sum log H - 1/|S_fg| sum log H``,
+    averaged over the batch; ``"class"`` balances every class by itself.  The grown labels are constants, as in the paper: the
+    gradient reaches the logits through the cross entropy only.  ``weight``: class weights of the cross entropy.
+
+    Conventions of ``CrossEntropyLoss``: ``grown`` (int64 (B,H,W)), ``counts`` (int64 (B,C)), ``pixel_weight`` (float32) and
+    ``thresh`` (float32 (C,)) are buffers of this object, filled by every call and allocated anew only when the shape changes,
+    so the addresses a launch plan freezes stay put; every option and every address is a plain attribute, so
+    ``plan.host_scalars`` puts them into the plan key and another ``balance`` records a new plan.  The thresholds live in the
+    device buffer and are read by the kernel: ``set_thresh(...)`` writes it WITHOUT a new plan (a threshold schedule replays ONE
+    plan).  Everything is a launch of the library without a host read.
+
+    ``train_step`` clamps its masks to at most 1 as the reference does, so seeds that go through it mark "unseeded" with a
+    NEGATIVE value (``seeds_from_cam(cam, lo, hi, ignore_index=-100)``); ``ignore_index`` here is what ``grown`` holds at the
+    pixels nothing reached, any value outside [0,C).
+
+        crit = wnn.SeededRegionGrowingLoss(thresh=(0.99, 0.85)).to(device)
+        seeds = PsuedoMasks.seeds_from_cam(cam, 0.05, 0.6, ignore_index=-100)
+        loss = train_step(model, optimizer, images, seeds, criterion=crit)
+    """
+
+    _pointers = ("weight", "pixel_weight", "grown", "counts", "thresh")
+    _shapes = ("pixel_weight", "thresh")
+
+    def __init__(self, thresh=(0.99, 0.85), balance="fg_bg", ignore_index=255, weight=None):
+        super().__init__()
+        ops.check_balance(balance, "SeededRegionGrowingLoss")
+        ops.srg_thresholds(thresh, self._spec_len(thresh))  # (its type; the count is checked against C at the first call)
+        self.register_buffer("weight", self._class_weight(weight))
+        for name in ("pixel_weight", "grown", "counts", "thresh"):
+            self.register_buffer(name, None, persistent=False)
+        self._thresh_spec = [thresh]                       # (a list: not a host scalar of the plan key - the values live on the device)
+        self.balance = balance
+        self.ignore_index = int(ignore_index)
+        self._refresh_pointers()
+
+    @staticmethod
+    def _spec_len(thresh):
+        return len(thresh) if isinstance(thresh, (tuple, list)) else 2
+
+    def set_thresh(self, thresh):
+        """Write the thresholds into the device buffer (a stream-ordered copy; the buffer keeps its address)."""
+        ops.srg_thresholds(thresh, self._spec_len(thresh) if self.thresh is None else self.thresh.numel())
+        self._thresh_spec = [thresh]
+        if self.thresh is not None:
+            self._write_thresh()
+        return self
+
+    def _write_thresh(self):
+        vals = ops.srg_thresholds(self._thresh_spec[0], self.thresh.numel())
+        self.thresh.copy_(torch.tensor(vals, dtype=torch.float32))
+
+    def forward(self, logits, labels):
+        # (options may have been assigned since the constructor checked them)
+        ops.check_balance(self.balance, "SeededRegionGrowingLoss")
+        if not torch.is_tensor(logits) or logits.dim() != 4:
+            raise ValueError("SeededRegionGrowingLoss: logits must be a (B,C,H,W) tensor")
+        B, Cc, H, W = logits.shape
+        if self.thresh is None or self.thresh.numel() != Cc or self.thresh.device != logits.device:
+            ops.srg_thresholds(self._thresh_spec[0], Cc)
+            self.thresh = torch.empty(Cc, device=logits.device, dtype=torch.float32)
+            self._write_thresh()
+        if self.pixel_weight is None or tuple(self.pixel_weight.shape) != (B, H, W) or self.pixel_weight.device != logits.device:
+            self.pixel_weight = torch.empty((B, H, W), device=logits.device, dtype=torch.float32)
+        bufs = {"grown": self.grown, "counts": self.counts}
+        ops.seeded_region_growing(ops.softmax_channels(logits.detach()), labels.long(), self.thresh,
+                                  ignore_index=self.ignore_index, out=bufs)
+        self._adopt(bufs, {"grown": "grown", "counts": "counts"})
+        ops.balanced_seed_weights(self.grown, self.counts, balance=self.balance, out=self.pixel_weight)
+        return ops.cross_entropy(logits, self.grown, self.ignore_index, weight=self.weight,
+                                 reduction="mean" if self.balance == "none" else "sum", pixel_weight=self.pixel_weight)
+
+    def extra_repr(self):
+        return (f"thresh={self._thresh_spec[0]!r}, balance={self.balance!r}, ignore_index={self.ignore_index}, "
+                f"weight={self.weight is not None}")
+
+
 class PAMR(nn.Module):
     """Pixel-adaptive mask refinement (Araslanov & Roth, CVPR 2020) as a module without parameters: ``forward(images,
     scores)`` is ``ops.pamr(images, scores, num_iter, dilations)`` - scores (B,C,H,W) propagated ``num_iter`` times over

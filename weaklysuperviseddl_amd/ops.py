@@ -3397,6 +3397,157 @@ def keep_largest_batched(masks):
     return out.view(m.shape)
 
 
+SRG_THRESH_BY_VALUE = 32               # WSDL_SRG_THRESH_BY_VALUE: thresholds that travel inside the launch
+_SRG_BALANCES = {"fg_bg": 0, "class": 1, "none": 2}
+
+
+def check_connectivity(connectivity, name="label_components"):
+    """ValueError unless ``connectivity`` is the int 4 or 8 (no device needed)."""
+    if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or int(connectivity) not in (4, 8):
+        raise ValueError(f"{name}: connectivity {connectivity!r}: 4 or 8")
+    return int(connectivity)
+
+
+def check_components_geometry(B, H, W, name="label_components"):
+    """ValueError for an empty map or one of more than 2^31 - 1 pixels (what the library refuses; no device needed)."""
+    if min(B, H, W) <= 0 or B * H * W > 2 ** 31 - 1:
+        raise ValueError(f"{name}: (B,H,W) = {(B, H, W)}: positive sizes with B H W <= 2^31 - 1")
+
+
+def _error_word(out, ws):
+    if out is not None:
+        out["error"] = ws[:4].view(torch.int32)
+
+
+def label_components(labels, *, background=None, connectivity=8, want_area=False, out=None):
+    """Connected components of int64 device label maps (B,H,W) (a bool / uint8 mask is converted): two pixels of an image
+    belong together if they are connected through pixels of the SAME value, ``connectivity`` 8 or 4.  Returns ``comp``, int32
+    (B,H,W): at every pixel the raster index ``y * W + x`` of the first pixel of its component - scipy's label order made
+    position-independent - and -1 where ``labels == background`` (None: every value forms components); with
+    ``want_area=True`` returns ``(comp, area)``, ``area`` int32 (B,H,W) the pixel count of the pixel's component (0 on
+    background).
+
+    Many workgroups per image (wsdl_label_components: tiles in LDS, a lock-free union across the tile seams, a flatten pass):
+    three launches, four with areas, integer atomics only, no host read, bitwise reproducible - a launch plan can hold the
+    call.  ``ops.keep_largest_batched`` keeps its own one-workgroup-per-mask kernel.  ``out``: a dict whose ``"comp"`` /
+    ``"area"`` tensors receive the maps (created there when missing or of another shape); ``out["error"]`` then views the
+    library's error word in the scratch buffer (int32: 0 unless a union gave up; valid until the next call that uses scratch)."""
+    connectivity = check_connectivity(connectivity)
+    if background is not None:
+        background = _int_option(background, "label_components: background")
+    labels = _edt_labels(labels, "label_components")
+    B, H, W = labels.shape
+    check_components_geometry(B, H, W)
+    comp = _out_tensor(out, "comp", (B, H, W), torch.int32, labels.device)
+    area = _out_tensor(out, "area", (B, H, W), torch.int32, labels.device) if want_area else None
+    ws = workspace(_ws_bytes("wsdl_label_components_workspace", B, H, W), labels.device)
+    check(lib().wsdl_label_components(_p(labels), B, H, W, connectivity, int(background is not None), background or 0, _p(comp),
+                                      _p(area), _p(ws), ws.numel(), _stream()))
+    _error_word(out, ws)
+    return (comp, area) if want_area else comp
+
+
+def srg_thresholds(thresh, C):
+    """``thresh`` of seeded region growing as a list of C floats: a number, a ``(bg, fg)`` pair - ``bg`` for class 0, ``fg`` for
+    the rest (the paper: 0.99 / 0.85) - or C numbers.  ValueError otherwise (no device needed)."""
+    def num(v):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or v != v:
+            raise ValueError(f"seeded_region_growing: thresh {thresh!r}: a number, a (bg, fg) pair or {C} numbers, none NaN")
+        return float(v)
+    if isinstance(thresh, (tuple, list)):
+        vals = [num(v) for v in thresh]
+        if len(vals) == 2:
+            return [vals[0]] + [vals[1]] * (C - 1)
+        if len(vals) == C:
+            return vals
+        raise ValueError(f"seeded_region_growing: thresh {thresh!r}: a number, a (bg, fg) pair or {C} numbers")
+    return [num(thresh)] * C
+
+
+def seeded_region_growing(scores, seeds, thresh, *, present=None, ignore_index=255, out=None):
+    """Deep seeded region growing (Huang et al., CVPR 2018; the reference has no such step) on the device.  ``scores``
+    (B,C,H,W) float32, usually softmax probabilities - they are only compared; ``seeds`` (B,H,W) int64: a value in [0,C) is a
+    seed of that class, anything else is unseeded; ``thresh``: a float32 (C,) DEVICE tensor (read by the kernel: its values may
+    change under a launch plan), or a number / a ``(bg, fg)`` pair / C numbers (``srg_thresholds``), which travel by value;
+    ``present``: optional (B,C) uint8 / bool device tensor, 0 = a class the image cannot contain.
+
+    A pixel is a candidate of the first class of largest score among the present ones if that score is > the class's
+    threshold (float32, strict; a NaN score: no candidate).  The candidate map is labelled (``label_components``'s kernels,
+    8-connected, same class) and a component grows iff one of its pixels carries a seed of the component's own class.
+    Returns ``(grown, counts)``: ``grown`` int64 (B,H,W) = the seed where there is one (seeds are never overwritten), else the
+    class of a grown component, else ``ignore_index``; ``counts`` int64 (B,C), the per-image pixels of each class in
+    ``grown``, left on the device.  Six launches and a memset, integer atomics only, no host read, bitwise reproducible; the
+    inputs are never written.  ``out``: a dict whose ``"grown"`` / ``"counts"`` tensors are filled (created when missing or of
+    another shape); ``out["error"]`` then views the labelling's error word (see ``label_components``)."""
+    if not torch.is_tensor(scores) or scores.dim() != 4:
+        raise WsdlError("seeded_region_growing: scores must be a (B,C,H,W) tensor")
+    B, Cc, H, W = scores.shape
+    thresh_dev = thresh_host = None
+    if torch.is_tensor(thresh):
+        if thresh.dtype != torch.float32 or tuple(thresh.shape) != (Cc,):
+            raise WsdlError(f"seeded_region_growing: a thresh tensor must be float32 {(Cc,)}")
+    else:
+        vals = srg_thresholds(thresh, Cc)
+    ignore_index = _int_option(ignore_index, "seeded_region_growing: ignore_index")
+    check_components_geometry(B, H, W, "seeded_region_growing")
+    scores = _dense(scores.detach(), "seeded_region_growing: scores")
+    dev = scores.device
+    if not torch.is_tensor(seeds) or tuple(seeds.shape) != (B, H, W) or seeds.device != dev:
+        raise WsdlError(f"seeded_region_growing: seeds must be a {(B, H, W)} tensor on {dev}")
+    seeds = _req(seeds, "seeded_region_growing: seeds", torch.int64).detach().contiguous()
+    if torch.is_tensor(thresh):
+        if thresh.device != dev:
+            raise WsdlError(f"seeded_region_growing: thresh is on {thresh.device}, the scores on {dev}")
+        thresh_dev = thresh.detach().contiguous()
+    elif Cc <= SRG_THRESH_BY_VALUE:
+        thresh_host = (C.c_float * Cc)(*vals)
+    else:
+        thresh_dev = torch.tensor(vals, dtype=torch.float32).to(dev)
+    if present is not None:
+        if not torch.is_tensor(present) or tuple(present.shape) != (B, Cc) or present.device != dev \
+                or present.dtype not in (torch.uint8, torch.bool):
+            raise WsdlError(f"seeded_region_growing: present must be a uint8 / bool {(B, Cc)} tensor on {dev}")
+        present = present.to(torch.uint8).contiguous()
+    grown = _out_tensor(out, "grown", (B, H, W), torch.int64, dev)
+    counts = _out_tensor(out, "counts", (B, Cc), torch.int64, dev)
+    ws = workspace(_ws_bytes("wsdl_seeded_region_growing_workspace", B, Cc, H, W), dev)
+    check(lib().wsdl_seeded_region_growing(_p(scores), _p(seeds), thresh_host, _p(thresh_dev), _p(present), B, Cc, H, W, ignore_index,
+                                           _p(grown), _p(counts), _p(ws), ws.numel(), _stream()))
+    _error_word(out, ws)
+    return grown, counts
+
+
+def check_balance(balance, name="balanced_seed_weights"):
+    if balance not in _SRG_BALANCES:
+        raise ValueError(f"{name}: balance {balance!r}: 'fg_bg', 'class' or 'none'")
+    return balance
+
+
+def balanced_seed_weights(grown, counts, *, balance="fg_bg", out=None):
+    """float32 (B,H,W) pixel weights of the seeding loss from ``seeded_region_growing``'s ``grown`` (int64 (B,H,W)) and ``counts``
+    (int64 (B,C)): a pixel whose label is in [0,C) gets ``float(1.0 / double(B * n))`` with ``n`` the number of pixels of its
+    group in its image - ``balance="fg_bg"``: class 0 and the classes >= 1 are the two groups (the paper's 1/|S_bg| and
+    1/|S_fg|), ``"class"``: every class by itself, ``"none"``: weight 1.  Any other label gets 0, and so does a group without a
+    pixel (the paper divides by zero there).  With ``ops.cross_entropy(..., reduction="sum", pixel_weight=)`` this is the
+    batch mean of the balanced seeding loss.  One launch, no host read.  ``out``: a dense float32 (B,H,W) device tensor to fill."""
+    check_balance(balance)
+    if not torch.is_tensor(grown) or grown.dim() != 3:
+        raise WsdlError("balanced_seed_weights: grown must be a (B,H,W) tensor")
+    grown = _req(grown, "balanced_seed_weights: grown", torch.int64).detach().contiguous()
+    B, H, W = grown.shape
+    if not torch.is_tensor(counts) or counts.dim() != 2 or counts.shape[0] != B or counts.shape[1] < 1 or counts.device != grown.device:
+        raise WsdlError(f"balanced_seed_weights: counts must be a ({B},C) tensor on {grown.device}")
+    counts = _req(counts, "balanced_seed_weights: counts", torch.int64).detach().contiguous()
+    check_components_geometry(B, H, W, "balanced_seed_weights")
+    if out is None:
+        out = torch.empty((B, H, W), device=grown.device, dtype=torch.float32)
+    elif not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (B, H, W) and out.device == grown.device
+              and out.is_contiguous()):
+        raise WsdlError(f"balanced_seed_weights: out must be a dense float32 {(B, H, W)} tensor on {grown.device}")
+    check(lib().wsdl_balanced_seed_weights(_p(grown), _p(counts), B, counts.shape[1], H, W, _SRG_BALANCES[balance], _p(out), _stream()))
+    return out
+
+
 def plane_relu_minmax(x):
     """(..., h, w) -> per plane: r = relu(x) - min(relu(x)); r / (max(r) + 1e-8)  (the reference's in-place
     ``cam -= cam.min(); cam /= cam.max() + 1e-8``: the maximum is taken AFTER the minimum has been subtracted)."""
