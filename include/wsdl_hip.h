@@ -951,6 +951,49 @@ int wsdl_seeded_region_growing(const float* scores, const int64_t* seeds, const 
 int wsdl_balanced_seed_weights(const int64_t* grown, const long long* counts, int B, int C, int H, int W, int balance, float* weights,
                                wsdl_stream_t stream);
 
+/* ---- SLIC superpixels, superpixel pooling (csrc/slic.hip) - the reference has no such step --------------------------------
+ * wsdl_slic: no counterpart in the reference.  SLIC (Achanta et al., TPAMI 2012; pixel-centric as in gSLIC) in fixed point on
+ *   8-bit images (B,3,H,W) uint8, never written; the three channels are used as given.  All arithmetic is integer, `/` floors.
+ *     grid        GH = max(1, (H + S/2) / S), GW likewise, K = GH GW; centre k = gy GW + gx starts at the pixel
+ *                 cy = ((2 gy + 1) H) / (2 GH), cx = ((2 gx + 1) W) / (2 GW) with that pixel's colour.  A centre is five ints
+ *                 (y, x, c0, c1, c2) in units of 1/16.  The home cell of pixel (y, x) is (min(GH-1, y GH / H), min(GW-1, x GW / W)).
+ *     assignment  over the centres of the existing cells (hy + dy, hx + dx), dy, dx in {-1, 0, 1}:
+ *                 D = S S sum_j (16 I_j - c_j)^2 + m m ((16 y - cy)^2 + (16 x - cx)^2) in 64 bits; smallest D, ties to the smallest k
+ *     update      per k: n and the plain integer sums of y, x, I_0, I_1, I_2 (64-bit); each component (16 sum + n/2) / n; n = 0 keeps it
+ *     loop        num_iter times assign, update; num_iter = 0 is one assignment against the initial centres.  raw (B,H,W) int32 is
+ *                 the label map of the last assignment, centres (B,K,5) int32 the values after the last update.
+ *     connectivity  raw is labelled 4-connected, every value, with areas (the kernels of wsdl_label_components).  The main component
+ *                 of a label is its largest, the smallest first pixel on ties.  A component is an ORPHAN iff it is not its label's
+ *                 main one, its area is < min_size and its first pixel is not pixel 0; an orphan with first pixel (y, x) is merged
+ *                 into the component of (y, x-1), of (y-1, x) when x = 0 - a different component with a smaller first pixel, so a
+ *                 chain of orphans ends at a kept component (more unions in the labelling's forest, then its flatten pass again;
+ *                 chains of any length).  segments (B,H,W) int32: the rank, in raster order of first pixels, of the kept
+ *                 component a pixel ends in; n_segments (B) int32, on the device, <= K + (H W) / min_size + 1.
+ *   8 + L + max(1, 2 num_iter) launches, L = 4 labelling launches (3 when H <= 32 and W <= 64), no host read, every parameter by
+ *   value, integer atomics only: bitwise reproducible.  ws: wsdl_slic_workspace bytes, 16-byte aligned; its first int32 is the
+ *   labelling's error word (see wsdl_label_components).  Refused without touching a device: non-positive sizes, a side > 8192,
+ *   B H W > 2^31 - 1, step outside [1, 128] (the workspace query returns 0 for these), compactness outside [1, 255],
+ *   num_iter < 0, min_size < 1.
+ * wsdl_superpixel_mean: no counterpart in the reference.  values (B,C,H,W) fp32, C <= 32; segments (B,H,W) int32 (a pixel whose id
+ *   is outside [0, n_max) is not pooled).  count (B,n_max) int32 = the pixels of every segment; every value is quantised to
+ *   q = llrint(double(clamp(v, -2^15, 2^15)) 2^24), the q are summed in 64-bit integers (on chip per tile first: one global atomic
+ *   per tile, channel and touched segment) and mean (B,C,n_max) = float(double(sum) / (double(n) 2^24)); 0 where n = 0; NaN for an
+ *   (image, channel, segment) that saw a NaN.  No float atomics: order-independent.  snapped (optional, (B,C,H,W)): every pixel's
+ *   segment mean (0 at an id outside [0, n_max)).  Two launches and two memsets, three launches with snapped.
+ *   ws: wsdl_superpixel_workspace(B, C, n_max) bytes, 8-byte aligned.
+ * wsdl_superpixel_vote: no counterpart in the reference.  labels (B,H,W) int64; out (B,H,W) int64 = at every pixel the label in
+ *   [0, num_classes) that most pixels of its segment carry, the smallest on ties; ignore_index for a segment without such a
+ *   pixel.  num_classes <= 64; integer counts.  Three launches and a memset.  ws: 4 B n_max num_classes bytes
+ *   (= wsdl_superpixel_workspace(B, num_classes, n_max) suffices). */
+size_t wsdl_slic_workspace(int B, int H, int W, int step);
+int wsdl_slic(const uint8_t* images, int B, int H, int W, int step, int compactness, int num_iter, int min_size, int* raw,
+              int* centres, int* segments, int* n_segments, void* ws, size_t ws_bytes, wsdl_stream_t stream);
+size_t wsdl_superpixel_workspace(int B, int C, int n_max);
+int wsdl_superpixel_mean(const float* values, const int* segments, int B, int C, int H, int W, int n_max, float* mean, int* count,
+                         float* snapped, void* ws, size_t ws_bytes, wsdl_stream_t stream);
+int wsdl_superpixel_vote(const int64_t* labels, const int* segments, int B, int H, int W, int n_max, int num_classes,
+                         long long ignore_index, int64_t* out, void* ws, size_t ws_bytes, wsdl_stream_t stream);
+
 /* ---- refine_pseudo_mask inner step (TraditionalModel/AlternatingDirectionCutLoss.py:736-757) -
  * KL(softmax(X) || S) with log(X+1e-8), reduction 'batchmean', and its gradient wrt softmax(X). */
 int wsdl_kl_div_fwd_bwd(const float* xn, const float* s, float* loss, float* dxn, size_t n, int batch,

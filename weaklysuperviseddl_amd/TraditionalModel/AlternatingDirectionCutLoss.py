@@ -168,7 +168,7 @@ def train_model(model, optimizer, criterion_ce=None, num_epochs=3, *, train_load
 
 
 def refine_dataset(model, dataset, repeats=5, chunk=64, threshold=0.3, lr=1e-4, num_steps=10, lambda_boundary=0.1,
-                   sigma_color=0.1, window_size=5, method="ncut", pamr_kwargs=None):
+                   sigma_color=0.1, window_size=5, method="ncut", pamr_kwargs=None, superpixel_kwargs=None):
     """Step 2 of an alternation (AlternatingDirectionCutLoss.py:803-810): ``repeats`` passes over the data set, each
     refining every pseudo mask and overwriting it - pass r+1 starts from pass r's thresholded masks, because the
     reference's dataset re-reads the PNG it has just overwritten.  In memory: ``dataset.set_masks``.  The network is
@@ -177,9 +177,17 @@ def refine_dataset(model, dataset, repeats=5, chunk=64, threshold=0.3, lr=1e-4, 
     ``method="pamr"`` (the reference has no such step; the default ``"ncut"`` is the reference's): each chunk's masks become
     ``ops.pamr(imgs, network_soft_prediction(model, imgs), **pamr_kwargs)[:, 1] > threshold``.  The network is frozen and
     the result does not depend on the old masks, so one pass is all there is: ``repeats`` is ignored, as are ``lr``,
-    ``num_steps``, ``lambda_boundary``, ``sigma_color`` and ``window_size``."""
-    if method not in ("ncut", "pamr"):
-        raise ValueError(f"refine_dataset: method {method!r}: 'ncut' or 'pamr'")
+    ``num_steps``, ``lambda_boundary``, ``sigma_color`` and ``window_size``.
+
+    ``method="superpixel"`` (no such step in the reference either): each chunk's masks become
+    ``ops.superpixel_snap(network_soft_prediction(model, imgs), segments, n_max)[:, 1] > threshold`` with ``segments`` the
+    ``ops.slic`` superpixels of the chunk's images (quantised with ``ops.slic_quantize``) and ``superpixel_kwargs`` the keywords
+    of ``ops.slic`` (default: ``step=16``).  One pass, as for ``"pamr"``."""
+    if method not in ("ncut", "pamr", "superpixel"):
+        raise ValueError(f"refine_dataset: method {method!r}: 'ncut', 'pamr' or 'superpixel'")
+    if method == "superpixel":
+        sp_kwargs = dict(superpixel_kwargs) if superpixel_kwargs else {"step": 16}
+        sp_step, _, _, sp_min = ops.check_slic_options(**dict(sp_kwargs, name="refine_dataset: superpixel_kwargs"))
     n = len(dataset)
     for s in range(0, n, chunk):
         idx = torch.arange(s, min(s + chunk, n), device=dataset.images.device)
@@ -187,6 +195,11 @@ def refine_dataset(model, dataset, repeats=5, chunk=64, threshold=0.3, lr=1e-4, 
         S = network_soft_prediction(model, imgs)
         if method == "pamr":
             dataset.set_masks(idx, (ops.pamr(imgs, S, **(pamr_kwargs or {}))[:, 1] > threshold).float())
+            continue
+        if method == "superpixel":
+            segments, _ = ops.slic(ops.slic_quantize(imgs), **sp_kwargs)
+            n_max = ops.slic_max_segments(imgs.shape[-2], imgs.shape[-1], sp_step, sp_min)
+            dataset.set_masks(idx, (ops.superpixel_snap(S, segments, n_max)[:, 1] > threshold).float())
             continue
         cache = ops.pairwise_cache(imgs, window_size, sigma_color)
         for _ in range(repeats):
@@ -213,7 +226,8 @@ def run_alternating_training(model, optimizer, dataset, num_alternations=10, epo
     the per-epoch step count is the minimum over the ranks; refinement is per-image independent and needs no
     collective.  ``augment``: an ``augment.Augment`` handed to ``dataset.batches`` - the training batches
     only; refinement reads the stored images and masks (the reference has no augmentation).  ``refine_kwargs`` goes to
-    ``refine_dataset``: ``{"method": "pamr"}`` refines with ``ops.pamr`` instead of the normalised-cut descent."""
+    ``refine_dataset``: ``{"method": "pamr"}`` refines with ``ops.pamr`` instead of the normalised-cut descent,
+    ``{"method": "superpixel", "superpixel_kwargs": {...}}`` with superpixel means of the network's prediction."""
     import torch.distributed as dist
     rk = dict(threshold=0.3, lr=1e-4, num_steps=10, lambda_boundary=0.1)
     rk.update(refine_kwargs or {})

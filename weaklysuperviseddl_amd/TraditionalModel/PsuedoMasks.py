@@ -15,6 +15,8 @@ Mirrors reference TraditionalModel/PsuedoMasks.py: ``keep_largest`` (:15-21) and
   * ``streams``: that many of the loader's batches are in flight on the device at once (``LayerCAMGenerator.generate_batches``);
     the masks are the same bit for bit;
   * ``pamr``: optional pixel-adaptive refinement of the CAM before its threshold (``ops.pamr``; off by default);
+  * ``superpixels``: optional snapping of the CAM, before its threshold, to the means over SLIC superpixels of the batch's
+    images (``ops.slic`` + ``ops.superpixel_snap``; off by default);
   * ``keep_largest(mask)`` is the reference's host function (skimage there; scipy.ndimage here - 8-connectivity, raster
     label order, first label wins area ties, empty mask returned unchanged).  ``generate_pseudo_masks`` itself labels
     the whole batch on the device (``keep_largest_batched`` -> ``ops.keep_largest_batched``, one workgroup per mask, the
@@ -66,6 +68,17 @@ def seeds_from_cam(cam, lo, hi, ignore_index=255):
     return torch.where(cam >= hi, torch.ones_like(seeds), seeds)
 
 
+def superpixel_cam(images, cam, **slic_kwargs):
+    """A CAM (B,H,W) snapped to the SLIC superpixels of ``images`` (B,3,H,W), float (ImageNet-normalised: ``ops.slic_quantize``)
+    or uint8: every pixel gets the mean of the CAM over its superpixel.  ``slic_kwargs`` are the keywords of ``ops.slic``."""
+    step, _, _, min_size = ops.check_slic_options(**dict(slic_kwargs, name="superpixel_cam"))
+    if images.is_floating_point():
+        images = ops.slic_quantize(images)
+    segments, _ = ops.slic(images, **slic_kwargs)
+    n_max = ops.slic_max_segments(cam.shape[-2], cam.shape[-1], step, min_size)
+    return ops.superpixel_snap(cam[:, None].float(), segments, n_max)[:, 0]
+
+
 def _to_png_u8(t):
     """torchvision.utils.save_image's quantisation: mul(255).add_(0.5).clamp_(0, 255) -> uint8, HWC."""
     return t.mul(255).add(0.5).clamp(0, 255).permute(1, 2, 0).to(torch.uint8).cpu().numpy()
@@ -74,11 +87,20 @@ def _to_png_u8(t):
 def generate_pseudo_masks(loader, layercam_gen, cam_thresh=0.3, alpha=1.0, keep_largest_masks=True,
                           run_id="default", out_root="/content", max_images=500, write_png=True,
                           device="cuda", rank=0, world=1, keep_images=False, streams=3, keep_on_device=False,
-                          device_batch=0, pamr=None):
+                          device_batch=0, pamr=None, superpixels=None):
     """``pamr``: None (the default: the masks are the thresholded CAMs, bit for bit as without the argument) or a dict of
     keyword arguments of ``ops.pamr`` (``{}``: its defaults) - the CAM WITHOUT its threshold is refined against the batch's
     images as a one-channel score map (pixel-adaptive mask refinement; the reference has no such step), the refined map is
-    thresholded (``>= cam_thresh``) and ``keep_largest`` applies as before.  The images must have the CAM's size."""
+    thresholded (``>= cam_thresh``) and ``keep_largest`` applies as before.  The images must have the CAM's size.
+
+    ``superpixels``: None (the default: bit for bit the path without the argument) or a dict of keyword arguments of ``ops.slic``
+    (``step`` is required) - the CAM WITHOUT its threshold is replaced by its means over the SLIC superpixels of the batch's
+    images (``superpixel_cam``; the reference has no such step), then ``>= cam_thresh``, then ``keep_largest`` as before.
+    Combining it with ``pamr`` is refused."""
+    if superpixels is not None:
+        if pamr is not None:
+            raise ValueError("generate_pseudo_masks: superpixels= and pamr= cannot be combined")
+        ops.check_slic_options(**dict(superpixels, name="generate_pseudo_masks: superpixels"))
     mask_dir = os.path.join(out_root, f"pseudo_masks_{run_id}")
     image_dir = os.path.join(out_root, f"images_{run_id}")
     if write_png:
@@ -113,6 +135,8 @@ def generate_pseudo_masks(loader, layercam_gen, cam_thresh=0.3, alpha=1.0, keep_
         for (imgs, imgs_d, _l, first_id, take), (cam, m) in zip(group, outs):
             if pamr is not None:
                 m = ops.pamr_labels(ops.pamr(imgs_d, cam[:, None], **pamr), thresh=cam_thresh).to(torch.uint8)
+            if superpixels is not None:
+                m = (superpixel_cam(imgs_d, cam, **superpixels) >= cam_thresh).to(torch.uint8)
             if keep_largest_masks:
                 m = keep_largest_batched(m)
             m_host = m if keep_on_device and not write_png else m.cpu().numpy()

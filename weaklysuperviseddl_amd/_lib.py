@@ -139,6 +139,11 @@ SIGNATURES = {
     "wsdl_seeded_region_growing_workspace": (_sz, [_i, _i, _i, _i]),
     "wsdl_seeded_region_growing": (_i, [_vp, _vp, C.POINTER(_f), _vp, _vp, _i, _i, _i, _i, _ll, _vp, _vp, _vp, _sz, _vp]),
     "wsdl_balanced_seed_weights": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "wsdl_slic_workspace": (_sz, [_i, _i, _i, _i]),
+    "wsdl_slic": (_i, [_vp] + [_i] * 7 + [_vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wsdl_superpixel_workspace": (_sz, [_i, _i, _i]),
+    "wsdl_superpixel_mean": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wsdl_superpixel_vote": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _ll, _vp, _vp, _sz, _vp]),
     "wsdl_kl_div_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, _sz, _vp]),
     "wsdl_kl_div_per_image_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _sz, _vp, _sz, _vp]),
     "wsdl_refine_combine": (_i, [_vp, _vp, _vp, _vp, _f, _f, _vp, _i, _sz, _vp]),

@@ -776,3 +776,42 @@ class PAMR(nn.Module):
 
     def extra_repr(self):
         return f"num_iter={self.num_iter}, dilations={self.dilations}"
+
+
+class Superpixels(nn.Module):
+    """Integer SLIC superpixels (``ops.slic``; the reference has no such step) as a module without parameters:
+    ``forward(images)`` returns ``(segments, n_segments)`` for uint8 (B,3,H,W) device images, or for float images normalised with
+    the ImageNet constants, which go through ``ops.slic_quantize`` first.  ``snap(images, scores)`` replaces every pixel of the
+    float32 (B,C,H,W) ``scores`` by its superpixel's mean (``ops.superpixel_snap``), ``vote(images, labels, num_classes)`` every
+    pixel of the int64 (B,H,W) ``labels`` by its superpixel's majority label (``ops.superpixel_vote``).  Not differentiable: the
+    results have no ``grad_fn``.
+
+        sp = wnn.Superpixels(step=16)
+        cam = sp.snap(images, cam[:, None])[:, 0]                 # a blurry CAM snapped to image edges
+        masks = sp.vote(images, masks, num_classes=2)             # a pseudo mask denoised without any learning
+    """
+
+    def __init__(self, step, compactness=10, num_iter=10, min_size=None):
+        super().__init__()
+        self.step, self.compactness, self.num_iter, self.min_size = ops.check_slic_options(step, compactness, num_iter, min_size,
+                                                                                           name="Superpixels")
+
+    def _images(self, images):
+        return ops.slic_quantize(images) if torch.is_tensor(images) and images.is_floating_point() else images
+
+    def max_segments(self, images):
+        return ops.slic_max_segments(images.shape[-2], images.shape[-1], self.step, self.min_size)
+
+    def forward(self, images):
+        return ops.slic(self._images(images), self.step, self.compactness, self.num_iter, self.min_size)
+
+    def snap(self, images, scores):
+        segments, _ = self.forward(images)
+        return ops.superpixel_snap(scores, segments, self.max_segments(images))
+
+    def vote(self, images, labels, num_classes, ignore_index=255):
+        segments, _ = self.forward(images)
+        return ops.superpixel_vote(labels, segments, self.max_segments(images), num_classes, ignore_index)
+
+    def extra_repr(self):
+        return f"step={self.step}, compactness={self.compactness}, num_iter={self.num_iter}, min_size={self.min_size}"

@@ -3548,6 +3548,194 @@ def balanced_seed_weights(grown, counts, *, balance="fg_bg", out=None):
     return out
 
 
+SLIC_MAX_STEP, SLIC_MAX_COMPACTNESS, SLIC_MAX_SIDE = 128, 255, 8192
+SUPERPIXEL_MAX_CHANNELS, SUPERPIXEL_MAX_CLASSES = 32, 64
+_SLIC_MEAN = (0.485, 0.456, 0.406)
+_SLIC_STD = (0.229, 0.224, 0.225)
+_slic_norm_cache = {}
+
+
+def check_slic_options(step, compactness=10, num_iter=10, min_size=None, name="slic"):
+    """``(step, compactness, num_iter, min_size)`` as ints, ``min_size=None`` resolved to ``max(1, step * step // 4)``;
+    ValueError unless step is an int in [1, 128], compactness an int in [1, 255], num_iter an int >= 0 and min_size an int >= 1
+    (what the library refuses; no device needed)."""
+    def integer(v, what, lo, hi=None):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+            raise ValueError(f"{name}: {what} {v!r}: an int " + (f"in [{lo}, {hi}]" if hi is not None else f">= {lo}"))
+        return int(v)
+    step = integer(step, "step", 1, SLIC_MAX_STEP)
+    compactness = integer(compactness, "compactness", 1, SLIC_MAX_COMPACTNESS)
+    num_iter = integer(num_iter, "num_iter", 0)
+    min_size = max(1, step * step // 4) if min_size is None else integer(min_size, "min_size", 1)
+    return step, compactness, num_iter, min_size
+
+
+def check_slic_geometry(B, H, W, name="slic"):
+    """ValueError for an empty batch, a side above 8192 or more than 2^31 - 1 pixels (what the library refuses; no device needed)."""
+    check_components_geometry(B, H, W, name)
+    if max(H, W) > SLIC_MAX_SIDE:
+        raise ValueError(f"{name}: (H,W) = {(H, W)}: sides up to {SLIC_MAX_SIDE}")
+
+
+def slic_grid(H, W, step):
+    """``(GH, GW)`` of the superpixel grid: ``max(1, (H + step // 2) // step)`` and likewise for W."""
+    return max(1, (H + step // 2) // step), max(1, (W + step // 2) // step)
+
+
+def slic_max_segments(H, W, step, min_size=None):
+    """The bound ``K + (H * W) // min_size + 1`` on the segments of one image that ``slic`` can return: the K main components and
+    pixel 0's, plus every other kept component (each has at least ``min_size`` pixels).  The size every per-segment buffer is
+    allocated with.  No device needed."""
+    step, _, _, min_size = check_slic_options(step, min_size=min_size, name="slic_max_segments")
+    GH, GW = slic_grid(H, W, step)
+    return GH * GW + (H * W) // min_size + 1
+
+
+def slic_launches(H, W, num_iter):
+    """Kernel launches of one ``slic`` call: ``8 + L + max(1, 2 * num_iter)`` with L = 4 labelling launches, 3 when the image
+    is a single labelling tile (H <= 32 and W <= 64)."""
+    return 8 + (3 if H <= 32 and W <= 64 else 4) + max(1, 2 * num_iter)
+
+
+def slic_quantize(images, mean=_SLIC_MEAN, std=_SLIC_STD):
+    """Float device images (B,3,H,W), normalised as ``(x - mean) / std`` per channel, back to uint8:
+    ``clamp(rint((x * std + mean) * 255), 0, 255)`` with plain tensor operations on the device.  Plumbing in front of ``slic``,
+    not part of its exact contract."""
+    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != 3 or not images.is_floating_point():
+        raise WsdlError("slic_quantize: images must be a float (B,3,H,W) tensor")
+    if not images.is_cuda:
+        raise WsdlError(f"slic_quantize: the HIP path needs a device tensor (got {images.device}); there is no CPU fallback")
+    x = images.detach()
+    key = (x.device, x.dtype, tuple(mean), tuple(std))
+    if key not in _slic_norm_cache:          # made once: a tensor from host values is a copy the host waits for
+        _slic_norm_cache[key] = (torch.tensor(key[2], dtype=x.dtype, device=x.device).view(1, 3, 1, 1),
+                                 torch.tensor(key[3], dtype=x.dtype, device=x.device).view(1, 3, 1, 1))
+    m, s = _slic_norm_cache[key]
+    return torch.clamp(torch.round((x * s + m) * 255), 0, 255).to(torch.uint8).contiguous()
+
+
+def slic(images, step, compactness=10, num_iter=10, min_size=None, out=None):
+    """Integer SLIC superpixels (Achanta et al., TPAMI 2012, pixel-centric as in gSLIC; the reference has no such step) of uint8
+    device images (B,3,H,W) - the three channels are used as given; float images go through ``slic_quantize`` first.  ``step``
+    (S, 1 to 128) is the spacing of the initial grid, ``compactness`` (m, 1 to 255) the weight of position against colour,
+    ``num_iter`` the number of assign / update rounds (0: one assignment against the initial centres), ``min_size`` (None:
+    ``max(1, S * S // 4)``) the area below which a stray component is merged away.
+
+    All arithmetic is integer, in units of 1/16 (include/wsdl_hip.h "SLIC superpixels" and tests/slic_oracle.py state it in
+    full): a pixel takes, among the centres of the 3 x 3 grid cells around its own, the one of smallest
+    ``D = S^2 |16 I - c|^2 + m^2 |16 (y, x) - (cy, cx)|^2`` (64 bits; ties to the smallest index), a centre becomes the rounded
+    mean ``(16 sum + n // 2) // n`` of its pixels.  The last assignment is labelled 4-connected (``label_components``' kernels,
+    with areas); a component that is not the largest of its label, is smaller than ``min_size`` and does not start at pixel 0 is
+    merged into the component of the pixel left of its first pixel (above it in column 0) - chains of such merges of any length.
+    Returns ``(segments, n_segments)``: ``segments`` int32 (B,H,W), dense ids in ``[0, n_b)`` ordered by each segment's first
+    pixel, every segment 4-connected; ``n_segments`` int32 (B,) on the device, at most ``slic_max_segments(H, W, step, min_size)``.
+
+    ``slic_launches(H, W, num_iter)`` = ``8 + L + max(1, 2 * num_iter)`` launches (L = 4, or 3 for an image of one 64 x 32
+    labelling tile), integer atomics only, no float anywhere, no host read, parameters by value, bitwise reproducible - a launch
+    plan can hold the call; the images are never written.  ``out``: a dict whose ``"segments"`` / ``"n_segments"`` / ``"raw"``
+    (int32 (B,H,W): the last assignment) / ``"centres"`` (int32 (B,K,5): y, x, c0, c1, c2 times 16) tensors are filled (created
+    when missing or of another shape); ``out["error"]`` then views the labelling's error word (see ``label_components``)."""
+    step, compactness, num_iter, min_size = check_slic_options(step, compactness, num_iter, min_size)
+    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != 3:
+        raise WsdlError("slic: images must be a (B,3,H,W) uint8 tensor")
+    if images.dtype != torch.uint8:
+        raise ValueError(f"slic: images must be uint8, got {images.dtype} (float images: slic_quantize)")
+    B, _, H, W = images.shape
+    check_slic_geometry(B, H, W)
+    images = _req(images, "slic: images", torch.uint8).contiguous()
+    dev = images.device
+    GH, GW = slic_grid(H, W, step)
+    segments = _out_tensor(out, "segments", (B, H, W), torch.int32, dev)
+    n_segments = _out_tensor(out, "n_segments", (B,), torch.int32, dev)
+    keep = out if out is not None else {}
+    raw = _out_tensor(keep, "raw", (B, H, W), torch.int32, dev)
+    centres = _out_tensor(keep, "centres", (B, GH * GW, 5), torch.int32, dev)
+    ws = workspace(_ws_bytes("wsdl_slic_workspace", B, H, W, step), dev)
+    check(lib().wsdl_slic(_p(images), B, H, W, step, compactness, num_iter, min_size, _p(raw), _p(centres), _p(segments),
+                          _p(n_segments), _p(ws), ws.numel(), _stream()))
+    _error_word(out, ws)
+    return segments, n_segments
+
+
+def _superpixel_segments(segments, shape, dev, name):
+    if not torch.is_tensor(segments) or tuple(segments.shape) != tuple(shape) or segments.device != dev:
+        raise WsdlError(f"{name}: segments must be an int32 {tuple(shape)} tensor on {dev}")
+    return _req(segments, f"{name}: segments", torch.int32).contiguous()
+
+
+def _segments_max(n, name):
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError(f"{name}: n_segments_max {n!r}: an int >= 1 (slic_max_segments)")
+    return int(n)
+
+
+def _superpixel_pool(values, segments, n_segments_max, out, snap, name):
+    n_max = _segments_max(n_segments_max, name)
+    if not torch.is_tensor(values) or values.dim() != 4:
+        raise WsdlError(f"{name}: values must be a (B,C,H,W) float32 tensor")
+    B, Cc, H, W = values.shape
+    if not 1 <= Cc <= SUPERPIXEL_MAX_CHANNELS:
+        raise ValueError(f"{name}: {Cc} channels: 1 to {SUPERPIXEL_MAX_CHANNELS}")
+    check_components_geometry(B, H, W, name)
+    values = _dense(values.detach(), f"{name}: values")
+    dev = values.device
+    segments = _superpixel_segments(segments, (B, H, W), dev, name)
+    nbytes = _ws_bytes("wsdl_superpixel_workspace", B, Cc, n_max)
+    if nbytes == 0:
+        raise WsdlError(f"{name}: B C n_segments_max = {B * Cc * n_max} > 2^31 - 1")
+    mean = _out_tensor(out, "mean", (B, Cc, n_max), torch.float32, dev)
+    count = _out_tensor(out, "count", (B, n_max), torch.int32, dev)
+    snapped = _out_tensor(out, "snapped", (B, Cc, H, W), torch.float32, dev) if snap else None
+    ws = workspace(nbytes, dev)
+    check(lib().wsdl_superpixel_mean(_p(values), _p(segments), B, Cc, H, W, n_max, _p(mean), _p(count), _p(snapped), _p(ws),
+                                     ws.numel(), _stream()))
+    return mean, count, snapped
+
+
+def superpixel_mean(values, segments, n_segments_max, out=None):
+    """The mean of float32 device ``values`` (B,C,H,W), C up to 32, over every segment of ``segments`` (int32 (B,H,W), as ``slic``
+    returns them): ``(mean, count)`` with ``mean`` float32 (B,C,n_segments_max) and ``count`` int32 (B,n_segments_max).  No float
+    atomics: every value is quantised to ``q = llrint(double(clamp(v, -2^15, 2^15)) * 2^24)``, the q are summed with 64-bit
+    integer atomics (on chip per tile first) and ``mean = float(double(sum) / (double(n) * 2^24))`` - independent of the order,
+    bit for bit the oracle's value; within 2^-24 (plus the rounding to float32) of the exact mean of values inside +-2^15.
+    0 where ``n = 0``; NaN for an (image, channel, segment) that saw a NaN.  A pixel whose id is outside
+    ``[0, n_segments_max)`` is not pooled.  Two launches and two memsets, no host read.  ``out``: a dict whose ``"mean"`` /
+    ``"count"`` tensors are filled (created when missing or of another shape)."""
+    mean, count, _ = _superpixel_pool(values, segments, n_segments_max, out, False, "superpixel_mean")
+    return mean, count
+
+
+def superpixel_snap(values, segments, n_segments_max, out=None):
+    """(B,C,H,W) float32: every pixel gets the ``superpixel_mean`` of its segment (0 at an id outside ``[0, n_segments_max)``) -
+    the mean pass plus a gather, three launches.  ``out``: a dict whose ``"snapped"`` (and ``"mean"`` / ``"count"``) tensors are
+    filled."""
+    return _superpixel_pool(values, segments, n_segments_max, out, True, "superpixel_snap")[2]
+
+
+def superpixel_vote(labels, segments, n_segments_max, num_classes, ignore_index=255):
+    """int64 (B,H,W): every pixel gets the majority label of its segment among the values of ``labels`` (int64 (B,H,W)) in
+    ``[0, num_classes)``, the smallest class on ties; ``ignore_index`` for a segment without such a pixel (and at a segment id
+    outside ``[0, n_segments_max)``).  Integer counts, ``num_classes`` up to 64; three launches and a memset, no host read."""
+    n_max = _segments_max(n_segments_max, "superpixel_vote")
+    if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or not 1 <= num_classes <= SUPERPIXEL_MAX_CLASSES:
+        raise ValueError(f"superpixel_vote: num_classes {num_classes!r}: an int in [1, {SUPERPIXEL_MAX_CLASSES}]")
+    ignore_index = _int_option(ignore_index, "superpixel_vote: ignore_index")
+    if not torch.is_tensor(labels) or labels.dim() != 3:
+        raise WsdlError("superpixel_vote: labels must be a (B,H,W) int64 tensor")
+    B, H, W = labels.shape
+    check_components_geometry(B, H, W, "superpixel_vote")
+    labels = _req(labels, "superpixel_vote: labels", torch.int64).detach().contiguous()
+    dev = labels.device
+    segments = _superpixel_segments(segments, (B, H, W), dev, "superpixel_vote")
+    if B * n_max * int(num_classes) > 2 ** 31 - 1:
+        raise WsdlError(f"superpixel_vote: B n_segments_max num_classes = {B * n_max * int(num_classes)} > 2^31 - 1")
+    out = torch.empty((B, H, W), dtype=torch.int64, device=dev)
+    ws = workspace(4 * B * n_max * int(num_classes), dev)
+    check(lib().wsdl_superpixel_vote(_p(labels), _p(segments), B, H, W, n_max, int(num_classes), ignore_index, _p(out), _p(ws),
+                                     ws.numel(), _stream()))
+    return out
+
+
 def plane_relu_minmax(x):
     """(..., h, w) -> per plane: r = relu(x) - min(relu(x)); r / (max(r) + 1e-8)  (the reference's in-place
     ``cam -= cam.min(); cam /= cam.max() + 1e-8``: the maximum is taken AFTER the minimum has been subtracted)."""
