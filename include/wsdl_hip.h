@@ -994,6 +994,64 @@ int wsdl_superpixel_mean(const float* values, const int* segments, int B, int C,
 int wsdl_superpixel_vote(const int64_t* labels, const int* segments, int B, int H, int W, int n_max, int num_classes,
                          long long ignore_index, int64_t* out, void* ws, size_t ws_bytes, wsdl_stream_t stream);
 
+/* ---- AffinityNet: learned pairwise affinities, their loss and the CAM random walk (Ahn & Kwak, CVPR 2018; csrc/affinity.hip)
+ * - the reference has no such step -
+ * Features f (B,D,H,W) fp32, dense NCHW; labels (B,H,W) int64 on the same H x W.
+ * Pair set: PSA's half disc of radius r, 2 <= r <= 8, in this order: first (0,x) for x = 1..r-1; then, for y = 1..r-1, every
+ *   (y,x) with x = -(r-1)..r-1 and x^2 + y^2 < r^2.  P = 4 at r = 2 - (0,1),(1,-1),(1,0),(1,1) -, 34 at r = 5, 96 at r = 8
+ *   (wsdl_affinity_num_pairs; 0 for a radius outside the range).
+ *   A pair (p, q = p + o_j) is VALID iff q lies inside the image.  This is NOT PSA's crop of the "from" region (PSA takes its
+ *   "from" pixels from the image shrunk by r - 1 on the left, right and bottom, so every pair it forms is complete): here every
+ *   pixel is a "from" pixel and the pairs that leave the image do not exist.
+ * Affinity: a(p,j) = exp(-(1/D) sum_d |f_d(p) - f_d(q)|) for a valid pair, exactly 0 for an invalid one; (B,P,H,W) fp32, plane j =
+ *   offset j.  The channels are summed 8 at a time in float (in a fixed order), those partial sums in double; exp in double,
+ *   one rounding of the result.
+ * Loss (PSA's train_aff).  Kinds from the labels: both ends != ignore_index, equal and 0: bg-positive; equal and > 0: fg-positive;
+ *   both != ignore_index and different: negative; anything else, or an invalid pair: not counted.  With the exact int64 counts
+ *   n_bg, n_fg, n_neg over the whole batch and s_k = w_k / (n_k + eps):
+ *     L = s_bg sum_bg -log(a + eps) + s_fg sum_fg -log(a + eps) + s_neg sum_neg -log(1 + eps - a)
+ *   An empty kind contributes 0; no counted pair at all gives L = 0 and a zero gradient.  The sums run in double: one partial per
+ *   workgroup, added in a fixed order by one workgroup; counts are integers; no float atomics - two calls give identical bits.
+ * Gradient, closed form, gather form (no atomics): dL/df_d(p) = (1/D) sum over the up to 2 P full-disc neighbours q of
+ *   c(p,q) sign(f_d(p) - f_d(q)) with the symmetric pair coefficient c = s_k a / (a + eps) for positives, c = -s_neg a / (1 + eps - a)
+ *   for negatives; sign(0) = 0.  c is a float; the terms are summed 4 at a time in float (2 pairs, both orientations), those
+ *   partial sums in double.
+ * Transitions and walk: the neighbourhood of a pixel is itself (affinity 1) plus both orientations of every valid pair, at most
+ *   2 P + 1 entries; w(p,q) = a(p,q)^beta / sum_q' a(p,q')^beta (beta > 0; the self term keeps the denominator >= 1); trans is
+ *   (B,2P+1,H,W) fp32: plane 0 self, plane 1 + 2j offset j (q = p + o_j), plane 2 + 2j its reverse (q = p - o_j, weight
+ *   a(q,j)^beta); 0 where q is outside.  One step is m'_c(p) = sum_q w(p,q) m_c(q), at most 2 P + 1 terms by fma in double in plane
+ *   order, rounded once; num_iter steps equal PSA's cam @ T^t with T the column-normalised dense (A + I)^beta (elementwise
+ *   power) and t = num_iter (PSA's defaults: beta 8, 256 steps).  No replicate padding: neighbours outside the image do not
+ *   exist - neither their weight nor any score enters the sum, so an infinite score spreads as inf, not NaN.  A constant map is a
+ *   fixed point.  Scores (B,C,H,W) fp32, 1 <= C <= 32.
+ * Limits: 1 <= D <= 1024, H, W >= 1, H W <= 2^20.  Offsets and scalars reach the kernels by value: a launch plan may hold the calls.
+ * wsdl_affinity_workspace: bytes of ws that suffice for every entry point below at this geometry (16-byte aligned); 0 outside
+ *   the limits (host-side, no device touched).
+ * wsdl_affinity_pair_affinity: aff (B,P,H,W).  One launch.
+ * wsdl_affinity_pair_affinity_backward: dfeat (B,D,H,W) = dL/df from daff = dL/da (B,P,H,W) and aff.  One launch.
+ * wsdl_affinity_pair_counts: counts_out[3] int64 = n_bg, n_fg, n_neg.  Two launches.
+ * wsdl_affinity_loss: counts, forward with the per-kind partial sums and the pair coefficients, the finalize (loss: one float) and,
+ *   if dfeat is not null, the gradient (B,D,H,W): five launches.  counts_out (optional): int64[3].
+ * wsdl_affinity_transitions: trans (B,2P+1,H,W) from aff.  One launch.
+ * wsdl_affinity_random_walk: num_iter steps from scores to out, one launch per step over the whole batch, ping-pong between two
+ *   buffers carved from ws (not needed for num_iter < 2); the result lands in out for every num_iter; num_iter = 0 copies;
+ *   scores is never written; out must not overlap scores or trans.  (A second path - one launch for all steps, one workgroup
+ *   per (image, channel) with its plane in LDS, identical bits - was built and measured: 2009 against 1915 us at scores
+ *   (16,2,32,32) and 7859 against 1938 us at (8,2,64,64), 256 steps; not faster at either, so it is not shipped.) */
+size_t wsdl_affinity_workspace(int B, int D, int C, int H, int W, int radius);
+int wsdl_affinity_num_pairs(int radius);
+int wsdl_affinity_pair_affinity(const float* feat, int B, int D, int H, int W, int radius, float* aff, wsdl_stream_t stream);
+int wsdl_affinity_pair_affinity_backward(const float* feat, const float* aff, const float* daff, float* dfeat, int B, int D, int H,
+                                         int W, int radius, wsdl_stream_t stream);
+int wsdl_affinity_pair_counts(const long long* labels, int B, int H, int W, int radius, long long ignore_index,
+                              long long* counts_out, void* ws, size_t ws_bytes, wsdl_stream_t stream);
+int wsdl_affinity_loss(const float* feat, const long long* labels, float* loss, float* dfeat, long long* counts_out, int B, int D,
+                       int H, int W, int radius, long long ignore_index, double w_bg, double w_fg, double w_neg, double eps, void* ws,
+                       size_t ws_bytes, wsdl_stream_t stream);
+int wsdl_affinity_transitions(const float* aff, float* trans, int B, int H, int W, int radius, double beta, wsdl_stream_t stream);
+int wsdl_affinity_random_walk(const float* trans, const float* scores, float* out, int B, int C, int H, int W, int radius,
+                              int num_iter, void* ws, size_t ws_bytes, wsdl_stream_t stream);
+
 /* ---- refine_pseudo_mask inner step (TraditionalModel/AlternatingDirectionCutLoss.py:736-757) -
  * KL(softmax(X) || S) with log(X+1e-8), reduction 'batchmean', and its gradient wrt softmax(X). */
 int wsdl_kl_div_fwd_bwd(const float* xn, const float* s, float* loss, float* dxn, size_t n, int batch,

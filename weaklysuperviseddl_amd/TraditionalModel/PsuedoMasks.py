@@ -17,6 +17,8 @@ Mirrors reference TraditionalModel/PsuedoMasks.py: ``keep_largest`` (:15-21) and
   * ``pamr``: optional pixel-adaptive refinement of the CAM before its threshold (``ops.pamr``; off by default);
   * ``superpixels``: optional snapping of the CAM, before its threshold, to the means over SLIC superpixels of the batch's
     images (``ops.slic`` + ``ops.superpixel_snap``; off by default);
+  * ``affinity``: optional random walk of the CAM, before its threshold, under the learned affinities of an ``AffinityNet``
+    (``ops.affinity_random_walk``; off by default);
   * ``keep_largest(mask)`` is the reference's host function (skimage there; scipy.ndimage here - 8-connectivity, raster
     label order, first label wins area ties, empty mask returned unchanged).  ``generate_pseudo_masks`` itself labels
     the whole batch on the device (``keep_largest_batched`` -> ``ops.keep_largest_batched``, one workgroup per mask, the
@@ -79,6 +81,26 @@ def superpixel_cam(images, cam, **slic_kwargs):
     return ops.superpixel_snap(cam[:, None].float(), segments, n_max)[:, 0]
 
 
+def _affinity_options(affinity):
+    """The ``affinity=`` dict of ``generate_pseudo_masks`` with its defaults; ValueError / WsdlError for what it cannot be."""
+    if not isinstance(affinity, dict) or "net" not in affinity or set(affinity) - {"net", "radius", "beta", "num_iter"}:
+        raise ValueError("generate_pseudo_masks: affinity= is a dict of net, radius, beta, num_iter (net is required)")
+    opts = dict(radius=5, beta=8.0, num_iter=256)
+    opts.update(affinity)
+    ops.check_affinity_options(opts["radius"], beta=opts["beta"], num_iter=opts["num_iter"], name="generate_pseudo_masks: affinity")
+    return opts
+
+
+def affinity_cam(images, cam, net, radius=5, beta=8.0, num_iter=256):
+    """A CAM (B,H,W) propagated by AffinityNet's random walk: resized to the feature size of ``net(images)``, walked ``num_iter``
+    steps as a one-channel map under ``ops.affinity_transitions(ops.pair_affinity(features), beta)``, resized back to H x W."""
+    with torch.no_grad():
+        feat = net(images)
+    small = ops.bilinear_resize(cam[:, None].float().contiguous(), tuple(feat.shape[-2:]))
+    walked = ops.affinity_random_walk(feat, small, radius=radius, beta=beta, num_iter=num_iter)
+    return ops.bilinear_resize(walked, tuple(cam.shape[-2:]))[:, 0]
+
+
 def _to_png_u8(t):
     """torchvision.utils.save_image's quantisation: mul(255).add_(0.5).clamp_(0, 255) -> uint8, HWC."""
     return t.mul(255).add(0.5).clamp(0, 255).permute(1, 2, 0).to(torch.uint8).cpu().numpy()
@@ -87,7 +109,7 @@ def _to_png_u8(t):
 def generate_pseudo_masks(loader, layercam_gen, cam_thresh=0.3, alpha=1.0, keep_largest_masks=True,
                           run_id="default", out_root="/content", max_images=500, write_png=True,
                           device="cuda", rank=0, world=1, keep_images=False, streams=3, keep_on_device=False,
-                          device_batch=0, pamr=None, superpixels=None):
+                          device_batch=0, pamr=None, superpixels=None, affinity=None):
     """``pamr``: None (the default: the masks are the thresholded CAMs, bit for bit as without the argument) or a dict of
     keyword arguments of ``ops.pamr`` (``{}``: its defaults) - the CAM WITHOUT its threshold is refined against the batch's
     images as a one-channel score map (pixel-adaptive mask refinement; the reference has no such step), the refined map is
@@ -96,7 +118,17 @@ def generate_pseudo_masks(loader, layercam_gen, cam_thresh=0.3, alpha=1.0, keep_
     ``superpixels``: None (the default: bit for bit the path without the argument) or a dict of keyword arguments of ``ops.slic``
     (``step`` is required) - the CAM WITHOUT its threshold is replaced by its means over the SLIC superpixels of the batch's
     images (``superpixel_cam``; the reference has no such step), then ``>= cam_thresh``, then ``keep_largest`` as before.
-    Combining it with ``pamr`` is refused."""
+    Combining it with ``pamr`` is refused.
+
+    ``affinity``: None (the default: bit for bit the path without the argument) or a dict with ``net`` (an ``AffinityNet``, on the
+    device, in eval mode) and optionally ``radius`` (5), ``beta`` (8.0) and ``num_iter`` (256) - the CAM WITHOUT its threshold is
+    resized to the net's feature size (``ops.bilinear_resize``), walked as a one-channel map under the affinities of the batch's
+    features (``affinity_cam``; the reference has no such step) and resized back, then ``>= cam_thresh``, then ``keep_largest``
+    as before.  Combining it with ``pamr`` or ``superpixels`` is refused."""
+    if affinity is not None:
+        if pamr is not None or superpixels is not None:
+            raise ValueError("generate_pseudo_masks: affinity= cannot be combined with pamr= or superpixels=")
+        affinity = _affinity_options(affinity)
     if superpixels is not None:
         if pamr is not None:
             raise ValueError("generate_pseudo_masks: superpixels= and pamr= cannot be combined")
@@ -137,6 +169,8 @@ def generate_pseudo_masks(loader, layercam_gen, cam_thresh=0.3, alpha=1.0, keep_
                 m = ops.pamr_labels(ops.pamr(imgs_d, cam[:, None], **pamr), thresh=cam_thresh).to(torch.uint8)
             if superpixels is not None:
                 m = (superpixel_cam(imgs_d, cam, **superpixels) >= cam_thresh).to(torch.uint8)
+            if affinity is not None:
+                m = (affinity_cam(imgs_d, cam, **affinity) >= cam_thresh).to(torch.uint8)
             if keep_largest_masks:
                 m = keep_largest_batched(m)
             m_host = m if keep_on_device and not write_png else m.cpu().numpy()

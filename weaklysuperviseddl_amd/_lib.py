@@ -144,6 +144,14 @@ SIGNATURES = {
     "wsdl_superpixel_workspace": (_sz, [_i, _i, _i]),
     "wsdl_superpixel_mean": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wsdl_superpixel_vote": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _ll, _vp, _vp, _sz, _vp]),
+    "wsdl_affinity_workspace": (_sz, [_i] * 6),
+    "wsdl_affinity_num_pairs": (_i, [_i]),
+    "wsdl_affinity_pair_affinity": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "wsdl_affinity_pair_affinity_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "wsdl_affinity_pair_counts": (_i, [_vp, _i, _i, _i, _i, _ll, _vp, _vp, _sz, _vp]),
+    "wsdl_affinity_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _ll] + [C.c_double] * 4 + [_vp, _sz, _vp]),
+    "wsdl_affinity_transitions": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_double, _vp]),
+    "wsdl_affinity_random_walk": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "wsdl_kl_div_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, _sz, _vp]),
     "wsdl_kl_div_per_image_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _sz, _vp, _sz, _vp]),
     "wsdl_refine_combine": (_i, [_vp, _vp, _vp, _vp, _f, _f, _vp, _i, _sz, _vp]),

@@ -815,3 +815,38 @@ class Superpixels(nn.Module):
 
     def extra_repr(self):
         return f"step={self.step}, compactness={self.compactness}, num_iter={self.num_iter}, min_size={self.min_size}"
+
+
+class AffinityLoss(nn.Module):
+    """AffinityNet's pair loss (Ahn & Kwak, CVPR 2018; ``ops.affinity_loss``) as a module without parameters:
+    ``forward(feat, labels)`` for float32 features (B,D,h,w) and int64 labels (B,h,w) at the feature size - 0 background, > 0
+    a class, ``ignore_index`` unsure (``affinity_labels_from_cam``).  ``weights`` are those of the bg-positive, fg-positive
+    and negative terms.  A plain module: not one of the segmentation criteria ``train_step`` takes."""
+
+    def __init__(self, radius=5, ignore_index=255, weights=ops.AFFINITY_WEIGHTS):
+        super().__init__()
+        ops.check_affinity_options(radius, weights=weights, name="AffinityLoss")
+        self.radius, self.ignore_index, self.weights = radius, int(ignore_index), tuple(float(v) for v in weights)
+
+    def forward(self, feat, labels):
+        return ops.affinity_loss(feat, labels, radius=self.radius, ignore_index=self.ignore_index, weights=self.weights)
+
+    def extra_repr(self):
+        return f"radius={self.radius}, ignore_index={self.ignore_index}, weights={self.weights}"
+
+
+class RandomWalk(nn.Module):
+    """AffinityNet's CAM propagation as a module without parameters: ``forward(feat, scores)`` is
+    ``ops.affinity_random_walk(feat, scores, radius=, beta=, num_iter=)`` - scores (B,C,h,w) walked ``num_iter`` steps under
+    the transition weights of features (B,D,h,w).  Not differentiable: the result has no ``grad_fn``."""
+
+    def __init__(self, radius=5, beta=8.0, num_iter=256):
+        super().__init__()
+        ops.check_affinity_options(radius, beta=beta, num_iter=num_iter, name="RandomWalk")
+        self.radius, self.beta, self.num_iter = radius, float(beta), num_iter
+
+    def forward(self, feat, scores):
+        return ops.affinity_random_walk(feat, scores, radius=self.radius, beta=self.beta, num_iter=self.num_iter)
+
+    def extra_repr(self):
+        return f"radius={self.radius}, beta={self.beta}, num_iter={self.num_iter}"

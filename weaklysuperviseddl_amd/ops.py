@@ -2763,6 +2763,244 @@ def pamr_labels(scores, thresh=0.5, min_conf=0.0, ignore_index=255):
     return labels
 
 
+# ---- AffinityNet: learned pairwise affinities, their loss, the CAM random walk (csrc/affinity.hip; include/wsdl_hip.h "AffinityNet")
+AFFINITY_WEIGHTS = (0.25, 0.25, 0.5)
+
+
+def affinity_offsets(radius):
+    """PSA's half disc of pair offsets ``(dy, dx)`` for ``radius`` in [2, 8], in the order of the affinity planes: first (0,x)
+    for x = 1..r-1, then, for y = 1..r-1, every (y,x) with x = -(r-1)..r-1 and x^2 + y^2 < r^2 (4 pairs at r = 2, 34 at r = 5).
+    Host only."""
+    r = _affinity_radius(radius)
+    out = [(0, x) for x in range(1, r)]
+    out += [(y, x) for y in range(1, r) for x in range(-(r - 1), r) if x * x + y * y < r * r]
+    return out
+
+
+def _affinity_radius(radius, name="affinity"):
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 2 <= radius <= 8:
+        raise WsdlError(f"{name}: radius {radius!r} must be an int in [2, 8]")
+    return radius
+
+
+def check_affinity_options(radius=5, *, feat=None, labels=None, aff=None, trans=None, scores=None, out=None, beta=None,
+                           num_iter=None, weights=None, eps=None, name="affinity"):
+    """Host-side validation of the affinity ops, before any device call: WsdlError for a radius outside [2, 8], a ``beta`` that
+    is not a finite number > 0, a ``num_iter`` that is not an int >= 0, ``weights`` that are not three finite numbers, an ``eps``
+    that is not > 0, tensors of the wrong rank, type or place, sizes that do not match each other (``labels`` (B,h,w) int64,
+    ``aff`` (B,P,h,w), ``trans`` (B,2P+1,h,w), ``scores`` (B,C,h,w) with C <= 32 against ``feat`` (B,D,h,w) with D <= 1024, h w <=
+    2^20), and an ``out`` that is not a dense float32 tensor of the expected shape or that shares memory with an input.
+    Returns the number of pairs P."""
+    r = _affinity_radius(radius, name)
+    P = len(affinity_offsets(r))
+    if beta is not None and (not _finite_number(beta) or beta <= 0):
+        raise WsdlError(f"{name}: beta {beta!r} must be a finite number > 0")
+    if num_iter is not None and (isinstance(num_iter, bool) or not isinstance(num_iter, int) or num_iter < 0):
+        raise WsdlError(f"{name}: num_iter {num_iter!r} must be an int >= 0")
+    if weights is not None:
+        try:
+            ok = len(weights) == 3 and all(_finite_number(v) for v in weights)
+        except TypeError:
+            ok = False
+        if not ok:
+            raise WsdlError(f"{name}: weights {weights!r} must be three finite numbers (bg, fg, neg)")
+    if eps is not None and (not _finite_number(eps) or eps <= 0):
+        raise WsdlError(f"{name}: eps {eps!r} must be a finite number > 0")
+    geom = None                                                     # (B, h, w, device) the tensors must agree on
+    for t, what, chan, dtype in ((feat, "feat", None, torch.float32), (labels, "labels", -1, torch.int64), (aff, "aff", P, torch.float32),
+                                 (trans, "trans", 2 * P + 1, torch.float32), (scores, "scores", None, torch.float32)):
+        if t is None:
+            continue
+        rank = 3 if chan == -1 else 4
+        if not torch.is_tensor(t) or t.dim() != rank:
+            raise WsdlError(f"{name}: {what} must be a {'(B,h,w)' if rank == 3 else '(B,C,h,w)'} tensor")
+        if t.dtype != dtype:
+            raise WsdlError(f"{name}: {what} must be {dtype}, got {t.dtype}")
+        if t.numel() == 0:
+            raise WsdlError(f"{name}: {what} {tuple(t.shape)} has an empty dimension")
+        if rank == 4 and chan is not None and t.shape[1] != chan:
+            raise WsdlError(f"{name}: {what} {tuple(t.shape)} must have {chan} planes at radius {r}")
+        if what == "feat" and t.shape[1] > 1024:
+            raise WsdlError(f"{name}: feat {tuple(t.shape)}: at most 1024 channels")
+        if what == "scores" and t.shape[1] > 32:
+            raise WsdlError(f"{name}: scores {tuple(t.shape)}: at most 32 channels")
+        g = (t.shape[0], t.shape[-2], t.shape[-1], t.device)
+        if g[1] * g[2] > 1 << 20:
+            raise WsdlError(f"{name}: {what} {tuple(t.shape)}: h w must be at most 2^20")
+        if geom is None:
+            geom = g
+        elif g != geom:
+            raise WsdlError(f"{name}: {what} {tuple(t.shape)} on {t.device} does not match the other tensors: batch {geom[0]}, size "
+                            f"{geom[1]} x {geom[2]} on {geom[3]}")
+    if out is not None:
+        if geom is None:
+            raise WsdlError(f"{name}: out= needs the tensor it belongs to (scores, or aff for the transitions)")
+        like = scores if scores is not None else None
+        shape = tuple(like.shape) if like is not None else (geom[0], 2 * P + 1, geom[1], geom[2])
+        if not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == shape and out.device == geom[3]
+                and out.is_contiguous() and not out.requires_grad):
+            raise WsdlError(f"{name}: out must be a dense float32 {shape} tensor on {geom[3]} that needs no gradient")
+        for t, what in ((scores, "scores"), (trans, "trans"), (aff, "aff")):
+            if t is not None and _shares_memory(out, t):
+                raise WsdlError(f"{name}: out shares memory with {what}")
+    return P
+
+
+def _shares_memory(a, b):
+    if a.device != b.device or a.numel() == 0 or b.numel() == 0:
+        return False
+    sa, sb = a.untyped_storage(), b.untyped_storage()
+    if sa.data_ptr() != sb.data_ptr():
+        return False
+
+    def span(t):
+        lo = t.storage_offset()
+        hi = lo + sum((n - 1) * s for n, s in zip(t.shape, t.stride())) + 1
+        return lo * t.element_size(), hi * t.element_size()
+    (a0, a1), (b0, b1) = span(a), span(b)
+    return a0 < b1 and b0 < a1
+
+
+def affinity_workspace(B, D, C_, H, W, radius=5):
+    """Bytes of scratch the affinity ops need at this geometry; 0 outside the limits (host-side)."""
+    try:
+        _affinity_radius(radius)
+    except WsdlError:
+        return 0
+    return int(lib().wsdl_affinity_workspace(int(B), int(D), int(C_), int(H), int(W), radius))
+
+
+def _affinity_ws(name, B, D, C_, H, W, radius, device):
+    nbytes = lib().wsdl_affinity_workspace(B, D, C_, H, W, radius)
+    if nbytes == 0:
+        raise WsdlError(f"{name}: bad geometry B={B} D={D} C={C_} h={H} w={W} radius={radius}")
+    return workspace(nbytes, device)
+
+
+class _PairAffinity(torch.autograd.Function):
+    """wsdl_affinity_pair_affinity / _backward: one launch each."""
+
+    @staticmethod
+    def forward(ctx, feat, radius, P):
+        feat = _dense(feat, "pair_affinity: feat")
+        B, D, H, W = feat.shape
+        aff = torch.empty(B, P, H, W, device=feat.device, dtype=torch.float32)
+        check(lib().wsdl_affinity_pair_affinity(_p(feat), B, D, H, W, radius, _p(aff), _stream()))
+        ctx.radius = radius
+        ctx.save_for_backward(feat, aff)
+        return aff
+
+    @staticmethod
+    def backward(ctx, daff):
+        feat, aff = ctx.saved_tensors
+        B, D, H, W = feat.shape
+        dfeat = torch.empty_like(feat)
+        check(lib().wsdl_affinity_pair_affinity_backward(_p(feat), _p(aff), _p(_dense(daff, "pair_affinity: upstream gradient")),
+                                                         _p(dfeat), B, D, H, W, ctx.radius, _stream()))
+        return dfeat, None, None
+
+
+def pair_affinity(feat, radius=5):
+    """AffinityNet's pairwise affinities (Ahn & Kwak, CVPR 2018) of float32 device features (B,D,h,w): (B,P,h,w) float32 with
+    ``a(p,j) = exp(-mean_d |f_d(p) - f_d(p + o_j)|)`` for the offsets ``o_j`` of ``affinity_offsets(radius)`` and exactly 0 where
+    ``p + o_j`` lies outside the image.  Differentiable in ``feat`` (closed-form gather, no atomics); one launch each way,
+    bitwise reproducible."""
+    P = check_affinity_options(radius, feat=feat, name="pair_affinity")
+    _req(feat, "pair_affinity: feat")
+    return _PairAffinity.apply(feat, radius, P)
+
+
+def affinity_pair_counts(labels, radius=5, ignore_index=255):
+    """int64 (3,) on the device: the numbers of bg-positive, fg-positive and negative pairs of int64 labels (B,h,w) over the
+    half disc of ``radius`` - both ends != ``ignore_index`` and equal 0 / equal > 0 / different; exact, no host read."""
+    check_affinity_options(radius, labels=labels, name="affinity_pair_counts")
+    _req(labels, "affinity_pair_counts: labels", torch.int64)
+    labels = labels.contiguous()
+    B, H, W = labels.shape
+    counts = torch.empty(3, device=labels.device, dtype=torch.int64)
+    ws = _affinity_ws("affinity_pair_counts", B, 1, 1, H, W, radius, labels.device)
+    check(lib().wsdl_affinity_pair_counts(_p(labels), B, H, W, radius, int(ignore_index), _p(counts), _p(ws), ws.numel(), _stream()))
+    return counts
+
+
+class _AffinityLoss(torch.autograd.Function):
+    """wsdl_affinity_loss: the loss and its complete gradient in five launches; the backward multiplies by the upstream
+    gradient only."""
+
+    @staticmethod
+    def forward(ctx, feat, labels, radius, ignore_index, weights, eps):
+        feat = _dense(feat, "affinity_loss: feat")
+        B, D, H, W = feat.shape
+        loss = torch.empty((), device=feat.device, dtype=torch.float32)
+        dfeat = torch.empty_like(feat) if ctx.needs_input_grad[0] else None      # (asked of the argument: `feat` may be a dense copy)
+        ws = _affinity_ws("affinity_loss", B, D, 1, H, W, radius, feat.device)
+        check(lib().wsdl_affinity_loss(_p(feat), _p(labels), _p(loss), _p(dfeat), None, B, D, H, W, radius, ignore_index, weights[0],
+                                       weights[1], weights[2], eps, _p(ws), ws.numel(), _stream()))
+        ctx.save_for_backward(dfeat)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dfeat,) = ctx.saved_tensors
+        return (_scaled_grad(dfeat, g),) + (None,) * 5
+
+
+def affinity_loss(feat, labels, *, radius=5, ignore_index=255, weights=AFFINITY_WEIGHTS, eps=1e-5):
+    """AffinityNet's training loss (PSA's ``train_aff``) on float32 device features (B,D,h,w) and int64 labels (B,h,w), a 0-dim
+    float32 tensor with its gradient.  Pairs over ``affinity_offsets(radius)``; a pair whose ends are both not
+    ``ignore_index`` is bg-positive (both 0), fg-positive (equal, > 0) or negative (different), anything else is not counted.
+    With the exact counts ``n`` over the batch: ``w_bg sum_bg -log(a + eps) / (n_bg + eps) + w_fg sum_fg -log(a + eps) / (n_fg +
+    eps) + w_neg sum_neg -log(1 + eps - a) / (n_neg + eps)``, ``weights = (w_bg, w_fg, w_neg)``.  An empty kind adds 0; without
+    a counted pair the loss and its gradient are 0.  Sums in double in a fixed order, no float atomics: bitwise reproducible;
+    no host read - a launch plan can hold the call and its backward."""
+    check_affinity_options(radius, feat=feat, labels=labels, weights=weights, eps=eps, name="affinity_loss")
+    _req(feat, "affinity_loss: feat")
+    _req(labels, "affinity_loss: labels", torch.int64)
+    return _AffinityLoss.apply(feat, labels.detach().contiguous(), radius, int(ignore_index), tuple(float(v) for v in weights),
+                               float(eps))
+
+
+def affinity_transitions(aff, beta=8.0, radius=5, out=None):
+    """The random walk's transition weights from affinities (B,P,h,w): (B,2P+1,h,w) float32 - plane 0 the pixel itself
+    (affinity 1), plane 1 + 2j its neighbour at offset j, plane 2 + 2j the neighbour at the reversed offset; ``a ** beta`` over
+    the sum of the pixel's row (>= 1 by the self term), 0 where the neighbour is outside the image.  Not differentiable."""
+    check_affinity_options(radius, aff=aff, out=out, beta=beta, name="affinity_transitions")
+    aff = _dense(aff.detach(), "affinity_transitions: aff")
+    B, P, H, W = aff.shape
+    if out is None:
+        out = torch.empty(B, 2 * P + 1, H, W, device=aff.device, dtype=torch.float32)
+    _req(out, "affinity_transitions: out")
+    check(lib().wsdl_affinity_transitions(_p(aff), _p(out), B, H, W, radius, float(beta), _stream()))
+    return out
+
+
+def random_walk(trans, scores, num_iter, *, radius=5, out=None):
+    """``num_iter`` steps ``m'_c(p) = sum_q w(p,q) m_c(q)`` of float32 device scores (B,C,h,w), 1 <= C <= 32, under the weights of
+    ``affinity_transitions`` - PSA's ``cam @ T^num_iter`` without the dense matrix.  Every step is a convex combination: the
+    result stays inside the input's range and a constant map is a fixed point; ``num_iter=0`` copies.  Not differentiable (the
+    inputs are detached); no host read, bitwise reproducible.  ``out``: a dense float32 tensor that receives the result; it
+    must not share memory with an input.  One launch per step: a launch plan can hold the call."""
+    check_affinity_options(radius, trans=trans, scores=scores, out=out, num_iter=num_iter, name="random_walk")
+    trans = _dense(trans.detach(), "random_walk: trans")
+    scores = _dense(scores.detach(), "random_walk: scores")
+    B, Cc, H, W = scores.shape
+    if out is None:
+        out = torch.empty_like(scores)
+    _req(out, "random_walk: out")
+    ws = _affinity_ws("random_walk", B, 1, Cc, H, W, radius, scores.device)
+    check(lib().wsdl_affinity_random_walk(_p(trans), _p(scores), _p(out), B, Cc, H, W, radius, num_iter, _p(ws),
+                                          ws.numel(), _stream()))
+    return out
+
+
+def affinity_random_walk(feat, scores, *, radius=5, beta=8.0, num_iter=256):
+    """``random_walk(affinity_transitions(pair_affinity(feat)), scores)``: scores (B,C,h,w) propagated under the affinities of
+    features (B,D,h,w) on the same h x w.  Not differentiable."""
+    check_affinity_options(radius, feat=feat, scores=scores, beta=beta, num_iter=num_iter, name="affinity_random_walk")
+    trans = affinity_transitions(pair_affinity(feat.detach(), radius), beta, radius)
+    return random_walk(trans, scores, num_iter, radius=radius)
+
+
 EDT_FAR = 1 << 30                       # WSDL_EDT_FAR: "no site" in a distance plane
 _EDT_METRICS = {"euclid": 0, "chebyshev": 1}
 
