@@ -1052,6 +1052,54 @@ int wsdl_affinity_transitions(const float* aff, float* trans, int B, int H, int 
 int wsdl_affinity_random_walk(const float* trans, const float* scores, float* out, int B, int C, int H, int W, int radius,
                               int num_iter, void* ws, size_t ws_bytes, wsdl_stream_t stream);
 
+/* ---- IRN boundary paths: affinities along the line between two pixels, their loss and the seed of the boundary CAM walk
+ * (Ahn, Cho & Kwak, CVPR 2019; csrc/boundary_affinity.hip) - the reference has no such step; this is the project's definition -
+ * One class-boundary map e (B,H,W) fp32 in [0,1], or its logits z; labels (B,H,W) int64 on the same H x W.
+ * Pairs: the half disc, the plane order and the validity rule of the AffinityNet block, 2 <= r <= 8.
+ * Paths: for the offset o_j = (dy,dx), dy >= 0, S_j is every integer point (y,x) with 0 <= y <= dy, min(0,dx) <= x <= max(0,dx) and
+ *   (dy x - dx y)^2 < dy^2 + dx^2 (integers: the distance to the line is below 1, IRN's "thick" line), in raster order of (y,x).
+ *   Both ends are members.  r = 2: 12 points over the 4 offsets, longest path 4; r = 5: 242, 11; r = 8: 1078, 16; the shortest
+ *   path has 2 points.  S_(1,-1) = (0,-1),(0,0),(1,-1),(1,0).  A path never leaves the rectangle between its ends, so every
+ *   point of a valid pair lies inside the image.
+ * Affinity: for a valid pair m = max over s in S_j of e(p + s) and a(p,j) = 1.0f - m, one float subtraction; exactly 0 for an
+ *   invalid pair (IRN pads the boundary map with 1).  arg(p,j), uint8: the FIRST point in path order that attains the maximum; a NaN
+ *   on the path gives NaN and arg is the first NaN (torch.max(dim)); 0 for an invalid pair.  A valid pair may have affinity 0 or 1.
+ *   The result equals a float32 evaluation bit for bit.  aff (B,P,H,W) fp32, arg (B,P,H,W) uint8.
+ * Backward: dedge(r) = - sum of daff(p,j) over every (j,t) with p = r - S_j[t], the pair (p,j) valid and arg(p,j) = t: gather
+ *   form, no atomics; the terms are added in (j,t) order in double and rounded once.
+ * Loss (IRN's pos_aff_loss / neg_aff_loss on the logits z of the boundary head): kinds, exact int64 counts and s_k = w_k / (n_k +
+ *   eps) as in the AffinityNet block.  zmax and its arg index over the path of the LOGITS (the sigmoid is monotone); a =
+ *   sigmoid(-zmax) = 1 / (1 + exp(zmax)) and 1 - a = sigmoid(zmax) = 1 / (1 + exp(-zmax)), each formed directly in double, never by
+ *   a subtraction:
+ *     L = s_bg sum_bg -log(a + eps) + s_fg sum_fg -log(a + eps) + s_neg sum_neg -log(sigmoid(zmax) + eps)
+ *   An empty kind contributes 0; no counted pair at all gives L = 0 and a zero gradient.  The pair coefficient dL/dzmax is c = s_k a (1 -
+ *   a) / (a + eps) for positives and c = -s_neg a (1 - a) / ((1 - a) + eps) for negatives, a float; it goes to the arg pixel only:
+ *   dL/dz(r) = sum of c(p,j) over the same (j,t) as above, in double, one rounding; (B,H,W) fp32.  The sums of the loss run in
+ *   double: one partial per workgroup, added in a fixed order by one workgroup; no float atomics - two calls give identical bits.
+ * Seed: out_c = scores_c * (1 - e), two float operations, for scores (B,C,H,W), 1 <= C <= 32: IRN's propagate_to_edge damps the seed
+ *   on predicted boundaries; the walk itself is wsdl_affinity_transitions / wsdl_affinity_random_walk on aff, unchanged.
+ * Limits: H, W >= 1, H W <= 2^20.  The path table is part of the code; every other value reaches the kernels by value or
+ *   through ws: a launch plan may hold the calls.
+ * wsdl_path_affinity_workspace: bytes of ws that suffice for wsdl_path_affinity_loss (16-byte aligned); 0 outside the limits
+ *   (host-side, no device touched).
+ * wsdl_path_affinity_paths: host-side, no device touched: the total number of path points at this radius, 0 for a radius outside
+ *   the range; lengths[P] (optional) receives the path lengths in plane order, points_yx[2 total] (optional) the points as y, x.
+ * wsdl_path_affinity: aff and, if arg is not null, arg.  One launch.
+ * wsdl_path_affinity_backward: dedge (B,H,W) from daff and arg.  One launch.
+ * wsdl_path_affinity_loss: counts (two launches), forward with the per-kind partial sums, the pair coefficients and the arg indices
+ *   in ws, the finalize (loss: one float) and, if dlogits is not null, the gather (B,H,W): five launches.  counts_out (optional):
+ *   int64[3].
+ * wsdl_path_affinity_seed: one launch; out may be scores. */
+size_t wsdl_path_affinity_workspace(int B, int H, int W, int radius);
+int wsdl_path_affinity_paths(int radius, int* lengths, int* points_yx);
+int wsdl_path_affinity(const float* edge, int B, int H, int W, int radius, float* aff, uint8_t* arg, wsdl_stream_t stream);
+int wsdl_path_affinity_backward(const float* daff, const uint8_t* arg, float* dedge, int B, int H, int W, int radius,
+                                wsdl_stream_t stream);
+int wsdl_path_affinity_loss(const float* logits, const long long* labels, float* loss, float* dlogits, long long* counts_out, int B,
+                            int H, int W, int radius, long long ignore_index, double w_bg, double w_fg, double w_neg, double eps,
+                            void* ws, size_t ws_bytes, wsdl_stream_t stream);
+int wsdl_path_affinity_seed(const float* edge, const float* scores, float* out, int B, int C, int H, int W, wsdl_stream_t stream);
+
 /* ---- refine_pseudo_mask inner step (TraditionalModel/AlternatingDirectionCutLoss.py:736-757) -
  * KL(softmax(X) || S) with log(X+1e-8), reduction 'batchmean', and its gradient wrt softmax(X). */
 int wsdl_kl_div_fwd_bwd(const float* xn, const float* s, float* loss, float* dxn, size_t n, int batch,

@@ -19,6 +19,8 @@ Mirrors reference TraditionalModel/PsuedoMasks.py: ``keep_largest`` (:15-21) and
     images (``ops.slic`` + ``ops.superpixel_snap``; off by default);
   * ``affinity``: optional random walk of the CAM, before its threshold, under the learned affinities of an ``AffinityNet``
     (``ops.affinity_random_walk``; off by default);
+  * ``boundary``: optional random walk of the CAM, before its threshold, under the boundary-path affinities of a
+    ``BoundaryNet`` (``ops.edge_random_walk``; off by default);
   * ``keep_largest(mask)`` is the reference's host function (skimage there; scipy.ndimage here - 8-connectivity, raster
     label order, first label wins area ties, empty mask returned unchanged).  ``generate_pseudo_masks`` itself labels
     the whole batch on the device (``keep_largest_batched`` -> ``ops.keep_largest_batched``, one workgroup per mask, the
@@ -101,6 +103,28 @@ def affinity_cam(images, cam, net, radius=5, beta=8.0, num_iter=256):
     return ops.bilinear_resize(walked, tuple(cam.shape[-2:]))[:, 0]
 
 
+def _boundary_options(boundary):
+    """The ``boundary=`` dict of ``generate_pseudo_masks`` with its defaults; ValueError / WsdlError for what it cannot be."""
+    if not isinstance(boundary, dict) or "net" not in boundary or set(boundary) - {"net", "radius", "beta", "num_iter"}:
+        raise ValueError("generate_pseudo_masks: boundary= is a dict of net, radius, beta, num_iter (net is required)")
+    opts = dict(radius=5, beta=10.0, num_iter=256)
+    opts.update(boundary)
+    ops.check_path_affinity_options(opts["radius"], beta=opts["beta"], num_iter=opts["num_iter"], name="generate_pseudo_masks: boundary")
+    return opts
+
+
+def boundary_cam(images, cam, net, radius=5, beta=10.0, num_iter=256):
+    """A CAM (B,H,W) propagated by IRN's boundary walk: ``edge = sigmoid(net(images))`` (a ``BoundaryNet``, no gradient), the CAM
+    resized to the edge size, ``ops.edge_random_walk`` as a one-channel map, resized back to H x W and divided by its per-image
+    maximum + 1e-5 (IRN's renormalisation; tensor operations on the device)."""
+    with torch.no_grad():
+        edge = torch.sigmoid(net(images))
+    small = ops.bilinear_resize(cam[:, None].float().contiguous(), tuple(edge.shape[-2:]))
+    walked = ops.edge_random_walk(edge, small, radius=radius, beta=beta, num_iter=num_iter)
+    back = ops.bilinear_resize(walked, tuple(cam.shape[-2:]))[:, 0]
+    return back / (back.amax(dim=(-2, -1), keepdim=True) + 1e-5)
+
+
 def _to_png_u8(t):
     """torchvision.utils.save_image's quantisation: mul(255).add_(0.5).clamp_(0, 255) -> uint8, HWC."""
     return t.mul(255).add(0.5).clamp(0, 255).permute(1, 2, 0).to(torch.uint8).cpu().numpy()
@@ -109,7 +133,7 @@ def _to_png_u8(t):
 def generate_pseudo_masks(loader, layercam_gen, cam_thresh=0.3, alpha=1.0, keep_largest_masks=True,
                           run_id="default", out_root="/content", max_images=500, write_png=True,
                           device="cuda", rank=0, world=1, keep_images=False, streams=3, keep_on_device=False,
-                          device_batch=0, pamr=None, superpixels=None, affinity=None):
+                          device_batch=0, pamr=None, superpixels=None, affinity=None, boundary=None):
     """``pamr``: None (the default: the masks are the thresholded CAMs, bit for bit as without the argument) or a dict of
     keyword arguments of ``ops.pamr`` (``{}``: its defaults) - the CAM WITHOUT its threshold is refined against the batch's
     images as a one-channel score map (pixel-adaptive mask refinement; the reference has no such step), the refined map is
@@ -124,7 +148,17 @@ def generate_pseudo_masks(loader, layercam_gen, cam_thresh=0.3, alpha=1.0, keep_
     device, in eval mode) and optionally ``radius`` (5), ``beta`` (8.0) and ``num_iter`` (256) - the CAM WITHOUT its threshold is
     resized to the net's feature size (``ops.bilinear_resize``), walked as a one-channel map under the affinities of the batch's
     features (``affinity_cam``; the reference has no such step) and resized back, then ``>= cam_thresh``, then ``keep_largest``
-    as before.  Combining it with ``pamr`` or ``superpixels`` is refused."""
+    as before.  Combining it with ``pamr`` or ``superpixels`` is refused.
+
+    ``boundary``: None (the default: bit for bit the path without the argument) or a dict with ``net`` (a ``BoundaryNet``, on the
+    device, in eval mode) and optionally ``radius`` (5), ``beta`` (10.0) and ``num_iter`` (256) - the CAM WITHOUT its threshold is
+    resized to the size of the net's boundary map, damped by ``1 - edge`` and walked as a one-channel map under the boundary-path
+    affinities (``boundary_cam``; the reference has no such step), resized back and divided by its per-image maximum, then
+    ``>= cam_thresh``, then ``keep_largest`` as before.  Combining it with ``pamr``, ``superpixels`` or ``affinity`` is refused."""
+    if boundary is not None:
+        if pamr is not None or superpixels is not None or affinity is not None:
+            raise ValueError("generate_pseudo_masks: boundary= cannot be combined with pamr=, superpixels= or affinity=")
+        boundary = _boundary_options(boundary)
     if affinity is not None:
         if pamr is not None or superpixels is not None:
             raise ValueError("generate_pseudo_masks: affinity= cannot be combined with pamr= or superpixels=")
@@ -171,6 +205,8 @@ def generate_pseudo_masks(loader, layercam_gen, cam_thresh=0.3, alpha=1.0, keep_
                 m = (superpixel_cam(imgs_d, cam, **superpixels) >= cam_thresh).to(torch.uint8)
             if affinity is not None:
                 m = (affinity_cam(imgs_d, cam, **affinity) >= cam_thresh).to(torch.uint8)
+            if boundary is not None:
+                m = (boundary_cam(imgs_d, cam, **boundary) >= cam_thresh).to(torch.uint8)
             if keep_largest_masks:
                 m = keep_largest_batched(m)
             m_host = m if keep_on_device and not write_png else m.cpu().numpy()

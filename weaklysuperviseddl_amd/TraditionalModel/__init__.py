@@ -11,4 +11,5 @@ from .AlternatingDirectionCutLoss import (  # noqa: F401
 from .AlternatingDirectionBoundaryLoss import ConstrainToBoundaryLossSingle  # noqa: F401
 from .ExtraUtilities import compute_iou_and_acc, download_data, load_split_data  # noqa: F401
 from .AffinityNet import AffinityNet, affinity_labels_from_cam, train_affinity_net  # noqa: F401
+from .BoundaryNet import BoundaryNet, train_boundary_net  # noqa: F401
 from .SegmentationDataset import PseudoSegmentationDataset, InMemoryPseudoDataset, images_to_tensor_device  # noqa: F401

@@ -152,6 +152,12 @@ SIGNATURES = {
     "wsdl_affinity_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _ll] + [C.c_double] * 4 + [_vp, _sz, _vp]),
     "wsdl_affinity_transitions": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_double, _vp]),
     "wsdl_affinity_random_walk": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "wsdl_path_affinity_workspace": (_sz, [_i] * 4),
+    "wsdl_path_affinity_paths": (_i, [_i, C.POINTER(_i), C.POINTER(_i)]),
+    "wsdl_path_affinity": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "wsdl_path_affinity_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "wsdl_path_affinity_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll] + [C.c_double] * 4 + [_vp, _sz, _vp]),
+    "wsdl_path_affinity_seed": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "wsdl_kl_div_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, _sz, _vp]),
     "wsdl_kl_div_per_image_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _sz, _vp, _sz, _vp]),
     "wsdl_refine_combine": (_i, [_vp, _vp, _vp, _vp, _f, _f, _vp, _i, _sz, _vp]),

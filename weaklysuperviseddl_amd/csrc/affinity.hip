@@ -15,12 +15,14 @@
 //                                   neighbours of c * sign(f(p) - f(q)); same tile, halo on all four sides; the 2 P
 //                                   coefficients of a pixel stay in registers over the channel loop.  No atomics.
 //   aff_counts_kernel / aff_counts_finalize_kernel / aff_loss_finalize_kernel : exact int64 counts, per-workgroup partials
-//                                   added in a fixed order by one workgroup.
+//                                   added in a fixed order by one workgroup (in affinity_pairs.h with the pair set: shared
+//                                   with boundary_affinity.hip).
 //   aff_transitions_kernel        : w(p,q) = a^beta / (1 + sum a^beta) over self + both orientations of every valid pair.
 //   aff_walk_kernel               : one random-walk step, one thread per pixel and plane, <= 2 P + 1 terms by fma in double in plane
 //                                   order, one rounding (as pamr.hip).
 // The offsets travel to the kernels by value (template parameter or AffOffsets): a launch plan copies argument values.
 #include "common.h"
+#include "affinity_pairs.h"
 
 #include <algorithm>
 #include <cmath>
@@ -28,56 +30,12 @@
 
 namespace {
 
-constexpr int kMinRadius = 2, kMaxRadius = 8;
-constexpr int kMaxP = 96;                  // pairs of the half disc at radius 8
 constexpr int kMaxChannels = 1024;         // D
 constexpr int kMaxScoreChannels = 32;      // C
-constexpr long long kMaxPlane = 1ll << 20; // h w
 constexpr int kTW = 32, kTH = 4;           // pixels of a workgroup's tile: one row = one LDS lane group
 constexpr int kPix = kTW * kTH;            // 128 pixels, two channel groups of 128 threads each
 constexpr int kKC = 16;                    // channels staged per step (8 per group)
 constexpr int kSlice = 32;                 // pairs whose group sums cross LDS per pass (32 x 128 doubles = 32 KiB)
-constexpr int kFinalizeThreads = 256;
-
-constexpr int half_disc(int r) {
-    int n = 0;
-    for (int y = 0; y < r; ++y)
-        for (int x = -(r - 1); x < r; ++x)
-            if ((y > 0 || x > 0) && x * x + y * y < r * r) ++n;
-    return n;
-}
-static_assert(half_disc(2) == 4 && half_disc(5) == 34 && half_disc(kMaxRadius) == kMaxP, "PSA's half disc");
-
-// offset j as (dy << 8) | (dx + 128), in the order of the header
-struct AffOffsets {
-    int n;
-    int o[kMaxP];
-};
-__host__ __device__ __forceinline__ int off_dy(int o) { return o >> 8; }
-__host__ __device__ __forceinline__ int off_dx(int o) { return (o & 255) - 128; }
-
-inline AffOffsets make_offsets(int r) {
-    AffOffsets a;
-    a.n = 0;
-    for (int j = 0; j < kMaxP; ++j) a.o[j] = 128;
-    for (int y = 0; y < r; ++y)
-        for (int x = -(r - 1); x < r; ++x)
-            if ((y > 0 || x > 0) && x * x + y * y < r * r) a.o[a.n++] = (y << 8) | (x + 128);
-    return a;
-}
-
-// 0 bg-positive, 1 fg-positive, 2 negative, -1 not counted
-__device__ __forceinline__ int pair_kind(long long lp, long long lq, long long ignore) {
-    if (lp == ignore || lq == ignore) return -1;
-    if (lp != lq) return 2;
-    return lp == 0 ? 0 : (lp > 0 ? 1 : -1);
-}
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 struct Tile {
     int b, y0, x0;
@@ -324,85 +282,6 @@ __global__ void __launch_bounds__(256) aff_grad_kernel(const float* __restrict__
     }
 }
 
-// ---------------------------------------------------------------------------------------------- counts and finalizes
-__global__ void __launch_bounds__(256) aff_counts_kernel(const long long* __restrict__ labels, long long* __restrict__ partial,
-                                                         int H, int W, long long n, AffOffsets off, long long ignore) {
-    __shared__ int s_cnt[3][4];
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    int cnt[3] = {0, 0, 0};
-    if (i < n) {
-        const long long HW = (long long)H * W;
-        const int p = (int)(i % HW), py = p / W, px = p - py * W;
-        const long long lp = labels[i];
-        for (int j = 0; j < off.n; ++j) {
-            const int dy = off_dy(off.o[j]), dx = off_dx(off.o[j]);
-            if (py + dy < H && px + dx >= 0 && px + dx < W) {
-                const int kind = pair_kind(lp, labels[i + dy * W + dx], ignore);
-                cnt[0] += kind == 0;
-                cnt[1] += kind == 1;
-                cnt[2] += kind == 2;
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int s = wave_sum_i(cnt[k]);
-        if ((threadIdx.x & 63) == 0) s_cnt[k][threadIdx.x >> 6] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int k = (int)threadIdx.x;
-        partial[(size_t)blockIdx.x * 3 + k] = (long long)s_cnt[k][0] + s_cnt[k][1] + s_cnt[k][2] + s_cnt[k][3];
-    }
-}
-
-// one workgroup: counts[k] = sum of the partials; scales[k] = w_k / (n_k + eps) (optional)
-__global__ void __launch_bounds__(kFinalizeThreads) aff_counts_finalize_kernel(const long long* __restrict__ partial, long long n_part,
-                                                                               long long* __restrict__ counts,
-                                                                               long long* __restrict__ counts_out,
-                                                                               double* __restrict__ scales, double w0, double w1,
-                                                                               double w2, double eps) {
-    __shared__ long long s[3][kFinalizeThreads];
-    long long c[3] = {0, 0, 0};
-    for (long long i = threadIdx.x; i < n_part; i += kFinalizeThreads)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) c[k] += partial[i * 3 + k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) s[k][threadIdx.x] = c[k];
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int k = (int)threadIdx.x;
-        long long tot = 0;
-        for (int i = 0; i < kFinalizeThreads; ++i) tot += s[k][i];
-        if (counts) counts[k] = tot;
-        if (counts_out) counts_out[k] = tot;
-        if (scales) scales[k] = (k == 0 ? w0 : (k == 1 ? w1 : w2)) / ((double)tot + eps);
-    }
-}
-
-// one workgroup: every thread adds its strided share of the partials in index order, the 256 shares are added in thread order
-__global__ void __launch_bounds__(kFinalizeThreads) aff_loss_finalize_kernel(const double* __restrict__ partial, long long n_part,
-                                                                             const double* __restrict__ scales,
-                                                                             float* __restrict__ loss) {
-    __shared__ double s[3][kFinalizeThreads];
-    double c[3] = {0.0, 0.0, 0.0};
-    for (long long i = threadIdx.x; i < n_part; i += kFinalizeThreads)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) c[k] += partial[i * 3 + k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) s[k][threadIdx.x] = c[k];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tot = 0.0;
-        for (int k = 0; k < 3; ++k) {
-            double sk = 0.0;
-            for (int i = 0; i < kFinalizeThreads; ++i) sk += s[k][i];
-            tot += scales[k] * sk;                           // (an empty kind has no term: 0)
-        }
-        *loss = (float)tot;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------- transitions and walk
 __global__ void __launch_bounds__(256) aff_transitions_kernel(const float* __restrict__ aff, float* __restrict__ trans, int H, int W,
                                                               long long n, AffOffsets off, double beta) {
@@ -497,11 +376,6 @@ inline bool geometry(int B, int D, int C, int H, int W, int radius, Geometry* g)
     return true;
 }
 
-inline bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + b_bytes && y < x + a_bytes;
-}
-
 template <int R>
 void launch_distance(bool loss, const float* f, float* out, const long long* labels, const double* scales, double* partial, int D,
                      int H, int W, const Geometry& g, long long ignore, double eps, hipStream_t s) {
@@ -547,11 +421,7 @@ void gradient(int radius, const float* f, const float* coef, const float* mul, f
 
 void counts(const long long* labels, long long* cpart, long long* counts_ws, long long* counts_out, double* scales, int B, int H, int W,
             int radius, long long ignore, double w0, double w1, double w2, double eps, const Geometry& g, hipStream_t s) {
-    const AffOffsets off = make_offsets(radius);
-    hipLaunchKernelGGL(aff_counts_kernel, dim3((unsigned)g.count_blocks), dim3(256), 0, s, labels, cpart, H, W, (long long)B * H * W, off,
-                       ignore);
-    hipLaunchKernelGGL(aff_counts_finalize_kernel, dim3(1), dim3(kFinalizeThreads), 0, s, (const long long*)cpart, g.count_blocks,
-                       counts_ws, counts_out, scales, w0, w1, w2, eps);
+    launch_counts(labels, cpart, counts_ws, counts_out, scales, B, H, W, radius, ignore, w0, w1, w2, eps, g.count_blocks, s);
 }
 
 // One plane per workgroup row keeps the most workgroups in flight: a step is a chain of dependent load batches, bound by
@@ -560,15 +430,6 @@ void walk_once(const float* w, const float* src, float* dst, int B, int C, int H
     const int bpp = (int)(((long long)H * W + 255) / 256);
     hipLaunchKernelGGL(aff_walk_kernel, dim3((unsigned)((long long)B * C * bpp)), dim3(256), 0, s, w, src, dst, C, H, W, bpp, off);
 }
-
-#define AFF_WS_CHECK(name, need)                                                                              \
-    do {                                                                                                      \
-        WSDL_REQUIRE(ws && reinterpret_cast<uintptr_t>(ws) % 16 == 0, name ": ws must be 16-byte aligned");   \
-        if (ws_bytes < (need)) {                                                                              \
-            wsdl::set_error(name ": workspace too small");                                                    \
-            return WSDL_EWORKSPACE;                                                                           \
-        }                                                                                                     \
-    } while (0)
 
 }  // namespace
 

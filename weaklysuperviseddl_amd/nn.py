@@ -850,3 +850,38 @@ class RandomWalk(nn.Module):
 
     def extra_repr(self):
         return f"radius={self.radius}, beta={self.beta}, num_iter={self.num_iter}"
+
+
+class PathAffinityLoss(nn.Module):
+    """IRN's boundary loss (Ahn, Cho & Kwak, CVPR 2019; ``ops.path_affinity_loss``) as a module without parameters:
+    ``forward(edge_logits, labels)`` for the float32 logits (B,1,h,w) or (B,h,w) of a boundary head and int64 labels (B,h,w) at
+    the logit size - 0 background, > 0 a class, ``ignore_index`` unsure (``affinity_labels_from_cam``).  ``weights`` are those of
+    the bg-positive, fg-positive and negative terms.  A plain module: not one of the segmentation criteria ``train_step`` takes."""
+
+    def __init__(self, radius=5, ignore_index=255, weights=ops.AFFINITY_WEIGHTS):
+        super().__init__()
+        ops.check_path_affinity_options(radius, weights=weights, name="PathAffinityLoss")
+        self.radius, self.ignore_index, self.weights = radius, int(ignore_index), tuple(float(v) for v in weights)
+
+    def forward(self, edge_logits, labels):
+        return ops.path_affinity_loss(edge_logits, labels, radius=self.radius, ignore_index=self.ignore_index, weights=self.weights)
+
+    def extra_repr(self):
+        return f"radius={self.radius}, ignore_index={self.ignore_index}, weights={self.weights}"
+
+
+class EdgeRandomWalk(nn.Module):
+    """IRN's CAM propagation as a module without parameters: ``forward(edge, scores)`` is ``ops.edge_random_walk(edge, scores,
+    radius=, beta=, num_iter=)`` - scores (B,C,h,w) damped by ``1 - edge`` and walked ``num_iter`` steps under the path affinities
+    of the boundary map (B,1,h,w) or (B,h,w).  Not differentiable: the result has no ``grad_fn``."""
+
+    def __init__(self, radius=5, beta=10.0, num_iter=256):
+        super().__init__()
+        ops.check_path_affinity_options(radius, beta=beta, num_iter=num_iter, name="EdgeRandomWalk")
+        self.radius, self.beta, self.num_iter = radius, float(beta), num_iter
+
+    def forward(self, edge, scores):
+        return ops.edge_random_walk(edge, scores, radius=self.radius, beta=self.beta, num_iter=self.num_iter)
+
+    def extra_repr(self):
+        return f"radius={self.radius}, beta={self.beta}, num_iter={self.num_iter}"

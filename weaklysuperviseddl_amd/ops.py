@@ -3001,7 +3001,164 @@ def affinity_random_walk(feat, scores, *, radius=5, beta=8.0, num_iter=256):
     return random_walk(trans, scores, num_iter, radius=radius)
 
 
-EDT_FAR = 1 << 30                       # WSDL_EDT_FAR: "no site" in a distance plane
+# ---- IRN boundary paths: affinities along the line between two pixels, their loss, the boundary CAM walk
+# (csrc/boundary_affinity.hip; include/wsdl_hip.h "IRN boundary paths")
+def affinity_paths(radius):
+    """The path of every offset of ``affinity_offsets(radius)``, in the same order: a list of lists of ``(dy, dx)`` - every
+    integer point of the rectangle between (0,0) and the offset whose distance to the line between them is below 1 (IRN's
+    thick line), in raster order; both ends are members.  Host only: the table comes from the library, no device is touched."""
+    r = _affinity_radius(radius, "affinity_paths")
+    P = len(affinity_offsets(r))
+    total = lib().wsdl_path_affinity_paths(r, None, None)
+    lengths, points = (C.c_int * P)(), (C.c_int * (2 * total))()
+    if lib().wsdl_path_affinity_paths(r, lengths, points) != total:
+        raise WsdlError(f"affinity_paths: the library has no path table for radius {r}")
+    out, at = [], 0
+    for n in lengths:
+        out.append([(points[2 * s], points[2 * s + 1]) for s in range(at, at + n)])
+        at += n
+    return out
+
+
+def _edge_plane(edge, name, what="edge"):
+    """The (B,h,w) view of a boundary map given as (B,h,w) or (B,1,h,w); WsdlError for anything else (host-side)."""
+    if not torch.is_tensor(edge) or edge.dim() not in (3, 4) or (edge.dim() == 4 and edge.shape[1] != 1):
+        raise WsdlError(f"{name}: {what} must be a (B,h,w) or (B,1,h,w) tensor")
+    if edge.dtype != torch.float32:
+        raise WsdlError(f"{name}: {what} must be torch.float32, got {edge.dtype}")
+    if edge.numel() == 0:
+        raise WsdlError(f"{name}: {what} {tuple(edge.shape)} has an empty dimension")
+    return edge[:, 0] if edge.dim() == 4 else edge
+
+
+def check_path_affinity_options(radius=5, *, edge=None, labels=None, scores=None, out=None, beta=None, num_iter=None, weights=None,
+                                eps=None, name="path_affinity"):
+    """Host-side validation of the boundary-path ops, before any device call - ``check_affinity_options`` with a boundary map
+    (or its logits) ``edge`` (B,h,w) or (B,1,h,w) float32 in place of the features: WsdlError for a bad radius, beta, num_iter,
+    weights or eps, for tensors of the wrong rank, type or place, for ``labels`` (B,h,w) int64 or ``scores`` (B,C,h,w), C <= 32,
+    that do not match the map's batch, size (h w <= 2^20) and device, and for an ``out`` that is not a dense float32 tensor of
+    the scores' shape or that shares memory with the scores or the map.  Returns the number of pairs P."""
+    plane = None if edge is None else _edge_plane(edge, name)[:, None]
+    P = check_affinity_options(radius, feat=plane, labels=labels, scores=scores, out=out, beta=beta, num_iter=num_iter, weights=weights,
+                               eps=eps, name=name)
+    if out is not None and plane is not None and _shares_memory(out, plane):
+        raise WsdlError(f"{name}: out shares memory with edge")
+    return P
+
+
+def _path_affinity_ws(name, B, H, W, radius, device):
+    nbytes = lib().wsdl_path_affinity_workspace(B, H, W, radius)
+    if nbytes == 0:
+        raise WsdlError(f"{name}: bad geometry B={B} h={H} w={W} radius={radius}")
+    return workspace(nbytes, device)
+
+
+class _PathAffinity(torch.autograd.Function):
+    """wsdl_path_affinity / _backward: one launch each; the arg indices are what the backward needs."""
+
+    @staticmethod
+    def forward(ctx, edge, radius, P):
+        edge = _dense(edge, "path_affinity: edge")
+        B, H, W = edge.shape
+        aff = torch.empty(B, P, H, W, device=edge.device, dtype=torch.float32)
+        arg = torch.empty(B, P, H, W, device=edge.device, dtype=torch.uint8)
+        check(lib().wsdl_path_affinity(_p(edge), B, H, W, radius, _p(aff), _p(arg), _stream()))
+        ctx.radius = radius
+        ctx.save_for_backward(arg)
+        ctx.mark_non_differentiable(arg)
+        return aff, arg
+
+    @staticmethod
+    def backward(ctx, daff, _darg):
+        (arg,) = ctx.saved_tensors
+        B, P, H, W = arg.shape
+        dedge = torch.empty(B, H, W, device=arg.device, dtype=torch.float32)
+        check(lib().wsdl_path_affinity_backward(_p(_dense(daff, "path_affinity: upstream gradient")), _p(arg), _p(dedge), B, H, W,
+                                                ctx.radius, _stream()))
+        return dedge, None, None
+
+
+def path_affinity(edge, radius=5, *, return_arg=False):
+    """IRN's boundary-path affinities (Ahn, Cho & Kwak, CVPR 2019) of a float32 device boundary map (B,h,w) or (B,1,h,w) in
+    [0, 1]: (B,P,h,w) float32 with ``a(p,j) = 1 - max of edge over the path`` between ``p`` and ``p + o_j``
+    (``affinity_paths(radius)``), one float subtraction, and exactly 0 where ``p + o_j`` lies outside the image.  A NaN on the
+    path gives NaN.  Differentiable in ``edge``: the gradient of a pair goes to the first point of its path that attains the
+    maximum (gather form, no atomics); one launch each way, bitwise reproducible.  ``return_arg``: also the uint8 (B,P,h,w)
+    index of that point in its path."""
+    P = check_path_affinity_options(radius, edge=edge, name="path_affinity")
+    _req(edge, "path_affinity: edge")
+    plane = _edge_plane(edge, "path_affinity")
+    if return_arg or (plane.requires_grad and torch.is_grad_enabled()):
+        aff, arg = _PathAffinity.apply(plane, radius, P)
+        return (aff, arg) if return_arg else aff
+    plane = _dense(plane.detach(), "path_affinity: edge")
+    B, H, W = plane.shape
+    aff = torch.empty(B, P, H, W, device=plane.device, dtype=torch.float32)
+    check(lib().wsdl_path_affinity(_p(plane), B, H, W, radius, _p(aff), None, _stream()))
+    return aff
+
+
+class _PathAffinityLoss(torch.autograd.Function):
+    """wsdl_path_affinity_loss: the loss and its complete gradient in five launches; the backward multiplies by the upstream
+    gradient only."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, radius, ignore_index, weights, eps, counts_out):
+        logits = _dense(logits, "path_affinity_loss: edge_logits")
+        B, H, W = logits.shape
+        loss = torch.empty((), device=logits.device, dtype=torch.float32)
+        dz = torch.empty_like(logits) if ctx.needs_input_grad[0] else None    # (asked of the argument: `logits` may be a dense copy)
+        ws = _path_affinity_ws("path_affinity_loss", B, H, W, radius, logits.device)
+        check(lib().wsdl_path_affinity_loss(_p(logits), _p(labels), _p(loss), _p(dz), _p(counts_out), B, H, W, radius, ignore_index,
+                                            weights[0], weights[1], weights[2], eps, _p(ws), ws.numel(), _stream()))
+        ctx.save_for_backward(dz)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dz,) = ctx.saved_tensors
+        return (_scaled_grad(dz, g),) + (None,) * 6
+
+
+def path_affinity_loss(edge_logits, labels, *, radius=5, ignore_index=255, weights=AFFINITY_WEIGHTS, eps=1e-5, counts_out=None):
+    """IRN's boundary loss (``pos_aff_loss`` / ``neg_aff_loss``) on the float32 device logits (B,h,w) or (B,1,h,w) of a boundary
+    head and int64 labels (B,h,w), a 0-dim float32 tensor with its gradient.  Pair kinds and exact counts ``n`` as in
+    ``affinity_loss``; with ``zmax`` the largest logit on a pair's path, ``a = sigmoid(-zmax)`` its affinity:
+    ``w_bg sum_bg -log(a + eps) / (n_bg + eps) + w_fg sum_fg -log(a + eps) / (n_fg + eps) + w_neg sum_neg -log(sigmoid(zmax) +
+    eps) / (n_neg + eps)`` - both sigmoids formed directly in double, so logits of +-40 stay finite.  The gradient of a pair goes
+    to the pixel that holds ``zmax``.  An empty kind adds 0; without a counted pair the loss and its gradient are 0.  Sums in
+    double in a fixed order, no float atomics: bitwise reproducible; no host read - a launch plan can hold the call and its
+    backward.  ``counts_out``: a dense int64 (3,) device tensor that receives the numbers of bg-positive, fg-positive and negative
+    pairs the call counted."""
+    check_path_affinity_options(radius, edge=edge_logits, labels=labels, weights=weights, eps=eps, name="path_affinity_loss")
+    _req(edge_logits, "path_affinity_loss: edge_logits")
+    _req(labels, "path_affinity_loss: labels", torch.int64)
+    if counts_out is not None:
+        if not (torch.is_tensor(counts_out) and counts_out.dtype == torch.int64 and tuple(counts_out.shape) == (3,)
+                and counts_out.is_contiguous() and counts_out.device == labels.device):
+            raise WsdlError(f"path_affinity_loss: counts_out must be a dense int64 (3,) tensor on {labels.device}")
+    return _PathAffinityLoss.apply(_edge_plane(edge_logits, "path_affinity_loss", "edge_logits"), labels.detach().contiguous(), radius,
+                                   int(ignore_index), tuple(float(v) for v in weights), float(eps), counts_out)
+
+
+def edge_random_walk(edge, scores, *, radius=5, beta=10.0, num_iter=256, out=None):
+    """IRN's ``propagate_to_edge``: ``random_walk(affinity_transitions(path_affinity(edge), beta), scores * (1 - edge))`` for a
+    float32 device boundary map (B,h,w) or (B,1,h,w) and scores (B,C,h,w), 1 <= C <= 32, on the same h x w - the seed is damped on
+    predicted boundaries, then walked ``num_iter`` steps on the stencil; a pair whose path crosses a boundary of 1 has affinity 0
+    and carries nothing.  Not differentiable; no host read: a launch plan can hold the call.  ``out``: a dense float32 tensor
+    that receives the result; it must not share memory with an input."""
+    check_path_affinity_options(radius, edge=edge, scores=scores, out=out, beta=beta, num_iter=num_iter, name="edge_random_walk")
+    _req(edge, "edge_random_walk: edge")
+    plane = _dense(_edge_plane(edge, "edge_random_walk").detach(), "edge_random_walk: edge")
+    scores = _dense(scores.detach(), "edge_random_walk: scores")
+    B, Cc, H, W = scores.shape
+    seed = torch.empty_like(scores)
+    check(lib().wsdl_path_affinity_seed(_p(plane), _p(scores), _p(seed), B, Cc, H, W, _stream()))
+    trans = affinity_transitions(path_affinity(plane, radius), beta, radius)
+    return random_walk(trans, seed, num_iter, radius=radius, out=out)
+
+
+EDT_FAR = 1 << 30                      # WSDL_EDT_FAR: "no site" in a distance plane
 _EDT_METRICS = {"euclid": 0, "chebyshev": 1}
 
 
