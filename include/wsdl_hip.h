@@ -1100,6 +1100,40 @@ int wsdl_path_affinity_loss(const float* logits, const long long* labels, float*
                             void* ws, size_t ws_bytes, wsdl_stream_t stream);
 int wsdl_path_affinity_seed(const float* edge, const float* scores, float* out, int B, int C, int H, int W, wsdl_stream_t stream);
 
+/* ---- GroupNorm (Wu & He, ECCV 2018; torch.nn.functional.group_norm) with an optional fused ReLU, and its complete backward
+ * (csrc/group_norm.hip) - the reference has no such layer; IRN's boundary head puts GroupNorm(4, 32) behind its reductions -
+ * x, y, dy, dx (B,C,HW) fp32 dense; G groups of C / G consecutive channels; gamma, beta (C) fp32, each may be null (1 and 0).
+ * With n = (C / G) HW, over group (b,g): mean = sum x / n, var = sum (x - mean)^2 / n (biased), rstd = 1 / sqrt(var + eps);
+ *   y = (x - mean) rstd gamma[c] + beta[c], then max(., 0) if relu (+0 for -0 and for a NaN, as wsdl_affine_act_fwd).
+ * Train and eval are the same function; there are no running statistics.  A group of one element is accepted (torch refuses it):
+ * y = beta and dx = 0 exactly.  A constant group has var = 0 and stays finite for eps > 0.  A NaN poisons its own group only.
+ * Backward, with m the ReLU mask (y > 0: 0 at exactly 0, as ATen; 1 without relu), g = dy m gamma[c], xhat = (x - mean) rstd:
+ *   dx = rstd (g - mean_grp(g) - xhat mean_grp(g xhat)),  dgamma[c] = sum_{b,hw} dy m xhat,  dbeta[c] = sum_{b,hw} dy m.
+ *   dx, dgamma and dbeta may each be null: only what is asked for is computed.  accumulate_param_grads: dgamma / dbeta receive
+ *   old + (float)sum, one float addition, instead of (float)sum.
+ * Arithmetic: the group statistics and every backward sum are accumulated in double.  The second moment is taken about a sample
+ *   of the data (per chunk: sum (x - K)^2 with K the chunk's first element) and the chunks' (n, mean, M2) are combined; nothing
+ *   is formed as E[x^2] - E[x]^2.  save_mean / save_rstd (B,G) are DOUBLE: rounding the mean of data at offset 1000 to a float
+ *   moves xhat by up to 6e-5 at sigma = 0.5, the size of the whole float32 error there.  Every element of y and dx is computed in
+ *   double and rounded once.  All partials are combined in a fixed order, no atomics: two calls give identical bits, and so
+ *   does a replayed plan.
+ * Parallelism: a plane (b,c) is cut into P chunks of L floats (L a multiple of 1024, >= 2048, chosen so that B C P is about 1024
+ *   where the tensor allows it); one 256-thread workgroup per chunk in every pass; per-chunk partials in ws; one wave per group /
+ *   per channel combines them.  float4 accesses where HW % 4 == 0 and the pointers are 16-byte aligned, one float per lane
+ *   otherwise.
+ * Limits, each refused with an error: B, C, HW >= 1; G >= 1 and C % G == 0; B C HW <= 2^31 - 1; ws_bytes >= the workspace
+ *   query, ws 8-byte aligned; eps finite and >= 0; relu in the backward needs y.
+ * wsdl_group_norm_workspace: bytes of ws that suffice for either direction; 0 for a bad geometry (host-side, no device touched).
+ * wsdl_group_norm_fwd: three launches (chunk statistics, one wave per group, apply).  y may be x.
+ * wsdl_group_norm_bwd: y is read only if relu.  Three launches (chunk sums, one wave per group and per channel, dx), two without
+ *   dx.  No host read and no allocation in either: a launch plan may hold both. */
+size_t wsdl_group_norm_workspace(int B, int C, int HW, int G);
+int wsdl_group_norm_fwd(const float* x, const float* gamma, const float* beta, float* y, double* save_mean, double* save_rstd, int B,
+                        int C, int HW, int G, double eps, int relu, void* ws, size_t ws_bytes, wsdl_stream_t stream);
+int wsdl_group_norm_bwd(const float* x, const float* dy, const float* y, const float* gamma, const double* save_mean,
+                        const double* save_rstd, float* dx, float* dgamma, float* dbeta, int B, int C, int HW, int G, int relu,
+                        int accumulate_param_grads, void* ws, size_t ws_bytes, wsdl_stream_t stream);
+
 /* ---- refine_pseudo_mask inner step (TraditionalModel/AlternatingDirectionCutLoss.py:736-757) -
  * KL(softmax(X) || S) with log(X+1e-8), reduction 'batchmean', and its gradient wrt softmax(X). */
 int wsdl_kl_div_fwd_bwd(const float* xn, const float* s, float* loss, float* dxn, size_t n, int batch,

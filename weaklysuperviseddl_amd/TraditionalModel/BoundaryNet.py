@@ -8,9 +8,12 @@ trunk the project already builds (``FrozenResNetCAM``): five bias-free 1 x 1 red
 convolution with bias to a single map: the boundary LOGITS.  Their sigmoid is the class-boundary map; the affinity of two pixels
 is one minus its maximum on the line between them (``ops.path_affinity``).  The logits feed ``ops.path_affinity_loss`` in training
 and, through a sigmoid, ``ops.edge_random_walk`` when a CAM is turned into a pseudo mask
-(``generate_pseudo_masks(boundary=...)``).  IRN puts GroupNorm behind its reductions; the library has no GroupNorm, so it is left
-out (as ``AffinityNet`` leaves out PSA's ELUs).  IRN's second branch - the displacement field and the instance centroids - is not
-built: the data set has one object per image.
+(``generate_pseudo_masks(boundary=...)``).  IRN puts GroupNorm(4, 32) behind its reductions: the five stages' activation scales
+differ by orders of magnitude, and the normalisation is what lets the head train from a random start.  ``norm="group"`` builds it
+(``wnn.GroupNorm`` with the ReLU fused); the default ``norm=None`` is the bare head of before, module for module.  One
+difference to IRN remains: the project's order is reduce -> normalise + ReLU -> resize for every stage, where IRN resizes the
+three coarser stages BEFORE their ReLU (as ``AffinityNet`` notes its missing ELUs).  IRN's second branch - the displacement
+field and the instance centroids - is not built: the data set has one object per image.
 """
 import torch
 import torch.nn as nn
@@ -23,12 +26,19 @@ EDGE_CHANNELS = 32
 
 
 class BoundaryNet(nn.Module):
-    """``BoundaryNet(trunk)``: ``trunk`` has ``layer0 .. layer4`` (a ``FrozenResNetCAM``); it stays frozen and in eval mode.
-    ``forward(x)`` for images (B,3,H,W) returns the boundary logits (B,1,H/4,W/4).  Trainable: ``fc_edge1 .. fc_edge5`` (IRN's
-    names), bias-free 1 x 1 convolutions to 32 channels, and ``fc_edge6``, 160 -> 1 with bias."""
+    """``BoundaryNet(trunk, norm=None, groups=4)``: ``trunk`` has ``layer0 .. layer4`` (a ``FrozenResNetCAM``); it stays frozen
+    and in eval mode.  ``forward(x)`` for images (B,3,H,W) returns the boundary logits (B,1,H/4,W/4).  Trainable: ``fc_edge1 ..
+    fc_edge5`` (IRN's names), bias-free 1 x 1 convolutions to 32 channels, and ``fc_edge6``, 160 -> 1 with bias.  ``norm="group"``
+    adds ``gn_edge1 .. gn_edge5``, ``wnn.GroupNorm(groups, 32, relu=True)``, behind the five reductions in place of the bare ReLU;
+    with ``norm=None`` the network has the same modules, state-dict keys and initial weights as before the option existed."""
 
-    def __init__(self, trunk):
+    def __init__(self, trunk, norm=None, groups=4):
         super().__init__()
+        if norm not in (None, "group"):
+            raise ValueError(f"BoundaryNet: norm {norm!r} must be None or 'group'")
+        if norm == "group":
+            ops.check_group_norm_options(groups, EDGE_CHANNELS, name="BoundaryNet")
+        self.norm = norm
         self.trunk = trunk
         for p in self.trunk.parameters():
             p.requires_grad = False
@@ -41,10 +51,16 @@ class BoundaryNet(nn.Module):
         for conv in self._convs():
             nn.init.kaiming_normal_(conv.weight)
         nn.init.zeros_(self.fc_edge6.bias)
+        if norm == "group":                     # (ones and zeros: no random draw, the convolutions above are the same either way)
+            for i in range(1, 6):
+                setattr(self, f"gn_edge{i}", wnn.GroupNorm(groups, EDGE_CHANNELS, relu=True))
         self.trunk.eval()
 
     def _convs(self):
         return (self.fc_edge1, self.fc_edge2, self.fc_edge3, self.fc_edge4, self.fc_edge5, self.fc_edge6)
+
+    def _norms(self):
+        return tuple(getattr(self, f"gn_edge{i}") for i in range(1, 6)) if self.norm == "group" else ()
 
     def train(self, mode=True):
         super().train(mode)
@@ -52,7 +68,7 @@ class BoundaryNet(nn.Module):
         return self
 
     def head_parameters(self):
-        return [p for conv in self._convs() for p in conv.parameters()]
+        return [p for m in self._convs() + self._norms() for p in m.parameters()]
 
     def forward(self, x):
         t = self.trunk
@@ -63,7 +79,8 @@ class BoundaryNet(nn.Module):
             f3 = t.layer3(f2)
             f4 = t.layer4(f3)
         size = tuple(f1.shape[-2:])
-        maps = [ops.relu(conv(f)) for conv, f in zip(self._convs(), (f0, f1, f2, f3, f4))]
+        acts = self._norms() or (ops.relu,) * 5
+        maps = [act(conv(f)) for act, conv, f in zip(acts, self._convs(), (f0, f1, f2, f3, f4))]
         maps = [m if tuple(m.shape[-2:]) == size else ops.bilinear_resize(m, size) for m in maps]
         return self.fc_edge6(ops.concat_channels(maps))
 

@@ -158,6 +158,9 @@ SIGNATURES = {
     "wsdl_path_affinity_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "wsdl_path_affinity_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll] + [C.c_double] * 4 + [_vp, _sz, _vp]),
     "wsdl_path_affinity_seed": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "wsdl_group_norm_workspace": (_sz, [_i] * 4),
+    "wsdl_group_norm_fwd": (_i, [_vp] * 6 + [_i] * 4 + [C.c_double, _i, _vp, _sz, _vp]),
+    "wsdl_group_norm_bwd": (_i, [_vp] * 9 + [_i] * 6 + [_vp, _sz, _vp]),
     "wsdl_kl_div_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, _sz, _vp]),
     "wsdl_kl_div_per_image_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _sz, _vp, _sz, _vp]),
     "wsdl_refine_combine": (_i, [_vp, _vp, _vp, _vp, _f, _f, _vp, _i, _sz, _vp]),

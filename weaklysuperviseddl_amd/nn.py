@@ -68,6 +68,31 @@ class BatchNorm2d(nn.Module):
                               self.training)
 
 
+class GroupNorm(nn.Module):
+    """``torch.nn.GroupNorm`` on the HIP path (``ops.group_norm``): torch's parameter names and initial values (``weight`` ones,
+    ``bias`` zeros), so its state dict loads; no buffers, train and eval are the same function.  ``relu=True`` fuses the
+    activation into the same launches.  Unlike torch's, a group of one element is accepted."""
+
+    def __init__(self, num_groups, num_channels, eps=1e-5, affine=True, relu=False):
+        super().__init__()
+        ops.check_group_norm_options(num_groups, num_channels, eps, name="GroupNorm")
+        self.num_groups, self.num_channels, self.eps, self.affine, self.relu = num_groups, num_channels, eps, bool(affine), bool(relu)
+        if self.affine:
+            self.weight = nn.Parameter(torch.ones(num_channels))
+            self.bias = nn.Parameter(torch.zeros(num_channels))
+        else:
+            self.register_parameter("weight", None)
+            self.register_parameter("bias", None)
+
+    def forward(self, x):
+        if x.dim() < 2 or x.shape[1] != self.num_channels:
+            raise ops.WsdlError(f"GroupNorm: expected (B, {self.num_channels}, *), got {tuple(x.shape)}")
+        return ops.group_norm(x, self.num_groups, self.weight, self.bias, self.eps, self.relu)
+
+    def extra_repr(self):
+        return f"{self.num_groups}, {self.num_channels}, eps={self.eps}, affine={self.affine}, relu={self.relu}"
+
+
 class ReLU(nn.Module):
     def forward(self, x):
         # fused into the producing kernel inside the models; stand-alone (hooked / called directly) it is one launch

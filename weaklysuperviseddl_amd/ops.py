@@ -1469,6 +1469,122 @@ def relu(x):
     return _AffineAct.apply(x, None, None, True)
 
 
+def check_group_norm_options(num_groups, num_channels=None, eps=1e-5, name="group_norm"):
+    """Host-side validation of GroupNorm's options, before any device call: WsdlError unless ``num_groups`` is an int >= 1 that
+    divides ``num_channels`` (an int >= 1, if given) and ``eps`` is a finite number >= 0."""
+    if isinstance(num_groups, bool) or not isinstance(num_groups, int) or num_groups < 1:
+        raise WsdlError(f"{name}: num_groups {num_groups!r} must be an int >= 1")
+    if num_channels is not None:
+        if isinstance(num_channels, bool) or not isinstance(num_channels, int) or num_channels < 1:
+            raise WsdlError(f"{name}: num_channels {num_channels!r} must be an int >= 1")
+        if num_channels % num_groups:
+            raise WsdlError(f"{name}: num_groups {num_groups} does not divide the {num_channels} channels")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not (0.0 <= float(eps) < float("inf")):
+        raise WsdlError(f"{name}: eps {eps!r} must be a finite number >= 0")
+
+
+def _group_norm_ws(B, Cc, HW, G, device):
+    nbytes = _ws_bytes("wsdl_group_norm_workspace", B, Cc, HW, G)
+    if nbytes == 0:
+        raise WsdlError(f"group_norm: bad geometry B={B} C={Cc} HW={HW} num_groups={G} (at most 2^31 - 1 elements)")
+    return workspace(nbytes, device)
+
+
+def group_norm_bwd(x, dy, y, gamma, stats, num_groups, relu, dx=None, dgamma=None, dbeta=None, accumulate=False):
+    """wsdl_group_norm_bwd on dense tensors: writes the gradients whose buffers are given (``dx`` like x, ``dgamma`` / ``dbeta``
+    (C,) float32; with ``accumulate`` the two parameter gradients are added to) and launches nothing for the others.  ``stats``:
+    the (2, B G) float64 mean / rstd the forward saved; ``y``: the forward output, read only under ``relu``."""
+    B, Cc = x.shape[0], x.shape[1]
+    HW = x.numel() // (B * Cc)
+    ws = _group_norm_ws(B, Cc, HW, num_groups, x.device)
+    check(lib().wsdl_group_norm_bwd(_p(x), _p(dy), _p(y if relu else None), _p(gamma), _p(stats[0]), _p(stats[1]), _p(dx), _p(dgamma),
+                                    _p(dbeta), B, Cc, HW, num_groups, int(relu), int(accumulate), _p(ws), ws.numel(), _stream()))
+
+
+def _grad_slot(param, wanted, Cc):
+    """(buffer, accumulate, sink) for a (C,) parameter gradient: the parameter's slice of a flat optimiser's gradient buffer
+    (``_sink_of``; take_fresh -> accumulate, as the convolution's bias) or a new tensor to hand back to autograd."""
+    if not wanted:
+        return None, False, None
+    sink = _sink_of(param)
+    if sink is not None and tuple(param.grad.shape) == (Cc,) and param.grad.is_contiguous() and param.grad.dtype == torch.float32:
+        return param.grad, not sink.take_fresh(param), sink
+    return torch.empty(Cc, device=param.device, dtype=torch.float32), False, None
+
+
+class _GroupNorm(torch.autograd.Function):
+    """wsdl_group_norm_fwd / _bwd: three launches each way (two in the backward when x needs no gradient).  The statistics are
+    saved in double; the backward launches for the needed gradients only and writes those of parameters a flat optimiser owns
+    straight into ``p.grad``."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, num_groups, eps, relu):
+        x = _dense(x, "group_norm: x")
+        B, Cc = x.shape[0], x.shape[1]
+        HW = x.numel() // (B * Cc)
+        gamma = None if weight is None else _dense(weight.detach(), "group_norm: weight")
+        beta = None if bias is None else _dense(bias.detach(), "group_norm: bias")
+        y = torch.empty_like(x)
+        stats = torch.empty(2, B * num_groups, device=x.device, dtype=torch.float64)      # mean, rstd
+        ws = _group_norm_ws(B, Cc, HW, num_groups, x.device)
+        check(lib().wsdl_group_norm_fwd(_p(x), _p(gamma), _p(beta), _p(y), _p(stats[0]), _p(stats[1]), B, Cc, HW, num_groups, eps,
+                                        int(relu), _p(ws), ws.numel(), _stream()))
+        ctx.cfg = (num_groups, relu)
+        ctx.params = (weight, bias)
+        ctx.save_for_backward(x, gamma, stats, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, stats, y = ctx.saved_tensors
+        num_groups, relu = ctx.cfg
+        pw, pb = ctx.params
+        Cc = x.shape[1]
+        dy = _dense(dy, "group_norm: upstream gradient")
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dg, acc_g, sink_g = _grad_slot(pw, pw is not None and ctx.needs_input_grad[1], Cc)
+        db, acc_b, sink_b = _grad_slot(pb, pb is not None and ctx.needs_input_grad[2], Cc)
+        if dg is not None and db is not None and acc_g != acc_b:
+            # one of the two is added to and the other stored (a parameter shared with another layer): a call each
+            group_norm_bwd(x, dy, y, gamma, stats, num_groups, relu, dx=dx, dgamma=dg, accumulate=acc_g)
+            group_norm_bwd(x, dy, y, gamma, stats, num_groups, relu, dbeta=db, accumulate=acc_b)
+        elif dx is not None or dg is not None or db is not None:
+            group_norm_bwd(x, dy, y, gamma, stats, num_groups, relu, dx=dx, dgamma=dg, dbeta=db, accumulate=acc_g or acc_b)
+        if sink_g is not None:
+            sink_g.grad_ready(pw)
+            dg = None
+        if sink_b is not None:
+            sink_b.grad_ready(pb)
+            db = None
+        return dx, dg, db, None, None, None
+
+
+def group_norm(x, num_groups, weight=None, bias=None, eps=1e-5, relu=False):
+    """``torch.nn.functional.group_norm`` for a float32 device tensor (B, C, *) with at least two dimensions, optionally followed
+    by a fused ReLU: over each group of ``C / num_groups`` channels of an image, ``y = (x - mean) / sqrt(var + eps) * weight[c] +
+    bias[c]`` with the biased variance.  Train and eval are the same function.  A group of one element is accepted (``y = bias``,
+    zero gradient to x).  Statistics and every backward sum in double, the variance from a shifted second moment, partials
+    combined in a fixed order without atomics: bitwise reproducible, no host read - a launch plan can hold the call and its
+    backward.  Differentiable in ``x``, ``weight`` and ``bias``; the gradients of parameters owned by a flat optimiser go
+    straight into ``p.grad``.  Non-dense inputs are copied first."""
+    check_group_norm_options(num_groups, eps=eps)
+    if not torch.is_tensor(x) or x.dim() < 2:
+        raise WsdlError("group_norm: x must be a (B, C, *) tensor with at least two dimensions")
+    check_group_norm_options(num_groups, int(x.shape[1]), eps)
+    _req(x, "group_norm: x")
+    if x.numel() == 0:
+        raise WsdlError(f"group_norm: x {tuple(x.shape)} has an empty dimension")
+    for t, name in ((weight, "weight"), (bias, "bias")):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or tuple(t.shape) != (x.shape[1],):
+            raise WsdlError(f"group_norm: {name} must be a ({x.shape[1]},) tensor")
+        _req(t, f"group_norm: {name}")
+        if t.device != x.device:
+            raise WsdlError(f"group_norm: {name} is on {t.device}, x on {x.device}")
+    return _GroupNorm.apply(x, weight, bias, num_groups, float(eps), bool(relu))
+
+
 class _MaxPool3x3s2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

@@ -40,7 +40,7 @@ RANGE_SENTINEL = [_os.environ.get("WSDL_RANGE_SENTINEL", "1") != "0"]      # Fla
 def _is_norm_module(m):
     from . import nn as wnn
     import torch.nn as tnn
-    return isinstance(m, (wnn.BatchNorm2d, tnn.modules.batchnorm._BatchNorm, tnn.GroupNorm, tnn.LayerNorm))
+    return isinstance(m, (wnn.BatchNorm2d, wnn.GroupNorm, tnn.modules.batchnorm._BatchNorm, tnn.GroupNorm, tnn.LayerNorm))
 
 
 def no_decay_norm_and_bias(model):
