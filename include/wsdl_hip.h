@@ -613,7 +613,11 @@ int wsdl_scale_by_pixel(const float* dl, const float* g, float* out, int B, int 
  * an upstream gradient of 1 (per image for normalise=1).
  * cache (optional): the image's colour affinities from wsdl_pairwise_cache (same B, H, W, window, sigma_color); the
  * kernel then reads them instead of evaluating 24 exponentials per pixel - refine_pseudo_mask evaluates the loss 10 x 5
- * times on one image (AlternatingDirectionCutLoss.py:736-757, :803-810).  Bit-identical results either way. */
+ * times on one image (AlternatingDirectionCutLoss.py:736-757, :803-810).  Bit-identical results either way.
+ * Accepted: window in {3, 5, 7}; H and W > window / 2 (one reflection, as F.pad); 1 <= C <= 32 and, at window 7,
+ * C <= 27: the (3 + C) x (32 + 2R) x (8 + 2R) float tile of a workgroup must fit 64 KiB of LDS (R = window / 2; 60480
+ * bytes at window 5 and C = 32, 63840 at window 7 and C = 27); 1 <= B <= 65535; sigma_color > 0; sigma_space <= 0 is "no
+ * spatial term".  Anything else: WSDL_EINVAL with the cause in wsdl_last_error, nothing launched. */
 int wsdl_pairwise_affinity_loss_fwd_bwd(const float* preds, const float* image, float* loss,
                                         float* dpreds, int B, int C, int H, int W, int window,
                                         float sigma_color, float sigma_space, int apply_softmax,

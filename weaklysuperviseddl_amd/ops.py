@@ -1855,12 +1855,12 @@ def _scaled_grad(dl, g, inv=None):
 class _PairwiseAffinityLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, preds, image, window, sigma_color, sigma_space, apply_softmax, normalise, cache=None):
+        need = preds.requires_grad           # asked of the argument: the dense copy of a strided view, made here, never needs one
         preds, image = _dense(preds, "preds"), _dense(image, "image")
         B, Cc, H, W = preds.shape
         if tuple(image.shape) != (B, 3, H, W):
             raise WsdlError(f"pairwise loss: image {tuple(image.shape)} does not match preds {tuple(preds.shape)}")
         loss = torch.empty(B if normalise else 1, device=preds.device, dtype=torch.float32)
-        need = preds.requires_grad
         dp = torch.empty_like(preds) if need else None
         ws = workspace(lib().wsdl_pairwise_workspace(B, H, W), preds.device)
         check(lib().wsdl_pairwise_affinity_loss_fwd_bwd(_p(preds), _p(image), _p(loss), _p(dp), B, Cc, H, W,
