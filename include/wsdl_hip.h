@@ -1138,6 +1138,47 @@ int wsdl_group_norm_bwd(const float* x, const float* dy, const float* y, const f
                         const double* save_rstd, float* dx, float* dgamma, float* dbeta, int B, int C, int HW, int G, int relu,
                         int accumulate_param_grads, void* ws, size_t ws_bytes, wsdl_stream_t stream);
 
+/* ---- multi-scale fusion: scaled + mirrored batches and the fusion of their maps (csrc/multiscale.hip) - the reference has no
+ * such step.  PSA / IRN build a CAM as the sum over scales and a horizontal flip, DeepLab-family results are reported with
+ * multi-scale + flip inference; these are the launches AROUND the network.  fp32 planes, dense NCHW, all bilinear arithmetic
+ * is wsdl_bilinear_fwd's (align_corners = false), bit for bit.
+ * wsdl_scale_flip: x (B,C,H,W) -> y ((1 + flip) B, C, h, w), one launch.  Images [0, B) are wsdl_bilinear_fwd's result
+ *   (h == H and w == W: a copy), images [B, 2B) the same planes mirrored left-right - resize THEN mirror.
+ * wsdl_multiscale_fuse: up to WSDL_MS_MAX_SOURCES sources -> one (B,C,H,W) map, one launch.  Source s is (B,C,h_s,w_s), or
+ *   (2B,C,h_s,w_s) with `mirrored`: images [B, 2B) then belong to mirrored inputs.  A MEMBER is a source's plain half or its
+ *   mirrored half, in source order, plain before mirrored.  Member value at output pixel (b,c,oh,ow):
+ *   act(bilinear_{(h_s,w_s)->(H,W)}(plane)[oh, x]) with x = ow for a plain half and W - 1 - ow for a mirrored one (it is
+ *   un-mirrored AFTER the resize); h_s == H and w_s == W reads plane[oh, x] itself.  act: 0 none; 1 softmax over the C values
+ *   of the member AT that output pixel (float maximum m, e_c = expf(v_c - m), double sum over c in order, e_c * (1 / sum));
+ *   2 sigmoid (e = expf(-|v|), 1 / (1 + e) or e / (1 + e), in double).  reduce: 0 weighted mean - sum over the members of
+ *   (weight_s / sum of all members' weights) * value, in double, a source of weight 0 takes no part; 1 maximum (weights are
+ *   not read; a NaN member makes the result NaN).  The double is rounded once.  Outputs, each may be null but not all:
+ *   scores (B,C,H,W); labels (B,H,W) int64 and conf (B,H,W) - wsdl_pamr_labels' rule on the ROUNDED scores: C >= 2 the index
+ *   of the first maximum, ignore_index where it is < min_conf, conf = that maximum; C == 1: score >= thresh, conf = the score.
+ *   Labels need no score planes.  1 <= C <= WSDL_MS_MAX_CHANNELS (C <= 24: a pixel's channels stay in registers; beyond, the
+ *   softmax statistics take a first pass over the taps).  No atomics: bitwise reproducible.  The sources are copied into the
+ *   launch BY VALUE: a launch plan may hold the call.  No output may overlap a source.
+ * wsdl_plane_max_normalize: out[b] = x[b] / max(x[b]) over the per_image values of image b, v / max in double rounded once;
+ *   an image whose maximum is <= 0, infinite or NaN (any NaN in it) is copied unchanged.  mask (optional, uint8, the shape of
+ *   x): out >= thresh && out > 0 (the rule of wsdl_layercam_epilogue's mask).  out may be x.  A memset and two launches; the
+ *   maximum goes through an integer atomic max on float bits: bitwise reproducible.  ws: wsdl_plane_max_workspace(B) bytes
+ *   (0 for B outside [1, 65535]). */
+#define WSDL_MS_MAX_SOURCES 8
+#define WSDL_MS_MAX_CHANNELS 64
+typedef struct wsdl_ms_source {
+    const float* data;
+    int h, w;
+    float weight;   /* >= 0, finite */
+    int mirrored;   /* != 0: the leading dimension is 2B */
+} wsdl_ms_source;
+int wsdl_scale_flip(const float* x, float* y, int B, int C, int H, int W, int h, int w, int flip, wsdl_stream_t stream);
+int wsdl_multiscale_fuse(const wsdl_ms_source* sources, int n_sources, int B, int C, int H, int W, int activation, int reduce,
+                         float* scores, long long* labels, float* conf, float thresh, float min_conf, long long ignore_index,
+                         wsdl_stream_t stream);
+size_t wsdl_plane_max_workspace(int B);
+int wsdl_plane_max_normalize(const float* x, float* out, unsigned char* mask, int B, long long per_image, float thresh, void* ws,
+                             size_t ws_bytes, wsdl_stream_t stream);
+
 /* ---- refine_pseudo_mask inner step (TraditionalModel/AlternatingDirectionCutLoss.py:736-757) -
  * KL(softmax(X) || S) with log(X+1e-8), reduction 'batchmean', and its gradient wrt softmax(X). */
 int wsdl_kl_div_fwd_bwd(const float* xn, const float* s, float* loss, float* dxn, size_t n, int batch,

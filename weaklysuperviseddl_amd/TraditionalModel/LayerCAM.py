@@ -160,6 +160,39 @@ class LayerCAMGenerator:
         with ops.prof_range("layercam/epilogue"):
             return ops.layercam_epilogue(acts, grads, self.out_hw, alpha, self.variant, thresh)
 
+    def generate_multiscale(self, images, scales=(0.5, 1.0, 1.5, 2.0), flip=True, alpha=1.0, class_idx=None, thresh=None,
+                            reduce="mean", multiple=32):
+        """The CAM as PSA and IRN build it: over ``scales`` and, with ``flip``, the mirror image.  images (B,3,H,W) on the device,
+        class_idx LongTensor (B,) or None -> cam (B,outH,outW) [, uint8 mask with ``thresh``].
+
+        Per scale ONE ``ops.scale_flip`` to ``ops.multiscale_sizes(H, W, scales, multiple)`` and one eager batch over
+        ``[plain; mirrored]`` (the class indices repeated for the mirrored half; with ``class_idx=None`` every image of the batch,
+        mirrored ones included, takes its own arg-max class).  Every scale's epilogue already lands on ``out_hw``, so the maps
+        have the target's size and ONE ``ops.multiscale_fuse`` launch un-mirrors and combines them (``reduce``: 'mean' or 'max');
+        ``ops.max_normalize`` then divides every image by its maximum and thresholds it (``v >= thresh and v > 0``, the
+        epilogue's own rule).  No hipGraph capture: the lanes' graphs are keyed to one shape and stay that way.
+
+        With the default split arithmetic an image's CAM depends on which images share its device batch (one scale per tensor:
+        the effect the README notes for coalesced CAMs); the mirrored half therefore shares a batch with the plain half."""
+        if not torch.is_tensor(images) or images.dim() != 4:
+            raise ValueError("generate_multiscale: images must be (B,3,H,W)")
+        if reduce not in ("mean", "max"):
+            raise ValueError(f"generate_multiscale: reduce {reduce!r}: 'mean' or 'max'")
+        sizes = ops.multiscale_sizes(int(images.shape[-2]), int(images.shape[-1]), scales, multiple)
+        if class_idx is not None:
+            class_idx = class_idx.to(images.device).view(-1)
+            if flip:
+                class_idx = torch.cat([class_idx, class_idx])
+        cams = []
+        for size in sizes:
+            x = ops.scale_flip(images, size, flip)
+            cams.append(self._generate_batch_eager(x, alpha, class_idx, None)[:, None])
+        fused = ops.multiscale_fuse(cams, self.out_hw, mirrored=bool(flip), reduce=reduce)
+        if thresh is None:
+            return ops.max_normalize(fused, out=fused)[:, 0]
+        cam, mask = ops.max_normalize(fused, thresh, out=fused)
+        return cam[:, 0], mask[:, 0]
+
     def generate_coalesced(self, batches, alpha=1.0, class_idxs=None, thresh=None, streams=3, device_batch=32):
         """The batches of a loader merged into device batches of up to ``device_batch`` images (eval-mode BatchNorm makes images
         independent of their batch), ``streams`` of those in flight, the results handed back per loader batch.  At B=8 a batch

@@ -133,8 +133,16 @@ def _to_png_u8(t):
 def generate_pseudo_masks(loader, layercam_gen, cam_thresh=0.3, alpha=1.0, keep_largest_masks=True,
                           run_id="default", out_root="/content", max_images=500, write_png=True,
                           device="cuda", rank=0, world=1, keep_images=False, streams=3, keep_on_device=False,
-                          device_batch=0, pamr=None, superpixels=None, affinity=None, boundary=None):
-    """``pamr``: None (the default: the masks are the thresholded CAMs, bit for bit as without the argument) or a dict of
+                          device_batch=0, pamr=None, superpixels=None, affinity=None, boundary=None, multiscale=None):
+    """``multiscale``: None (the default: bit for bit the path without the argument) or a dict of keyword arguments of
+    ``LayerCAMGenerator.generate_multiscale`` (``scales``, ``flip``, ``reduce``, ``multiple``; ``{}``: its defaults) - the CAM of every
+    loader batch is the fusion over scales and the mirror image, divided by its per-image maximum; it takes the place of the CAM
+    before ``pamr`` / ``superpixels`` / ``affinity`` / ``boundary`` and the threshold (``v >= cam_thresh and v > 0``).  One eager pass
+    per loader batch and scale (``streams`` is not used, no hipGraph); ``device_batch > 0`` together with it is refused.  With the
+    default split arithmetic an image's CAM depends on which images share its device batch (the per-tensor scale effect the README
+    notes for coalesced CAMs): the masks depend on the loader's batches, and the mirrored half shares a batch with the plain half.
+
+    ``pamr``: None (the default: the masks are the thresholded CAMs, bit for bit as without the argument) or a dict of
     keyword arguments of ``ops.pamr`` (``{}``: its defaults) - the CAM WITHOUT its threshold is refined against the batch's
     images as a one-channel score map (pixel-adaptive mask refinement; the reference has no such step), the refined map is
     thresholded (``>= cam_thresh``) and ``keep_largest`` applies as before.  The images must have the CAM's size.
@@ -155,6 +163,13 @@ def generate_pseudo_masks(loader, layercam_gen, cam_thresh=0.3, alpha=1.0, keep_
     resized to the size of the net's boundary map, damped by ``1 - edge`` and walked as a one-channel map under the boundary-path
     affinities (``boundary_cam``; the reference has no such step), resized back and divided by its per-image maximum, then
     ``>= cam_thresh``, then ``keep_largest`` as before.  Combining it with ``pamr``, ``superpixels`` or ``affinity`` is refused."""
+    if multiscale is not None:
+        if not isinstance(multiscale, dict) or set(multiscale) - {"scales", "flip", "reduce", "multiple"}:
+            raise ValueError("generate_pseudo_masks: multiscale= is a dict of scales, flip, reduce, multiple")
+        if device_batch > 0:
+            raise ValueError("generate_pseudo_masks: multiscale= cannot be combined with device_batch > 0")
+        if not hasattr(layercam_gen, "generate_multiscale"):
+            raise ValueError("generate_pseudo_masks: multiscale= needs a generator with generate_multiscale")
     if boundary is not None:
         if pamr is not None or superpixels is not None or affinity is not None:
             raise ValueError("generate_pseudo_masks: boundary= cannot be combined with pamr=, superpixels= or affinity=")
@@ -192,7 +207,9 @@ def generate_pseudo_masks(loader, layercam_gen, cam_thresh=0.3, alpha=1.0, keep_
         # into device batches of n images.  A merged batch has its own per-tensor amax scales, tile and K-split choices, so
         # its masks equal the per-batch ones only outside the fp32 band of the network (~4e-3 of the CAM's range) and DO
         # depend on the flush threshold and the sharding - not for runs that must be reproducible
-        if hasattr(layercam_gen, "generate_coalesced"):
+        if multiscale is not None:
+            outs = [layercam_gen.generate_multiscale(g[1], alpha=alpha, class_idx=g[2], thresh=cam_thresh, **multiscale) for g in group]
+        elif hasattr(layercam_gen, "generate_coalesced"):
             outs = layercam_gen.generate_coalesced([g[1] for g in group], alpha, [g[2] for g in group], cam_thresh, streams, device_batch)
         elif hasattr(layercam_gen, "generate_batches"):
             outs = layercam_gen.generate_batches([g[1] for g in group], alpha, [g[2] for g in group], cam_thresh, streams)

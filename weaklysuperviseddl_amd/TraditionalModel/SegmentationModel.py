@@ -241,6 +241,13 @@ class SegmentationModel(nn.Module):
         self._join_aux()
         return super().load_state_dict(*args, **kwargs)
 
+    def head_logits(self, x):
+        """The classifier's output BEFORE the final ``bilinear_resize`` of ``forward``: (B, C, h/8, w/8), the stride-8 logits
+        ``ops.multiscale_fuse`` resamples itself (``bilinear_resize(head_logits(x), x.shape[-2:])`` is ``forward(x)['out']``).  The
+        aux head is not computed."""
+        self._join_aux()
+        return self.classifier(self.backbone(x)["out"])
+
     def forward(self, x):
         size = x.shape[-2:]
         self._join_aux()              # a previous forward's aux head may still be writing the statistics read / written now
@@ -440,14 +447,57 @@ def make_optimizer(model, lr=1e-4, early_step=None, *, kind="adam", **optimizer_
     return opt
 
 
+MULTISCALE_SCALES = (0.5, 0.75, 1.0, 1.25, 1.5, 1.75)
+
+
 @torch.no_grad()
-def evaluate_model(model, loader, device="cuda", binarize="notebook"):
+def predict_multiscale(model, images, scales=MULTISCALE_SCALES, flip=True, *, multiple=32, activation="softmax", scores=False,
+                       min_conf=0.0, ignore_index=255):
+    """Multi-scale + flip inference, the protocol DeepLab-family results are reported with: images (B,3,H,W) on the device ->
+    int64 labels (B,H,W), or ``(labels, scores)`` with ``scores=True`` (float32 (B,C,H,W), the fused map).
+
+    In eval mode (the model's mode is restored afterwards) and without gradients: per scale ONE ``ops.scale_flip`` to
+    ``ops.multiscale_sizes(H, W, scales, multiple)`` and ONE network pass over ``[plain; mirrored]`` that stops at the stride-8
+    logits (``model.head_logits``; a model without it gives ``model(x)["out"]``), then ONE ``ops.multiscale_fuse`` launch to
+    H x W: ``activation`` per member ('softmax': probabilities are averaged, 'none': logits), the mean over scales and mirror
+    images, the arg-max (``ignore_index`` where the fused maximum is below ``min_conf``).  No full-size map per scale exists.
+
+    With the default split arithmetic of the convolutions an image's logits depend on which images share its device batch (one
+    scale per tensor - the effect the README notes for coalesced CAMs); the mirrored half therefore shares a batch with the plain
+    half, and a prediction is reproducible for the same batch, not across batch compositions."""
+    if not torch.is_tensor(images) or images.dim() != 4:
+        raise ValueError("predict_multiscale: images must be (B,3,H,W)")
+    H, W = int(images.shape[-2]), int(images.shape[-1])
+    sizes = ops.multiscale_sizes(H, W, scales, multiple)
+    was_training = model.training
+    model.eval()
+    try:
+        head = getattr(model, "head_logits", None)
+        sources = []
+        for size in sizes:
+            x = ops.scale_flip(images, size, flip)
+            sources.append(head(x) if head is not None else model(x)["out"])
+        res = ops.multiscale_fuse(sources, (H, W), mirrored=bool(flip), activation=activation, scores=bool(scores), labels=True,
+                                  min_conf=min_conf, ignore_index=ignore_index)
+    finally:
+        if was_training:
+            model.train()
+    return (res[1], res[0]) if scores else res
+
+
+@torch.no_grad()
+def evaluate_model(model, loader, device="cuda", binarize="notebook", *, scales=None, flip=False):
     """argmax -> nearest resize to the ground truth's size -> IoU / pixel accuracy, averaged over the loader's images
     (one image - the first of each batch - per batch, as the reference).  Ground truth from the Oxford-IIIT Pet trimap:
       binarize="notebook": ``tm[tm == 2] = 1; tm = 1 - tm``      (AlternatingDirectionCutLoss.py:639-682, the script
                            that actually runs - SURVEY.md section 0);
-      binarize="modular" : ``tm = (tm == 1)``                    (SegmentationModel.py:126-159)."""
+      binarize="modular" : ``tm = (tm == 1)``                    (SegmentationModel.py:126-159).
+    ``scales`` / ``flip`` (keyword-only; the default ``None`` / ``False`` is the single-scale body above, launch for launch):
+    the prediction is ``predict_multiscale(model, x, scales or (1.0,), flip)`` - softmax probabilities averaged over the scales
+    and the mirror image - with the same image selection, ground-truth rule and nearest resize.  (Its note on device batches
+    applies: here every batch is one image and its mirror image.)"""
     model.eval()
+    multi = scales is not None or bool(flip)
     ious, accs = [], []
     for img, (_label, true_mask) in loader:
         x = img[0].to(device).unsqueeze(0)
@@ -459,8 +509,11 @@ def evaluate_model(model, loader, device="cuda", binarize="notebook"):
             tm = (tm == 1).long()
         else:
             raise ValueError(binarize)
-        out = model(x)["out"]
-        pred = out.squeeze(0).argmax(dim=0)
+        if multi:
+            pred = predict_multiscale(model, x, (1.0,) if scales is None else scales, flip)[0]
+        else:
+            out = model(x)["out"]
+            pred = out.squeeze(0).argmax(dim=0)
         if pred.shape != tm.shape:
             # F.interpolate(mode='nearest'): source index = floor(dst * in / out)
             idx_h = (torch.arange(tm.shape[-2], device=device) * pred.shape[0] // tm.shape[-2])

@@ -3,7 +3,8 @@ from .ClassificationModel import FrozenResNetCAM, train_fc_only, evaluate_classi
 from .LayerCAM import LayerCAMGenerator, CAMGenerator, evaluate_layercam_on_test_set  # noqa: F401
 from .PsuedoMasks import generate_pseudo_masks, keep_largest, generate, stage_handoff  # noqa: F401
 from .SegmentationModel import (SegmentationModel, build_segmentation_model, train_step, evaluate_model,  # noqa: F401
-                                train_segmentation_model, evaluate_boundary_iou, evaluate_surface_distances)
+                                train_segmentation_model, evaluate_boundary_iou, evaluate_surface_distances,
+                                predict_multiscale)
 from .AlternatingDirectionCutLoss import (  # noqa: F401
     LocalNormalizedCutLoss, compute_affinities, refine_pseudo_mask, refine_pseudo_masks_batched, train_model,
     refine_dataset, run_alternating_training, network_soft_prediction, apply_dense_crf,

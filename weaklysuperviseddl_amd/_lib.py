@@ -161,6 +161,10 @@ SIGNATURES = {
     "wsdl_group_norm_workspace": (_sz, [_i] * 4),
     "wsdl_group_norm_fwd": (_i, [_vp] * 6 + [_i] * 4 + [C.c_double, _i, _vp, _sz, _vp]),
     "wsdl_group_norm_bwd": (_i, [_vp] * 9 + [_i] * 6 + [_vp, _sz, _vp]),
+    "wsdl_scale_flip": (_i, [_vp, _vp] + [_i] * 7 + [_vp]),
+    "wsdl_multiscale_fuse": (_i, [_vp] + [_i] * 7 + [_vp, _vp, _vp, _f, _f, _ll, _vp]),
+    "wsdl_plane_max_workspace": (_sz, [_i]),
+    "wsdl_plane_max_normalize": (_i, [_vp, _vp, _vp, _i, _ll, _f, _vp, _sz, _vp]),
     "wsdl_kl_div_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, _sz, _vp]),
     "wsdl_kl_div_per_image_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _sz, _vp, _sz, _vp]),
     "wsdl_refine_combine": (_i, [_vp, _vp, _vp, _vp, _f, _f, _vp, _i, _sz, _vp]),

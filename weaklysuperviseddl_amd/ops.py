@@ -2879,6 +2879,203 @@ def pamr_labels(scores, thresh=0.5, min_conf=0.0, ignore_index=255):
     return labels
 
 
+# ---- multi-scale + flip test-time fusion (csrc/multiscale.hip; include/wsdl_hip.h "multi-scale fusion")
+MS_MAX_SOURCES = 8
+MS_MAX_CHANNELS = 64
+_MS_ACTIVATIONS = {"none": 0, "softmax": 1, "sigmoid": 2}
+_MS_REDUCTIONS = {"mean": 0, "max": 1}
+
+
+class _MsSource(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("h", C.c_int), ("w", C.c_int), ("weight", C.c_float), ("mirrored", C.c_int)]
+
+
+def _hw(size, name):
+    try:
+        H, W = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: size {size!r} must be (H, W)") from None
+    if H < 1 or W < 1:
+        raise ValueError(f"{name}: size {size!r} must be positive")
+    return H, W
+
+
+def multiscale_sizes(H, W, scales, multiple=32):
+    """The input sizes of a multi-scale pass over H x W images: per scale ``s`` the pair
+    ``(max(multiple, floor(s H / multiple + 0.5) multiple), likewise for W)`` - the nearest multiple, halves up, never below one
+    ``multiple`` (the networks' output stride is 8 and the classifier's 32).  Host only.  ValueError for a scale that is not a
+    positive finite number, for more than 8 scales, for none, and for two scales that land on the same size."""
+    if isinstance(multiple, bool) or not isinstance(multiple, int) or multiple < 1:
+        raise ValueError(f"multiscale_sizes: multiple {multiple!r} must be an int >= 1")
+    H, W = _hw((H, W), "multiscale_sizes")
+    try:
+        scales = tuple(float(s) for s in scales)
+    except (TypeError, ValueError):
+        raise ValueError(f"multiscale_sizes: scales {scales!r} must be a sequence of numbers") from None
+    if not 1 <= len(scales) <= MS_MAX_SOURCES:
+        raise ValueError(f"multiscale_sizes: 1 to {MS_MAX_SOURCES} scales, got {len(scales)}")
+    if any(not (s > 0 and s < float("inf")) for s in scales):
+        raise ValueError(f"multiscale_sizes: scales {scales!r} must be positive and finite")
+    sizes = [(max(multiple, int(np.floor(s * H / multiple + 0.5)) * multiple), max(multiple, int(np.floor(s * W / multiple + 0.5)) * multiple))
+             for s in scales]
+    if len(set(sizes)) != len(sizes):
+        raise ValueError(f"multiscale_sizes: scales {scales!r} give the sizes {sizes!r}: two scales land on the same size")
+    return sizes
+
+
+def scale_flip(images, size, flip=False, out=None):
+    """images (B,C,H,W) float32 on the device -> ((1 + flip) B, C, h, w): images ``[0, B)`` are ``bilinear_resize(images, size)``
+    bit for bit (a copy when ``size`` is the input's), images ``[B, 2B)`` the same planes mirrored left-right - resize, THEN
+    mirror (mirror-then-resize differs in the last bit).  One launch, no host read, not differentiable (the input is detached);
+    a launch plan can hold the call.  A strided input is copied first.  ``out``: a dense float32 tensor of the result's shape on
+    the same device that receives it (it must not overlap ``images``)."""
+    h, w = _hw(size, "scale_flip")
+    if not torch.is_tensor(images) or images.dim() != 4 or images.numel() == 0:
+        raise WsdlError("scale_flip: images must be a non-empty (B,C,H,W) tensor")
+    images = _dense(images.detach(), "scale_flip: images")
+    B, Cc, H, W = images.shape
+    shape = (B * (2 if flip else 1), Cc, h, w)
+    if out is None:
+        out = torch.empty(shape, device=images.device, dtype=torch.float32)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape
+              and out.device == images.device and out.is_contiguous() and not out.requires_grad):
+        raise WsdlError(f"scale_flip: out must be a dense float32 {shape} tensor on {images.device} that needs no gradient")
+    check(lib().wsdl_scale_flip(_p(images), _p(out), B, Cc, H, W, h, w, int(bool(flip)), _stream()))
+    return out
+
+
+def check_multiscale_fuse(sources, size, mirrored=False, weights=None, activation="none", reduce="mean"):
+    """The host-side refusals of ``multiscale_fuse`` - before any device work, each stating its cause.  Returns
+    ``(B, C, H, W, mirrored flags, weights)``."""
+    H, W = _hw(size, "multiscale_fuse")
+    if activation not in _MS_ACTIVATIONS:
+        raise ValueError(f"multiscale_fuse: activation {activation!r}: 'none', 'softmax' or 'sigmoid'")
+    if reduce not in _MS_REDUCTIONS:
+        raise ValueError(f"multiscale_fuse: reduce {reduce!r}: 'mean' or 'max'")
+    if torch.is_tensor(sources):
+        sources = [sources]
+    sources = list(sources)
+    n = len(sources)
+    if not 1 <= n <= MS_MAX_SOURCES:
+        raise ValueError(f"multiscale_fuse: 1 to {MS_MAX_SOURCES} sources, got {n}")
+    if isinstance(mirrored, (bool, int)):
+        mirrored = [bool(mirrored)] * n
+    else:
+        mirrored = [bool(m) for m in mirrored]
+        if len(mirrored) != n:
+            raise ValueError(f"multiscale_fuse: {len(mirrored)} mirrored flags for {n} sources")
+    if weights is not None:
+        if reduce == "max":
+            raise ValueError("multiscale_fuse: reduce='max' takes no weights")
+        try:
+            weights = [float(v) for v in weights]
+        except (TypeError, ValueError):
+            raise ValueError(f"multiscale_fuse: weights {weights!r} must be a sequence of numbers") from None
+        if len(weights) != n:
+            raise ValueError(f"multiscale_fuse: {len(weights)} weights for {n} sources")
+        if any(not (0.0 <= v < float("inf")) for v in weights) or not sum(weights) > 0:
+            raise ValueError(f"multiscale_fuse: weights {weights!r} must be finite, >= 0 and not all zero")
+    else:
+        weights = [1.0] * n
+    B = Cc = None
+    for k, (t, m) in enumerate(zip(sources, mirrored)):
+        if not torch.is_tensor(t) or t.dim() != 4 or t.numel() == 0:
+            raise WsdlError(f"multiscale_fuse: source {k} must be a non-empty (B,C,h,w) tensor")
+        if t.dtype != torch.float32:
+            raise WsdlError(f"multiscale_fuse: source {k}: expected torch.float32, got {t.dtype}")
+        lead = t.shape[0]
+        if m:
+            if lead % 2:
+                raise WsdlError(f"multiscale_fuse: source {k} is mirrored but its leading dimension {lead} is odd "
+                                "(plain images first, then their mirror images)")
+            lead //= 2
+        if B is None:
+            B, Cc = lead, t.shape[1]
+        if lead != B:
+            raise WsdlError(f"multiscale_fuse: source {k} holds {lead} images, source 0 holds {B}")
+        if t.shape[1] != Cc:
+            raise WsdlError(f"multiscale_fuse: source {k} has {t.shape[1]} channels, source 0 has {Cc}")
+    if Cc > MS_MAX_CHANNELS:
+        raise WsdlError(f"multiscale_fuse: {Cc} channels, at most {MS_MAX_CHANNELS}")
+    if activation == "softmax" and Cc == 1:
+        raise ValueError("multiscale_fuse: activation='softmax' needs more than one channel (use 'sigmoid')")
+    for k, t in enumerate(sources):
+        if not t.is_cuda:
+            raise WsdlError(f"multiscale_fuse: source {k}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
+        if t.device != sources[0].device:
+            raise WsdlError(f"multiscale_fuse: source {k} is on {t.device}, source 0 on {sources[0].device}")
+    return B, Cc, H, W, mirrored, weights
+
+
+def multiscale_fuse(sources, size, *, mirrored=False, weights=None, activation="none", reduce="mean", scores=True, labels=False,
+                    conf=False, thresh=0.5, min_conf=0.0, ignore_index=255, out=None):
+    """Fuse up to 8 float32 device maps of different sizes into one map of ``size`` = (H, W) in ONE launch, without a full-size
+    intermediate per source.  ``sources[k]`` is (B,C,h_k,w_k), or (2B,C,h_k,w_k) when ``mirrored`` (a bool for all, or one per
+    source): images ``[B, 2B)`` are then the network's outputs for the mirrored inputs, as ``scale_flip(flip=True)`` orders them.
+    Every member - a source's plain half, then its mirrored half, in source order - contributes
+    ``act(bilinear_resize(member, size))`` at the output pixel, the mirrored half un-mirrored after its resize; a source that
+    already has the target's size is read directly.  ``activation``: 'none', 'softmax' (over C, taken AFTER the resize, at the
+    output pixel) or 'sigmoid'; ``reduce``: 'mean' (weighted by ``weights``, one per source, default all 1; both halves of a
+    source carry its weight) or 'max'.  The members of a pixel are combined in double and rounded once; no atomics: two calls
+    give the same bits.
+
+    Returns what was asked for, in this order, as one tensor or a tuple: ``scores`` (B,C,H,W) float32; ``labels`` (B,H,W) int64,
+    exactly ``pamr_labels(scores, thresh, min_conf, ignore_index)``; ``conf`` (B,H,W) float32, the score behind the label (C = 1:
+    the score).  Labels and ``conf`` need no score planes.  ``out``: a dict whose 'scores' / 'labels' / 'conf' entries, where they
+    are dense tensors of the right shape, type and device, receive the results (others are put there).
+
+    Not differentiable (inputs detached), no host read: a launch plan can hold the call.  Strided sources are copied first.
+    Refused before any device work, with the cause: a wrong dtype or device, batch / channel / count mismatches, a mirrored source
+    with an odd leading dimension, C > 64, more than 8 sources, ``reduce='max'`` with weights, ``activation='softmax'`` with C = 1."""
+    B, Cc, H, W, mirrored, weights = check_multiscale_fuse(sources, size, mirrored, weights, activation, reduce)
+    if not (scores or labels or conf):
+        raise ValueError("multiscale_fuse: nothing asked for (scores, labels, conf)")
+    if out is not None and not isinstance(out, dict):
+        raise ValueError("multiscale_fuse: out is a dict with 'scores', 'labels' and / or 'conf'")
+    if torch.is_tensor(sources):
+        sources = [sources]
+    srcs = [_dense(t.detach(), "multiscale_fuse: source") for t in sources]
+    dev = srcs[0].device
+    arr = (_MsSource * len(srcs))()
+    for k, (t, m, wt) in enumerate(zip(srcs, mirrored, weights)):
+        arr[k].data, arr[k].h, arr[k].w, arr[k].weight, arr[k].mirrored = _p(t), t.shape[2], t.shape[3], wt, int(m)
+    t_scores = _out_tensor(out, "scores", (B, Cc, H, W), torch.float32, dev) if scores else None
+    t_labels = _out_tensor(out, "labels", (B, H, W), torch.int64, dev) if labels else None
+    t_conf = _out_tensor(out, "conf", (B, H, W), torch.float32, dev) if conf else None
+    check(lib().wsdl_multiscale_fuse(arr, len(srcs), B, Cc, H, W, _MS_ACTIVATIONS[activation], _MS_REDUCTIONS[reduce], _p(t_scores),
+                                     _p(t_labels), _p(t_conf), float(thresh), float(min_conf), int(ignore_index), _stream()))
+    res = tuple(t for t in (t_scores, t_labels, t_conf) if t is not None)
+    return res[0] if len(res) == 1 else res
+
+
+def max_normalize(scores, thresh=None, out=None):
+    """Divide every image of float32 device ``scores`` (B, ...) by its own maximum - PSA's normalisation of a combined CAM -
+    ``v / max`` formed in double and rounded once.  An image whose maximum is <= 0 or not finite (any NaN in it) is left as it
+    is.  ``thresh``: also return a uint8 mask of the same shape, ``v >= thresh and v > 0`` on the normalised values (the rule of
+    the LayerCAM epilogue's mask).  ``out``: the tensor that receives the result (dense, same shape; may be ``scores`` itself).
+    A memset and two launches, the maximum through an integer atomic max: bitwise reproducible, no host read, not
+    differentiable; a launch plan can hold the call."""
+    if not torch.is_tensor(scores) or scores.dim() < 2 or scores.numel() == 0:
+        raise WsdlError("max_normalize: scores must be a non-empty (B, ...) tensor")
+    if thresh is not None and not float(thresh) == float(thresh):
+        raise ValueError("max_normalize: thresh is NaN")
+    x = _dense(scores.detach(), "max_normalize: scores")
+    B = x.shape[0]
+    if out is None:
+        out = torch.empty_like(x)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.shape == x.shape and out.device == x.device
+              and out.is_contiguous() and not out.requires_grad):
+        raise WsdlError(f"max_normalize: out must be a dense float32 {tuple(x.shape)} tensor on {x.device} that needs no gradient")
+    nbytes = lib().wsdl_plane_max_workspace(B)
+    if nbytes == 0:
+        raise WsdlError(f"max_normalize: {B} images, at most 65535")
+    mask = torch.empty(x.shape, device=x.device, dtype=torch.uint8) if thresh is not None else None
+    ws = workspace(nbytes, x.device)
+    check(lib().wsdl_plane_max_normalize(_p(x), _p(out), _p(mask), B, x.numel() // B, float(thresh if thresh is not None else 0.0),
+                                         _p(ws), ws.numel(), _stream()))
+    return out if mask is None else (out, mask)
+
+
 # ---- AffinityNet: learned pairwise affinities, their loss, the CAM random walk (csrc/affinity.hip; include/wsdl_hip.h "AffinityNet")
 AFFINITY_WEIGHTS = (0.25, 0.25, 0.5)
 
