@@ -1196,6 +1196,44 @@ int wsdl_refine_combine(const float* dkl, const float* dnc, const float* kl, con
 int wsdl_softmax_fwd(const float* x, float* y, int B, int C, int HW, wsdl_stream_t stream);
 int wsdl_softmax_bwd(const float* y, const float* dy, float* dx, int B, int C, int HW, wsdl_stream_t stream);
 
+/* ---- Class prototypes: masked feature pooling, prototype similarity maps and the pixel-to-prototype contrast loss
+ * (SIPE: Chen et al., CVPR 2022; Du et al., CVPR 2022; Wang et al., ICCV 2021; csrc/prototype.hip) - the reference has no such
+ * step; this is the project's definition.  feat is float (B,D,H,W), dense, D <= 2048, H W <= 2^20, K <= 32 classes.
+ * Norms: n(x) = max(sqrt(sum_d x_d^2), eps) and u_p = f_p / n(f_p) (F.normalize).  A segment s is one image (S = B) or the whole
+ * batch (S = 1).
+ *   Prototypes: mass[s,k] = sum of w_p (pixel_weight, or 1 when it is null) over the pixels of s with labels_p == k; labels equal to
+ *   ignore_index or outside [0,K) are not pooled; proto[s,k,:] = sum w_p x_p / mass[s,k] with x_p = u_p (normalize) or f_p, exactly 0
+ *   where the mass is not > 0.  Sums in double, every (s,k,d) sum owned by one wave per image, the images added in order: no
+ *   atomics, the same bits on every call.  mass is float: exact up to 2^24 for unit weights.
+ *   Similarity: sim[b,k,p] = <u_p, q_k>, q_k = proto[s(b),k,:] / n(proto[s(b),k,:]) (a zero prototype gives 0); activation 0: as it
+ *   is, 1: max(sim, 0), 2: the softmax over the classes marked in present (S,K) uint8 (null: all) of sim / temperature, exactly 0
+ *   for an absent class.
+ *   Contrast: z_{p,k} = sim[b,k,p] / temperature over the present classes, l_p = -log softmax(z_p)[y_p]; a pixel counts iff its
+ *   label is not ignore_index and its class is present; a label outside [0,K) other than ignore_index gives NaN.  reduction 0:
+ *   loss = sum w_p l_p / sum w_p over the counted pixels (0 without one), 1: the sum, 2: loss is (B,H,W), w_p l_p per pixel (0
+ *   where not counted).  dfeat (null: forward only, the same loss bits) receives, with g_k = w_p (softmax_k - [k == y_p]),
+ *   v = sum_k g_k q_k / temperature and c = sum_k g_k sim_k / temperature: (v - c u_p) / n(f_p), or v / eps where the norm is
+ *   below eps; exact zeros at a pixel that does not count.  The prototypes are constants.  inv (one float, may be null)
+ *   receives the factor the mean's gradient still needs, 1 / sum w_p (0 without a counted pixel; 1 for the sum).
+ *   Bank: bank[k,:] = m bank[k,:] + (1 - m) proto[k,:] and count[k] += 1 for the classes with mass[k] > 0; a class whose count was
+ *   0 takes proto[k,:] as it is; the others are untouched.
+ * wsdl_proto_workspace: bytes of ws that suffice for every entry point below at this geometry (16-byte aligned); 0 outside the
+ * limits.  wsdl_proto_pool: three launches; wsdl_proto_similarity: two; wsdl_proto_contrast: two and the one-workgroup finalize
+ * (none for reduction 2); wsdl_proto_ema: one.  No host read, every parameter by value: a launch plan can hold them. */
+size_t wsdl_proto_workspace(int B, int D, int K, int H, int W);
+int wsdl_proto_pool(const float* feat, const long long* labels, const float* pixel_weight, float* proto, float* mass, int B, int D,
+                    int H, int W, int K, int per_image, int normalize, long long ignore_index, double eps, void* ws, size_t ws_bytes,
+                    wsdl_stream_t stream);
+int wsdl_proto_similarity(const float* feat, const float* proto, const unsigned char* present, float* out, int B, int D, int H, int W,
+                          int K, int S, int activation, double temperature, double eps, void* ws, size_t ws_bytes,
+                          wsdl_stream_t stream);
+int wsdl_proto_contrast(const float* feat, const float* proto, const long long* labels, const unsigned char* present,
+                        const float* pixel_weight, float* loss, float* dfeat, float* inv, int B, int D, int H, int W, int K, int S,
+                        long long ignore_index, double temperature, double eps, int reduction, void* ws, size_t ws_bytes,
+                        wsdl_stream_t stream);
+int wsdl_proto_ema(float* bank, long long* count, const float* proto, const float* mass, int K, int D, double momentum,
+                   wsdl_stream_t stream);
+
 /* ---- launch plans: the reference's training / CAM loops as one host call per iteration ------------------------------
  * The reference runs its loops statement by statement from Python (one training iteration:
  * TraditionalModel/AlternatingDirectionCutLoss.py:693-703 = SegmentationModel.py:96-113; one CAM batch:

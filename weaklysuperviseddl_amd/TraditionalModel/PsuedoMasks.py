@@ -21,6 +21,8 @@ Mirrors reference TraditionalModel/PsuedoMasks.py: ``keep_largest`` (:15-21) and
     (``ops.affinity_random_walk``; off by default);
   * ``boundary``: optional random walk of the CAM, before its threshold, under the boundary-path affinities of a
     ``BoundaryNet`` (``ops.edge_random_walk``; off by default);
+  * ``generate_prototype_pseudo_masks``: optional prototype CAM - the softmax similarity of every pixel's features to the image's own foreground and
+    background prototypes, pooled over the CAM's sure regions (``prototype_cam``; off by default);
   * ``keep_largest(mask)`` is the reference's host function (skimage there; scipy.ndimage here - 8-connectivity, raster
     label order, first label wins area ties, empty mask returned unchanged).  ``generate_pseudo_masks`` itself labels
     the whole batch on the device (``keep_largest_batched`` -> ``ops.keep_largest_batched``, one workgroup per mask, the
@@ -125,6 +127,36 @@ def boundary_cam(images, cam, net, radius=5, beta=10.0, num_iter=256):
     return back / (back.amax(dim=(-2, -1), keepdim=True) + 1e-5)
 
 
+def _prototype_options(prototype):
+    """The ``prototype`` dict of ``generate_prototype_pseudo_masks`` with its defaults; ValueError / WsdlError for what it cannot be."""
+    if not isinstance(prototype, dict) or "net" not in prototype or set(prototype) - {"net", "lo", "hi", "temperature"}:
+        raise ValueError("generate_prototype_pseudo_masks: prototype is a dict of net, lo, hi, temperature (net is required)")
+    opts = dict(lo=0.05, hi=0.3, temperature=0.1)
+    opts.update(prototype)
+    if not opts["lo"] < opts["hi"]:
+        raise ValueError(f"generate_prototype_pseudo_masks: lo {opts['lo']!r} must be below hi {opts['hi']!r}")
+    ops.check_prototype_options(temperature=opts["temperature"], name="generate_prototype_pseudo_masks")
+    return opts
+
+
+def prototype_cam(images, cam, net, *, lo=0.05, hi=0.3, temperature=0.1):
+    """A CAM (B,H,W) in [0, 1] replaced by its image-specific prototype CAM (SIPE, Chen et al., CVPR 2022): the features are
+    ``net(images)`` (B,D,h,w), without a gradient; the seeds ``seeds_from_cam(cam, lo, hi)`` - 1 sure foreground, 0 sure background -
+    are down-sampled to h x w by nearest neighbour; ``ops.class_prototypes`` pools one background and one foreground prototype per
+    image; the result is the foreground channel of ``ops.prototype_similarity(..., activation='softmax', temperature=)``, resized
+    back to H x W (``ops.bilinear_resize``).  An image without a background seed or without a foreground seed keeps its input CAM
+    (a ``torch.where`` on the masses: no host read)."""
+    with torch.no_grad():
+        feat = net(images)
+    seeds = seeds_from_cam(cam, lo, hi)
+    iy = nearest_resize_index(feat.shape[-2], seeds.shape[1], seeds.device)
+    ix = nearest_resize_index(feat.shape[-1], seeds.shape[2], seeds.device)
+    proto, mass = ops.class_prototypes(feat, seeds[:, iy][:, :, ix].contiguous(), 2)
+    sim = ops.prototype_similarity(feat, proto, activation="softmax", temperature=temperature)
+    back = ops.bilinear_resize(sim[:, 1:2].contiguous(), tuple(cam.shape[-2:]))[:, 0]
+    return torch.where((mass > 0).all(dim=1)[:, None, None], back, cam.float())
+
+
 def _to_png_u8(t):
     """torchvision.utils.save_image's quantisation: mul(255).add_(0.5).clamp_(0, 255) -> uint8, HWC."""
     return t.mul(255).add(0.5).clamp(0, 255).permute(1, 2, 0).to(torch.uint8).cpu().numpy()
@@ -163,6 +195,32 @@ def generate_pseudo_masks(loader, layercam_gen, cam_thresh=0.3, alpha=1.0, keep_
     resized to the size of the net's boundary map, damped by ``1 - edge`` and walked as a one-channel map under the boundary-path
     affinities (``boundary_cam``; the reference has no such step), resized back and divided by its per-image maximum, then
     ``>= cam_thresh``, then ``keep_largest`` as before.  Combining it with ``pamr``, ``superpixels`` or ``affinity`` is refused."""
+    return _generate_pseudo_masks(loader, layercam_gen, cam_thresh, alpha, keep_largest_masks, run_id, out_root, max_images, write_png,
+                                  device, rank, world, keep_images, streams, keep_on_device, device_batch, pamr, superpixels, affinity,
+                                  boundary, multiscale, None)
+
+
+def generate_prototype_pseudo_masks(loader, layercam_gen, prototype, **kwargs):
+    """``generate_pseudo_masks(loader, layercam_gen, **kwargs)`` with the prototype CAM in front of the threshold.  (A function of
+    its own: the positional signature of ``generate_pseudo_masks`` is pinned.)  ``prototype``: None (bit for bit
+    ``generate_pseudo_masks``) or a dict with ``net`` (a ``TrunkFeatures`` or a ``ProjectionNet``, on the device, in eval mode) and
+    optionally ``lo`` (0.05), ``hi`` (0.3) and ``temperature`` (0.1) - the CAM WITHOUT its threshold is replaced by the prototype CAM
+    of the batch's features (``prototype_cam``; the reference has no such step), then ``>= cam_thresh``, then ``keep_largest`` as
+    before.  Combining it with ``pamr``, ``superpixels``, ``affinity`` or ``boundary`` is refused; ``multiscale`` may come first.  The
+    results are left where ``generate_pseudo_masks`` leaves them (``generate_pseudo_masks.last_masks`` / ``.last_ids`` /
+    ``.last_images``)."""
+    return _generate_pseudo_masks(loader, layercam_gen, prototype=prototype, **kwargs)
+
+
+def _generate_pseudo_masks(loader, layercam_gen, cam_thresh=0.3, alpha=1.0, keep_largest_masks=True, run_id="default",
+                           out_root="/content", max_images=500, write_png=True, device="cuda", rank=0, world=1, keep_images=False,
+                           streams=3, keep_on_device=False, device_batch=0, pamr=None, superpixels=None, affinity=None, boundary=None,
+                           multiscale=None, prototype=None):
+    """The body of ``generate_pseudo_masks`` / ``generate_prototype_pseudo_masks`` (their docstrings)."""
+    if prototype is not None:
+        if pamr is not None or superpixels is not None or affinity is not None or boundary is not None:
+            raise ValueError("generate_prototype_pseudo_masks: prototype cannot be combined with pamr=, superpixels=, affinity= or boundary=")
+        prototype = _prototype_options(prototype)
     if multiscale is not None:
         if not isinstance(multiscale, dict) or set(multiscale) - {"scales", "flip", "reduce", "multiple"}:
             raise ValueError("generate_pseudo_masks: multiscale= is a dict of scales, flip, reduce, multiple")
@@ -224,6 +282,8 @@ def generate_pseudo_masks(loader, layercam_gen, cam_thresh=0.3, alpha=1.0, keep_
                 m = (affinity_cam(imgs_d, cam, **affinity) >= cam_thresh).to(torch.uint8)
             if boundary is not None:
                 m = (boundary_cam(imgs_d, cam, **boundary) >= cam_thresh).to(torch.uint8)
+            if prototype is not None:
+                m = (prototype_cam(imgs_d, cam, **prototype) >= cam_thresh).to(torch.uint8)
             if keep_largest_masks:
                 m = keep_largest_batched(m)
             m_host = m if keep_on_device and not write_png else m.cpu().numpy()

@@ -170,6 +170,11 @@ SIGNATURES = {
     "wsdl_refine_combine": (_i, [_vp, _vp, _vp, _vp, _f, _f, _vp, _i, _sz, _vp]),
     "wsdl_softmax_fwd": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "wsdl_softmax_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "wsdl_proto_workspace": (_sz, [_i] * 5),
+    "wsdl_proto_pool": (_i, [_vp] * 5 + [_i] * 7 + [_ll, C.c_double, _vp, _sz, _vp]),
+    "wsdl_proto_similarity": (_i, [_vp] * 4 + [_i] * 7 + [C.c_double, C.c_double, _vp, _sz, _vp]),
+    "wsdl_proto_contrast": (_i, [_vp] * 8 + [_i] * 6 + [_ll, C.c_double, C.c_double, _i, _vp, _sz, _vp]),
+    "wsdl_proto_ema": (_i, [_vp] * 4 + [_i, _i, C.c_double, _vp]),
     # launch plans + the stream ordering / small helpers a plan needs to see (csrc/plan.hip)
     "wsdl_plan_begin": (_i, []),
     "wsdl_plan_recording": (_i, []),

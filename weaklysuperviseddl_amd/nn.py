@@ -877,6 +877,74 @@ class RandomWalk(nn.Module):
         return f"radius={self.radius}, beta={self.beta}, num_iter={self.num_iter}"
 
 
+class PrototypeContrastLoss(nn.Module):
+    """Pixel-to-prototype contrast (Du et al., CVPR 2022; Wang et al., ICCV 2021; ``ops.prototype_contrast_loss``) as a module
+    without parameters: ``forward(feat, labels)`` for float32 features (B,D,h,w) and int64 labels (B,h,w) in [0, num_classes) or
+    ``ignore_index``.  The prototypes are pooled from the DETACHED features (``ops.class_prototypes``, unit vectors) into the
+    module's own buffers - ``source='batch'``: one set over the batch, ``'image'``: one per image, ``'bank'``: the batch's set is
+    first folded into a moving average over the calls (``ops.prototype_ema_`` with ``momentum``; ``bank`` (K,D), ``count`` (K,)
+    int64, registered buffers: they are in the state dict and move with ``.to()``; ``reset()`` empties both) and the bank is what the
+    pixels are compared with.  The classes present are those with ``mass >
+    0`` (``count > 0`` for the bank); then the fused loss, mean over the counted pixels.  The gradient flows into ``feat`` only.
+    A plain module: not one of the segmentation criteria ``train_step`` takes."""
+
+    SOURCES = ("batch", "image", "bank")
+
+    def __init__(self, num_classes, temperature=0.1, source="batch", momentum=0.99, ignore_index=255):
+        super().__init__()
+        ops.check_prototype_options(num_classes=num_classes, temperature=temperature, momentum=momentum, name="PrototypeContrastLoss")
+        if source not in self.SOURCES:
+            raise ops.WsdlError(f"PrototypeContrastLoss: source {source!r}: 'batch', 'image' or 'bank'")
+        self.num_classes, self.temperature, self.source = num_classes, float(temperature), source
+        self.momentum, self.ignore_index = float(momentum), int(ignore_index)
+        # registered buffers, filled at the first call (the channel count is the features'): ``bank`` and ``count`` are part of the
+        # state dict and move with ``.to()``; ``proto`` and ``mass`` are the last call's scratch and are not saved
+        self.register_buffer("bank", None)
+        self.register_buffer("count", None)
+        self.register_buffer("proto", None, persistent=False)
+        self.register_buffer("mass", None, persistent=False)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        # a bank saved after its first call loads into a module that has not been called yet
+        for name in ("bank", "count"):
+            saved = state_dict.get(prefix + name)
+            if saved is not None and (getattr(self, name) is None or getattr(self, name).shape != saved.shape):
+                setattr(self, name, torch.empty_like(saved, device=saved.device if getattr(self, name) is None else getattr(self, name).device))
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def reset(self):
+        """Empty the bank: every class takes the next prototype it sees as it is."""
+        if self.bank is not None:
+            ops.memset_zero(self.bank)
+            ops.memset_zero(self.count)
+
+    def _make_buffers(self, S, D, device):
+        if self.proto is None or tuple(self.proto.shape) != (S, self.num_classes, D) or self.proto.device != device:
+            self.proto = torch.zeros(S, self.num_classes, D, device=device)
+            self.mass = torch.zeros(S, self.num_classes, device=device)
+        if self.source == "bank" and (self.bank is None or self.bank.shape[1] != D or self.bank.device != device):
+            self.bank = torch.zeros(self.num_classes, D, device=device)
+            self.count = torch.zeros(self.num_classes, dtype=torch.int64, device=device)
+
+    def forward(self, feat, labels):
+        per_image = self.source == "image"
+        ops.check_prototype_options(feat=feat, labels=labels, name="PrototypeContrastLoss")
+        self._make_buffers(feat.shape[0] if per_image else 1, feat.shape[1], feat.device)
+        ops.class_prototypes(feat.detach(), labels, self.num_classes, per_image=per_image, ignore_index=self.ignore_index,
+                             out=(self.proto, self.mass))
+        if self.source == "bank":
+            ops.prototype_ema_(self.bank, self.count, self.proto, self.mass, self.momentum)
+            proto, present = self.bank[None], self.count[None] > 0
+        else:
+            proto, present = self.proto, self.mass > 0
+        return ops.prototype_contrast_loss(feat, proto, labels, temperature=self.temperature, present=present,
+                                           ignore_index=self.ignore_index)
+
+    def extra_repr(self):
+        return (f"num_classes={self.num_classes}, temperature={self.temperature}, source={self.source!r}, momentum={self.momentum}, "
+                f"ignore_index={self.ignore_index}")
+
+
 class PathAffinityLoss(nn.Module):
     """IRN's boundary loss (Ahn, Cho & Kwak, CVPR 2019; ``ops.path_affinity_loss``) as a module without parameters:
     ``forward(edge_logits, labels)`` for the float32 logits (B,1,h,w) or (B,h,w) of a boundary head and int64 labels (B,h,w) at

@@ -3314,6 +3314,266 @@ def affinity_random_walk(feat, scores, *, radius=5, beta=8.0, num_iter=256):
     return random_walk(trans, scores, num_iter, radius=radius)
 
 
+# ---- class prototypes, prototype similarity maps, the pixel-to-prototype contrast loss (csrc/prototype.hip; include/wsdl_hip.h
+# "Class prototypes")
+PROTOTYPE_MAX_CHANNELS, PROTOTYPE_MAX_CLASSES = 2048, 32
+_PROTO_ACTIVATIONS = {"none": 0, "relu": 1, "softmax": 2}
+
+
+def check_prototype_options(*, feat=None, labels=None, proto=None, mass=None, present=None, pixel_weight=None, bank=None, count=None,
+                            num_classes=None, temperature=None, eps=None, momentum=None, activation=None, reduction=None, out=None,
+                            name="prototype"):
+    """Host-side validation of the prototype ops, before any device call.  WsdlError for: a ``num_classes`` that is not an int in
+    [1, 32]; a ``temperature`` or an ``eps`` that is not a finite number > 0; a ``momentum`` outside [0, 1]; an unknown
+    ``activation`` / ``reduction``; tensors of the wrong rank, type or place - ``feat`` (B,D,h,w) float32 with D <= 2048 and h w <=
+    2^20, ``labels`` (B,h,w) int64, ``pixel_weight`` (B,h,w) float32, ``proto`` (S,K,D) float32 with K <= 32, ``mass`` (S,K) float32,
+    ``present`` (S,K) bool / uint8, ``bank`` (K,D) float32 and ``count`` (K,) int64; a number of segments S that is neither 1 nor the
+    batch size, or that differs between ``proto``, ``mass`` and ``present``; an ``out`` that is not a dense float32 tensor of the
+    result's shape (``(B,K,h,w)`` beside ``proto``, else ``(proto (S,K,D), mass (S,K))``), that needs a gradient or that shares
+    memory with an input.  Returns ``(K, S)`` (None where unknown)."""
+    K = None
+    if num_classes is not None:
+        if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 1 <= num_classes <= PROTOTYPE_MAX_CLASSES:
+            raise WsdlError(f"{name}: num_classes {num_classes!r} must be an int in [1, {PROTOTYPE_MAX_CLASSES}]")
+        K = num_classes
+    for v, what in ((temperature, "temperature"), (eps, "eps")):
+        if v is not None and (not _finite_number(v) or v <= 0):
+            raise WsdlError(f"{name}: {what} {v!r} must be a finite number > 0")
+    if momentum is not None and (not _finite_number(momentum) or not 0.0 <= momentum <= 1.0):
+        raise WsdlError(f"{name}: momentum {momentum!r} must be a number in [0, 1]")
+    if activation is not None and activation not in _PROTO_ACTIVATIONS:
+        raise WsdlError(f"{name}: activation {activation!r}: 'none', 'relu' or 'softmax'")
+    if reduction is not None and reduction not in _CE_REDUCTIONS:
+        raise WsdlError(f"{name}: reduction {reduction!r}: 'mean', 'sum' or 'none'")
+    tensors = ((feat, "feat", 4, (torch.float32,)), (labels, "labels", 3, (torch.int64,)),
+               (pixel_weight, "pixel_weight", 3, (torch.float32,)), (proto, "proto", 3, (torch.float32,)),
+               (mass, "mass", 2, (torch.float32,)), (present, "present", 2, (torch.bool, torch.uint8)),
+               (bank, "bank", 2, (torch.float32,)), (count, "count", 1, (torch.int64,)))
+    for t, what, rank, dtypes in tensors:
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or t.dim() != rank:
+            raise WsdlError(f"{name}: {what} must be a tensor of rank {rank}")
+        if t.dtype not in dtypes:
+            raise WsdlError(f"{name}: {what} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+        if t.numel() == 0:
+            raise WsdlError(f"{name}: {what} {tuple(t.shape)} has an empty dimension")
+    B = D = None
+    if feat is not None:
+        B, D, h, w = feat.shape
+        if D > PROTOTYPE_MAX_CHANNELS:
+            raise WsdlError(f"{name}: feat {tuple(feat.shape)}: at most {PROTOTYPE_MAX_CHANNELS} channels")
+        if h * w > 1 << 20:
+            raise WsdlError(f"{name}: feat {tuple(feat.shape)}: h w must be at most 2^20")
+        for t, what in ((labels, "labels"), (pixel_weight, "pixel_weight")):
+            if t is not None and tuple(t.shape) != (B, h, w):
+                raise WsdlError(f"{name}: {what} {tuple(t.shape)} must be {(B, h, w)}, the size of feat {tuple(feat.shape)}")
+    S = None
+    if proto is not None:
+        S, Kp, Dp = proto.shape
+        if Kp > PROTOTYPE_MAX_CLASSES:
+            raise WsdlError(f"{name}: proto {tuple(proto.shape)}: at most {PROTOTYPE_MAX_CLASSES} classes")
+        if K is not None and Kp != K:
+            raise WsdlError(f"{name}: proto {tuple(proto.shape)} does not have num_classes = {K} classes")
+        K = Kp
+        if Dp > PROTOTYPE_MAX_CHANNELS or (D is not None and Dp != D):
+            raise WsdlError(f"{name}: proto {tuple(proto.shape)} must have the channels of feat, {D if D is not None else '<= 2048'}")
+        D = Dp
+        if B is not None and S not in (1, B):
+            raise WsdlError(f"{name}: proto {tuple(proto.shape)}: {S} segments for a batch of {B} (1 or the batch size)")
+    for t, what in ((mass, "mass"), (present, "present")):
+        if t is None:
+            continue
+        if K is not None and t.shape[1] != K:
+            raise WsdlError(f"{name}: {what} {tuple(t.shape)} must have {K} classes")
+        K = t.shape[1]
+        if K > PROTOTYPE_MAX_CLASSES:
+            raise WsdlError(f"{name}: {what} {tuple(t.shape)}: at most {PROTOTYPE_MAX_CLASSES} classes")
+        if S is not None and t.shape[0] != S:
+            raise WsdlError(f"{name}: {what} {tuple(t.shape)} has {t.shape[0]} segments, the other tensors {S}")
+        S = t.shape[0]
+        if B is not None and S not in (1, B):
+            raise WsdlError(f"{name}: {what} {tuple(t.shape)}: {S} segments for a batch of {B} (1 or the batch size)")
+    if bank is not None:
+        if bank.shape[0] > PROTOTYPE_MAX_CLASSES or bank.shape[1] > PROTOTYPE_MAX_CHANNELS:
+            raise WsdlError(f"{name}: bank {tuple(bank.shape)}: at most {PROTOTYPE_MAX_CLASSES} classes of {PROTOTYPE_MAX_CHANNELS} channels")
+        if S is not None and S != 1:
+            raise WsdlError(f"{name}: the bank takes the prototypes of one segment, got {S}")
+        if (K is not None and bank.shape[0] != K) or (D is not None and bank.shape[1] != D):
+            raise WsdlError(f"{name}: bank {tuple(bank.shape)} must be {(K, D)}")
+        K, D = bank.shape
+        if count is not None and count.shape[0] != K:
+            raise WsdlError(f"{name}: count {tuple(count.shape)} must be {(K,)}")
+        if not bank.is_contiguous() or (count is not None and not count.is_contiguous()) or bank.requires_grad:
+            raise WsdlError(f"{name}: bank and count must be dense and need no gradient")
+        if proto is not None and _shares_memory(bank, proto):
+            raise WsdlError(f"{name}: bank shares memory with proto")
+    if out is not None:
+        if feat is None:
+            raise WsdlError(f"{name}: out= needs the features it belongs to")
+        if proto is not None:
+            wanted = [(out, (B, K, feat.shape[2], feat.shape[3]), "out")]
+        else:
+            if not isinstance(out, (tuple, list)) or len(out) != 2 or K is None:
+                raise WsdlError(f"{name}: out must be a pair (proto, mass) of tensors")
+            wanted = [(out[0], None, "out[0]"), (out[1], None, "out[1]")]
+            if torch.is_tensor(out[0]) and out[0].dim() == 3:
+                So = out[0].shape[0]
+                wanted = [(out[0], (So, K, D), "out[0]"), (out[1], (So, K), "out[1]")]
+        for t, shape, what in wanted:
+            if not (torch.is_tensor(t) and shape is not None and t.dtype == torch.float32 and tuple(t.shape) == tuple(shape)
+                    and t.device == feat.device and t.is_contiguous() and not t.requires_grad):
+                raise WsdlError(f"{name}: {what} must be a dense float32 {shape if shape is not None else '(S,K,D)'} tensor on "
+                                f"{feat.device} that needs no gradient")
+            for other, oname in ((feat, "feat"), (proto, "proto"), (labels, "labels"), (pixel_weight, "pixel_weight"),
+                                 (present, "present")):
+                if other is not None and _shares_memory(t, other):
+                    raise WsdlError(f"{name}: {what} shares memory with {oname}")
+        if len(wanted) == 2 and _shares_memory(wanted[0][0], wanted[1][0]):
+            raise WsdlError(f"{name}: out[0] shares memory with out[1]")
+    device = None                                   # the place last: everything above can be refused without a device
+    for t, what, _rank, _dtypes in tensors:
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise WsdlError(f"{name}: {what}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
+        if device is None:
+            device = t.device
+        elif t.device != device:
+            raise WsdlError(f"{name}: {what} is on {t.device}, the other tensors on {device}")
+    return K, S
+
+
+def prototype_workspace(B, D, K, H, W):
+    """Bytes of scratch the prototype ops need at this geometry; 0 outside the limits (host-side)."""
+    return int(lib().wsdl_proto_workspace(int(B), int(D), int(K), int(H), int(W)))
+
+
+def _proto_ws(name, B, D, K, H, W, device):
+    nbytes = _ws_bytes("wsdl_proto_workspace", B, D, K, H, W)
+    if nbytes == 0:
+        raise WsdlError(f"{name}: bad geometry B={B} D={D} K={K} h={H} w={W}")
+    return workspace(nbytes, device)
+
+
+def _present_u8(present):
+    if present is None:
+        return None
+    present = present.detach().contiguous()
+    return present.view(torch.uint8) if present.dtype == torch.bool else present
+
+
+def class_prototypes(feat, labels, num_classes, *, pixel_weight=None, per_image=True, normalize=True, ignore_index=255, eps=1e-12,
+                     out=None):
+    """Class prototypes of float32 device features (B,D,h,w) under int64 labels (B,h,w): ``(proto, mass)`` with ``proto`` (S,K,D)
+    and ``mass`` (S,K) float32, a segment being one image (``per_image``, S = B) or the whole batch (S = 1).  ``mass[s,k]`` is the
+    sum of ``pixel_weight`` (B,h,w) float32, or of 1, over the segment's pixels with label k; labels equal to ``ignore_index`` or
+    outside [0, K) are not pooled.  ``proto[s,k]`` is the weighted mean over those pixels of the unit vector ``f_p / max(|f_p|,
+    eps)`` (``normalize``, the default) or of ``f_p``; exactly 0 where the mass is 0.  Sums in double in a fixed order, no
+    atomics: bitwise reproducible; no host read - a launch plan can hold the call.  Not differentiable (the inputs are
+    detached).  ``out``: a pair of dense float32 tensors that receive the results; they must not share memory with an input."""
+    check_prototype_options(feat=feat, labels=labels, pixel_weight=pixel_weight, num_classes=num_classes, eps=eps, out=out,
+                            name="class_prototypes")
+    feat = _dense(feat.detach(), "class_prototypes: feat")
+    labels = labels.detach().contiguous()
+    pixel_weight = None if pixel_weight is None else pixel_weight.detach().contiguous()
+    B, D, H, W = feat.shape
+    S = B if per_image else 1
+    if out is None:
+        out = (torch.empty(S, num_classes, D, device=feat.device, dtype=torch.float32),
+               torch.empty(S, num_classes, device=feat.device, dtype=torch.float32))
+    elif out[0].shape[0] != S:
+        raise WsdlError(f"class_prototypes: out[0] {tuple(out[0].shape)} must have {S} segments")
+    ws = _proto_ws("class_prototypes", B, D, num_classes, H, W, feat.device)
+    check(lib().wsdl_proto_pool(_p(feat), _p(labels), _p(pixel_weight), _p(out[0]), _p(out[1]), B, D, H, W, num_classes, int(bool(per_image)),
+                                int(bool(normalize)), int(ignore_index), float(eps), _p(ws), ws.numel(), _stream()))
+    return out[0], out[1]
+
+
+def prototype_similarity(feat, proto, *, activation="none", temperature=1.0, present=None, eps=1e-12, out=None):
+    """Cosine similarity of every pixel of float32 device features (B,D,h,w) to the prototypes (S,K,D) of its segment (S = 1: the
+    same for every image, S = B: its image's): (B,K,h,w) float32, ``<f_p / max(|f_p|, eps), q_k / max(|q_k|, eps)>``, 0 for a zero
+    prototype.  ``activation``: 'none', 'relu' (SIPE's prototype CAM) or 'softmax' - over the classes marked in ``present`` (S,K)
+    bool / uint8 (None: all) of the similarity over ``temperature``, exactly 0 for an absent class.  One pass over the features;
+    not differentiable; no host read, bitwise reproducible.  ``out``: a dense float32 tensor that receives the result."""
+    K, S = check_prototype_options(feat=feat, proto=proto, present=present, activation=activation, temperature=temperature, eps=eps,
+                                   out=out, name="prototype_similarity")
+    feat = _dense(feat.detach(), "prototype_similarity: feat")
+    proto = _dense(proto.detach(), "prototype_similarity: proto")
+    present = _present_u8(present)
+    B, D, H, W = feat.shape
+    if out is None:
+        out = torch.empty(B, K, H, W, device=feat.device, dtype=torch.float32)
+    ws = _proto_ws("prototype_similarity", B, D, K, H, W, feat.device)
+    check(lib().wsdl_proto_similarity(_p(feat), _p(proto), _p(present), _p(out), B, D, H, W, K, S, _PROTO_ACTIVATIONS[activation],
+                                      float(temperature), float(eps), _p(ws), ws.numel(), _stream()))
+    return out
+
+
+class _PrototypeContrast(torch.autograd.Function):
+    """wsdl_proto_contrast: the loss and its gradient in one pass; the backward multiplies by the upstream gradient only."""
+
+    @staticmethod
+    def forward(ctx, feat, proto, labels, present, pixel_weight, K, S, ignore_index, temperature, eps, reduction):
+        feat = _dense(feat, "prototype_contrast_loss: feat")
+        B, D, H, W = feat.shape
+        none = reduction == 2
+        loss = torch.empty((B, H, W) if none else (), device=feat.device, dtype=torch.float32)
+        dfeat = torch.empty_like(feat) if ctx.needs_input_grad[0] else None      # (asked of the argument: `feat` may be a dense copy)
+        inv = torch.empty(1, device=feat.device, dtype=torch.float32) if reduction == 0 else None
+        ws = _proto_ws("prototype_contrast_loss", B, D, K, H, W, feat.device)
+        check(lib().wsdl_proto_contrast(_p(feat), _p(proto), _p(labels), _p(present), _p(pixel_weight), _p(loss), _p(dfeat), _p(inv), B, D, H,
+                                        W, K, S, ignore_index, temperature, eps, reduction, _p(ws), ws.numel(), _stream()))
+        ctx.none = none
+        ctx.save_for_backward(dfeat, inv)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dfeat, inv = ctx.saved_tensors
+        if not ctx.none:
+            return (_scaled_grad(dfeat, g, inv),) + (None,) * 10
+        out = torch.empty_like(dfeat)
+        B, D, H, W = dfeat.shape
+        check(lib().wsdl_scale_by_pixel(_p(dfeat), _p(_dense(g, "upstream gradient")), _p(out), B, D, H, W, _stream()))
+        return (out,) + (None,) * 10
+
+
+def prototype_contrast_loss(feat, proto, labels, *, temperature=0.1, present=None, pixel_weight=None, ignore_index=255,
+                            reduction="mean", eps=1e-12):
+    """Pixel-to-prototype contrast (InfoNCE; Du et al., CVPR 2022) of float32 device features (B,D,h,w) against prototypes (S,K,D)
+    (S = 1 or B) under int64 labels (B,h,w): with ``z_{p,k} = cos(f_p, q_k) / temperature`` over the classes marked in
+    ``present`` (S,K) bool / uint8 (None: all), ``l_p = -log softmax(z_p)[label_p]``.  A pixel counts iff its label is not
+    ``ignore_index`` and its class is present; a label outside [0, K) other than ``ignore_index`` gives NaN ('none': at that pixel
+    only).  'mean' is ``sum w_p l_p / sum w_p`` over the counted pixels with ``w_p = pixel_weight`` (B,h,w) float32 or 1, and 0 -
+    with a zero gradient - when no pixel counts; 'sum' and 'none' as in ``cross_entropy``.  The gradient flows into ``feat``
+    only (the prototypes are constants, as in the papers) and comes from the same launch; an uncounted pixel gets exact zeros.
+    Sums in double in a fixed order: bitwise reproducible; no host read - a launch plan can hold the call and its backward."""
+    K, S = check_prototype_options(feat=feat, proto=proto, labels=labels, present=present, pixel_weight=pixel_weight,
+                                   temperature=temperature, eps=eps, reduction=reduction, name="prototype_contrast_loss")
+    pixel_weight = None if pixel_weight is None else pixel_weight.detach().contiguous()
+    return _PrototypeContrast.apply(feat, _dense(proto.detach(), "prototype_contrast_loss: proto"), labels.detach().contiguous(),
+                                    _present_u8(present), pixel_weight, K, S, int(ignore_index), float(temperature), float(eps),
+                                    _CE_REDUCTIONS[reduction])
+
+
+def prototype_ema_(bank, count, proto, mass, momentum):
+    """In place: ``bank[k] = momentum bank[k] + (1 - momentum) proto[k]`` and ``count[k] += 1`` for the classes with ``mass[k] >
+    0``; a class whose count was 0 takes ``proto[k]`` as it is, a class of zero mass is untouched.  ``bank`` (K,D) float32, ``count``
+    (K,) int64, ``proto`` (1,K,D) or (K,D), ``mass`` (1,K) or (K,).  One launch, no host read.  Returns ``bank``."""
+    if torch.is_tensor(proto) and proto.dim() == 2:
+        proto = proto[None]
+    if torch.is_tensor(mass) and mass.dim() == 1:
+        mass = mass[None]
+    check_prototype_options(proto=proto, mass=mass, bank=bank, count=count, momentum=momentum, name="prototype_ema_")
+    if count is None:
+        raise WsdlError("prototype_ema_: count must be a (K,) int64 tensor")
+    K, D = bank.shape
+    check(lib().wsdl_proto_ema(_p(bank), _p(count), _p(_dense(proto.detach(), "prototype_ema_: proto")),
+                               _p(_dense(mass.detach(), "prototype_ema_: mass")), K, D, float(momentum), _stream()))
+    return bank
+
+
 # ---- IRN boundary paths: affinities along the line between two pixels, their loss, the boundary CAM walk
 # (csrc/boundary_affinity.hip; include/wsdl_hip.h "IRN boundary paths")
 def affinity_paths(radius):
