@@ -8,13 +8,17 @@
 // d loss_c / d p_{i,c} = -sign([label_i == c] - p_{i,c}) (J_k - J_{k-1}) at the pixel's rank k.  The loss is the mean over
 // the classes that occur ('present') or over all of them.
 //
-// On the device: one stable radix sort of (key = e as its bit pattern - non-negative floats order like their bits,
-// value = pixel index + flag bits) per class (rocPRIM: a sort is library work, like a plain GEMM), one inclusive scan of
-// the packed (F, N) counts, one pass that forms the differences, the dot product (fixed-order two-stage sum: bitwise
-// reproducible) and scatters the gradient to the pixels.  HBM-bound: ~70 bytes per pixel and class.
-// Ignored pixels (label == ignore) get the smallest key and count for neither F nor N: the sums never see them and
-// their gradient is exactly zero - the same as removing them (flatten_probas).  Ties in e are ordered by pixel index
-// (the reference: whatever torch.sort does); the loss does not depend on the order inside a tie.
+// On the device: one stable radix sort of (key = e as its bit pattern with the sign bit set - non-negative floats order
+// like their bits -, value = pixel index + flag bits) per class (rocPRIM: a sort is library work, like a plain GEMM), one
+// inclusive scan of the packed (F, N) counts, one pass that forms the differences, the dot product (fixed-order two-stage
+// sum: bitwise reproducible) and scatters the gradient to the pixels.  HBM-bound: ~70 bytes per pixel and class.
+// Ignored pixels (label == ignore) get key 0, which no valid pixel has (e is never negative, so its sign bit is free: the bit
+// order_bits() of lovasz_seg.hip sets): they sort strictly behind EVERY valid pixel, one with e == 0 included, and count for
+// neither F nor N: the sums never see them and their gradient is exactly zero - the same as removing them (flatten_probas).
+// So the sorted prefix in front of a valid pixel is empty or holds a valid pixel, and no J is formed from G + N == 0 (an
+// ignored pixel in front of the valid ones of an absent class whose errors are all 0 gave 1 - 0 / 0 = NaN).
+// Ties in e are ordered by pixel index (the reference: whatever torch.sort does); the loss does not depend on the order
+// inside a tie.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -29,6 +33,7 @@ namespace {
 
 constexpr int kThreadsL = 256;
 constexpr unsigned kFg = 0x80000000u, kValid = 0x40000000u, kIdx = 0x3fffffffu;
+constexpr unsigned kValidKey = 0x80000000u;     // set in the key of every valid pixel, stripped where the key is read back
 constexpr int kParts = 1024;
 
 // counts[c] = pixels of class c (labels outside [0, C) and the ignored label are in no class).  One global atomic per
@@ -87,7 +92,7 @@ __global__ void lov_keys_kernel(const float* __restrict__ probas, const int64_t*
         const bool valid = l != ignore;
         const bool fg = valid && l == c;
         const float e = fabsf((fg ? 1.f : 0.f) - p);
-        keys[i] = valid ? __float_as_uint(e) : 0u;
+        keys[i] = valid ? (__float_as_uint(e) | kValidKey) : 0u;
         vals[i] = (unsigned)i | (fg ? kFg : 0u) | (valid ? kValid : 0u);
     }
 }
@@ -122,7 +127,7 @@ __global__ void lov_apply_kernel(const unsigned* __restrict__ keys, const unsign
         const float jk = jaccard(cum[k], G);
         const float jp = k > 0 ? jaccard(cum[k - 1], G) : 0.f;
         const float g = k > 0 ? jk - jp : jk;
-        const float e = __uint_as_float(keys[k]);
+        const float e = __uint_as_float(keys[k] & ~kValidKey);
         acc += (double)e * (double)g;
         if (dprobas) {
             const long long i = v & kIdx;
