@@ -722,6 +722,44 @@ int wsdl_grad_clip_finalize(const double* partials, int n_partials, const float*
 int wsdl_flat_step_dev(int algo, float* p, const float* g, float* m, float* v, size_t n, const uint8_t* decay_blocks,
                        const float* hyper_dev, const int* step_dev, const float* stats_dev, wsdl_stream_t stream);
 
+/* ---- EMA teacher: the average of the weights over training, and the teacher's label correction (csrc/ema.hip) -
+ * The "mean teacher" copy (Tarvainen & Valpola, NeurIPS 2017) of the flat parameter buffer, as launches ordered behind the step
+ * launch.  Per element, in double and rounded once:  e <- float( fma(a, double(p) - double(e), double(e)) ),  a = 1 - d,
+ * d = decay, or with warm-up d = min(decay, float((1 + k) / (10 + k))) - the ratio formed in double and rounded to float32, so
+ * that d is a float either way and a a dyadic number of at most 27 bits (a 53-bit 9 / (10 + k) puts exact results on float32
+ * ties, which fused and unfused evaluations break differently) -, k = max(0, *step_dev - *start_dev - 1) = the updates already
+ * applied: step_dev is the optimiser's device step number (a skipped step does not advance it), start_dev a device copy of it
+ * taken when the average was attached or reset.  hyper_ema_dev = two floats {decay, warmup != 0} in device memory; a is formed
+ * in double from the float decay.  a == 1 (decay 0) is a copy, e = p exactly.  stats_dev (optional) is the flat optimiser's:
+ * apply == 0 returns at once, e untouched.  A NaN or inf in p propagates into e: skip_nonfinite is the guard, there is none here.
+ * wsdl_flat_ema: one launch over n floats, float4 loads and stores, grid stride over a capped grid, a scalar tail of n & 3
+ * elements; 16-byte aligned, non-overlapping buffers.  No atomics: bitwise reproducible.
+ * wsdl_ema_table: one launch for many small tensors (BatchNorm running statistics): table_dev = `count` wsdl_ema_entry in device
+ * memory; workgroup (x, y) handles the chunks y, y + 4, ... of 1024 floats of the tensors x, x + gridDim.x, ...; mode 0 = the
+ * formula above, mode 1 = dst = src (hyper_ema_dev, step_dev, start_dev may then be NULL).  4-byte aligned pointers: a tensor
+ * whose two pointers are not both 16-byte aligned takes a scalar path.  The same skip test.  Tensors must not overlap. */
+typedef struct {
+    float* dst;
+    const float* src;
+    long long numel;
+} wsdl_ema_entry;
+int wsdl_flat_ema(float* e, const float* p, size_t n, const float* hyper_ema_dev, const int* step_dev, const int* start_dev,
+                  const float* stats_dev, wsdl_stream_t stream);
+int wsdl_ema_table(const wsdl_ema_entry* table_dev, int count, const float* hyper_ema_dev, const int* step_dev, const int* start_dev,
+                   const float* stats_dev, int mode, wsdl_stream_t stream);
+/* Label correction from teacher logits (B,C,H,W) float32, C <= WSDL_TEACHER_MAX_CLASSES, and the current labels (B,H,W) int64, one
+ * pass: t = the first class of largest logit, p = float(1 / sum_c exp(double(l_c) - double(l_t))) (the softmax maximum); a pixel
+ * with any non-finite logit has p = 0 and is never confident; a pixel is confident iff p >= *tau_dev (one float in device
+ * memory).  y == ignore_index: y' = y, conf = 0.  Otherwise conf = p and, where the pixel is confident and t != y, y' = t (mode 0,
+ * "replace") or y' = ignore_index (mode 1, "ignore"); else y' = y.  out_conf (B,H,W) float32 and counts may be NULL; counts[0..2]
+ * += (pixels with y' == y that were not ignored on input, pixels with y' != y, pixels ignored on input) - integer atomics, one
+ * per counter and workgroup: exact and order-independent.  Four pixels per lane where H W % 4 == 0; the channels of C = 2 and 3
+ * are held in registers, any other C reads its pixel's channels twice (no per-lane array: no scratch).  No host read, every
+ * parameter by value: a launch plan can hold the call. */
+#define WSDL_TEACHER_MAX_CLASSES 64
+int wsdl_teacher_targets(const float* logits, const long long* labels, int B, int C, int H, int W, const float* tau_dev, int mode,
+                         long long ignore_index, long long* out_labels, float* out_conf, long long* counts, wsdl_stream_t stream);
+
 /* ---- pixel mining: selecting pixels by their loss without a host read (csrc/pixel_mining.hip) -
  * wsdl_kth_value: x holds `segments` runs of n_per_segment floats.  The candidates of segment s are the x[s*n + i] that are
  * not NaN and, when `valid` (one byte per element) is given, have valid[s*n + i] != 0; n_valid[s] receives their number n.

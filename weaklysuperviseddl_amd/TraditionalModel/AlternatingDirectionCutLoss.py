@@ -168,7 +168,7 @@ def train_model(model, optimizer, criterion_ce=None, num_epochs=3, *, train_load
 
 
 def refine_dataset(model, dataset, repeats=5, chunk=64, threshold=0.3, lr=1e-4, num_steps=10, lambda_boundary=0.1,
-                   sigma_color=0.1, window_size=5, method="ncut", pamr_kwargs=None, superpixel_kwargs=None):
+                   sigma_color=0.1, window_size=5, method="ncut", pamr_kwargs=None, superpixel_kwargs=None, teacher_kwargs=None):
     """Step 2 of an alternation (AlternatingDirectionCutLoss.py:803-810): ``repeats`` passes over the data set, each
     refining every pseudo mask and overwriting it - pass r+1 starts from pass r's thresholded masks, because the
     reference's dataset re-reads the PNG it has just overwritten.  In memory: ``dataset.set_masks``.  The network is
@@ -182,9 +182,23 @@ def refine_dataset(model, dataset, repeats=5, chunk=64, threshold=0.3, lr=1e-4, 
     ``method="superpixel"`` (no such step in the reference either): each chunk's masks become
     ``ops.superpixel_snap(network_soft_prediction(model, imgs), segments, n_max)[:, 1] > threshold`` with ``segments`` the
     ``ops.slic`` superpixels of the chunk's images (quantised with ``ops.slic_quantize``) and ``superpixel_kwargs`` the keywords
-    of ``ops.slic`` (default: ``step=16``).  One pass, as for ``"pamr"``."""
-    if method not in ("ncut", "pamr", "superpixel"):
-        raise ValueError(f"refine_dataset: method {method!r}: 'ncut', 'pamr' or 'superpixel'")
+    of ``ops.slic`` (default: ``step=16``).  One pass, as for ``"pamr"``.
+
+    ``method="teacher"`` (no such step in the reference either): label correction by ``model`` - meant to be an EMA teacher
+    (``ema.FlatEMA``; ``run_alternating_training(ema=)`` passes it).  Each chunk's masks become ``ops.teacher_targets(model(imgs)
+    ["out"] in eval mode, masks.long() clamped to {0, 1}, **teacher_kwargs).float()``: a label changes only where the network's
+    softmax maximum reaches ``tau`` (default 0.9) and disagrees.  ``mode`` must be 'replace' (the default): the stored masks
+    are {0, 1}, there is no ignore value to store, so 'ignore' is refused; -100 never reaches ``set_masks``.  One pass."""
+    if method not in ("ncut", "pamr", "superpixel", "teacher"):
+        raise ValueError(f"refine_dataset: method {method!r}: 'ncut', 'pamr', 'superpixel' or 'teacher'")
+    if method == "teacher":
+        t_kwargs = dict(teacher_kwargs or {})
+        if t_kwargs.setdefault("mode", "replace") != "replace":
+            raise ValueError("refine_dataset: method 'teacher' in 'ignore' mode: the stored masks are {0, 1} and cannot hold an "
+                             "ignore value; use mode='replace' here (train_step_mean_teacher takes 'ignore' online)")
+        for k in ("out", "conf", "counts"):
+            if t_kwargs.get(k) not in (None, False):
+                raise ValueError(f"refine_dataset: teacher_kwargs[{k!r}] is not supported here")
     if method == "superpixel":
         sp_kwargs = dict(superpixel_kwargs) if superpixel_kwargs else {"step": 16}
         sp_step, _, _, sp_min = ops.check_slic_options(**dict(sp_kwargs, name="refine_dataset: superpixel_kwargs"))
@@ -192,6 +206,13 @@ def refine_dataset(model, dataset, repeats=5, chunk=64, threshold=0.3, lr=1e-4, 
     for s in range(0, n, chunk):
         idx = torch.arange(s, min(s + chunk, n), device=dataset.images.device)
         imgs = dataset.images[idx]
+        if method == "teacher":
+            model.eval()
+            with torch.no_grad():
+                logits = model(imgs)["out"]
+            labels = ops.clamp_max_labels(dataset.masks[idx].long(), 1)
+            dataset.set_masks(idx, ops.teacher_targets(logits, labels, **t_kwargs).float())
+            continue
         S = network_soft_prediction(model, imgs)
         if method == "pamr":
             dataset.set_masks(idx, (ops.pamr(imgs, S, **(pamr_kwargs or {}))[:, 1] > threshold).float())
@@ -213,7 +234,7 @@ def refine_dataset(model, dataset, repeats=5, chunk=64, threshold=0.3, lr=1e-4, 
 
 def run_alternating_training(model, optimizer, dataset, num_alternations=10, epochs_per_round=10, refine_repeats=5,
                              first_batch_size=4, later_batch_size=32, refine_chunk=64, refine_kwargs=None,
-                             evaluate=None, seed=0, device="cuda", log=print, augment=None):
+                             evaluate=None, seed=0, device="cuda", log=print, augment=None, ema=None):
     """The alternating-direction outer loop (reference AlternatingDirectionCutLoss.py:791-818; the modular re-write
     AlternatingDirectionBoundaryLoss.py:153-206 is dead code): per alternation
       1. ``train_model`` for ``epochs_per_round`` epochs on the current pseudo masks (batch 4 in the first
@@ -227,8 +248,14 @@ def run_alternating_training(model, optimizer, dataset, num_alternations=10, epo
     collective.  ``augment``: an ``augment.Augment`` handed to ``dataset.batches`` - the training batches
     only; refinement reads the stored images and masks (the reference has no augmentation).  ``refine_kwargs`` goes to
     ``refine_dataset``: ``{"method": "pamr"}`` refines with ``ops.pamr`` instead of the normalised-cut descent,
-    ``{"method": "superpixel", "superpixel_kwargs": {...}}`` with superpixel means of the network's prediction."""
+    ``{"method": "superpixel", "superpixel_kwargs": {...}}`` with superpixel means of the network's prediction.
+    ``ema``: an ``ema.FlatEMA`` attached to ``optimizer``.  Training is unchanged (the average follows every step by itself);
+    step 2's ``evaluate`` and step 3's ``refine_dataset`` receive ``ema.teacher`` - the average of the weights over training -
+    instead of the raw weights the last minibatch left; ``refine_kwargs={"method": "teacher"}`` makes step 3 the teacher's
+    label correction."""
     import torch.distributed as dist
+    if ema is not None and (ema.opt is not optimizer or ema.model is not model):
+        raise ValueError("run_alternating_training: ema must be the FlatEMA of this model and this optimizer")
     rk = dict(threshold=0.3, lr=1e-4, num_steps=10, lambda_boundary=0.1)
     rk.update(refine_kwargs or {})
     dp = dist.is_initialized() and dist.get_world_size() > 1
@@ -247,10 +274,11 @@ def run_alternating_training(model, optimizer, dataset, num_alternations=10, epo
         losses = train_model(model, optimizer, None, epochs_per_round,
                              train_loader=lambda: dataset.batches(bs, shuffle=True, generator=gen, limit=steps, **kw),
                              device=device, log=log if rank == 0 else None)
-        metrics = evaluate(model) if evaluate is not None else None
+        judge = model if ema is None else ema.teacher
+        metrics = evaluate(judge) if evaluate is not None else None
         if log and rank == 0 and metrics is not None:
             log(f"Iteration {it + 1}: Evaluation -> {metrics}")
-        refine_dataset(model, dataset, repeats=refine_repeats, chunk=refine_chunk, **rk)
+        refine_dataset(judge, dataset, repeats=refine_repeats, chunk=refine_chunk, **rk)
         history.append({"losses": losses, "metrics": metrics})
     if log and rank == 0:
         log("Alternating training and pseudo mask updates completed.")

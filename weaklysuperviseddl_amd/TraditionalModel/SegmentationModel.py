@@ -403,6 +403,32 @@ def _train_step_eager(model, optimizer, images, masks, extra_loss=None, loss_fn=
     return loss.detach()
 
 
+def train_step_mean_teacher(model, ema, optimizer, images, masks, criterion=None, *, tau=0.9, mode="ignore", weight_by_conf=False):
+    """One mean-teacher iteration: the EMA teacher (``ema.FlatEMA`` attached to ``optimizer``) corrects the batch's noisy labels,
+    then the ordinary ``train_step`` runs on the corrected masks; returns its loss tensor.
+
+    The teacher's eval-mode forward runs eagerly under ``no_grad``; ``ops.teacher_targets(teacher logits, masks clamped to
+    {0, 1}, tau, mode)`` makes the labels - ``mode="ignore"`` (default) writes -100 where the teacher is confident and
+    disagrees, which survives ``train_step``'s clamp and is the cross entropy's default ignore value; ``"replace"`` writes the
+    teacher's class.  ``tau``: a number or a one-element float32 device tensor (a schedule).  ``weight_by_conf``: the teacher's
+    confidence becomes the pixel weight of ``criterion``, which must then be a ``wnn.CrossEntropyLoss``
+    (``criterion.set_pixel_weight(conf)``).  The student's step is the same call as without a teacher, so from its third
+    occurrence it replays its launch plan - the corrected masks are plan inputs - and the EMA launches are part of that plan."""
+    if ema is None or getattr(optimizer, "ema", None) is not ema or ema.model is not model:
+        raise ValueError("train_step_mean_teacher: ema must be the FlatEMA attached to this optimizer for this model")
+    if weight_by_conf and not isinstance(criterion, wnn.CrossEntropyLoss):
+        raise ValueError("train_step_mean_teacher: weight_by_conf needs criterion=wnn.CrossEntropyLoss(...) (set_pixel_weight)")
+    with torch.no_grad():
+        logits = ema.teacher(images)["out"]
+    labels = ops.clamp_max_labels(masks.long(), 1)
+    if weight_by_conf:
+        labels, conf = ops.teacher_targets(logits, labels, tau, mode, conf=True)
+        criterion.set_pixel_weight(conf)
+    else:
+        labels = ops.teacher_targets(logits, labels, tau, mode)
+    return train_step(model, optimizer, images, labels, criterion=criterion)
+
+
 def make_optimizer(model, lr=1e-4, early_step=None, *, kind="adam", **optimizer_kwargs):
     """torch.optim.Adam(model.parameters(), lr) semantics on one flat buffer.  ``kind``: 'adam' (optim.FlatAdam), 'adamw'
     (optim.FlatAdamW) or 'sgd' (optim.FlatSGD); ``optimizer_kwargs`` go to that class (weight_decay, momentum, nesterov,
@@ -591,7 +617,7 @@ def evaluate_surface_distances(model, loader, device="cuda", binarize="notebook"
 
 def train_segmentation_model(loss_fn, run_id, lr=1e-4, num_epochs=10, batch_size=4, val_split=0.2, *, out_root="/content",
                              device="cuda", val_loader=None, num_workers=0, seed=None, log=print, model=None,
-                             optimizer_kind="adam", optimizer_kwargs=None, criterion=None):
+                             optimizer_kind="adam", optimizer_kwargs=None, criterion=None, ema=None):
     """Reference ``train_segmentation_model(loss_fn, run_id, lr=1e-4, num_epochs=10, batch_size=4, val_split=0.2)``
     (TraditionalModel/SegmentationModel.py:59-122), same positional signature, returns ``(model, final_loss)``.
 
@@ -608,7 +634,10 @@ def train_segmentation_model(loss_fn, run_id, lr=1e-4, num_epochs=10, batch_size
     device, an existing model to continue from, ``optimizer_kind`` / ``optimizer_kwargs`` (``make_optimizer``'s ``kind`` and
     keyword arguments; the default is the reference's Adam(lr)), ``criterion`` (handed to ``train_step`` in place of
     ``loss_fn``'s loss, e.g. ``wnn.MinedCrossEntropyLoss(mode="trim", drop_frac=0.2)`` against the label noise of the pseudo
-    masks; ``None``: the ``loss_fn`` loss as before)."""
+    masks; ``None``: the ``loss_fn`` loss as before), ``ema`` (a dict of ``ema.FlatEMA`` keywords, e.g. ``{"decay": 0.999}``: a
+    teacher - a second ``build_segmentation_model`` - follows the weights by their moving average; it is validated beside
+    the student, and the ``FlatEMA`` is left as ``model.ema``, its ``teacher`` the network to predict and refine with;
+    ``None``: no launch is added)."""
     from torch.utils.data import DataLoader
     from .SegmentationDataset import PseudoSegmentationDataset
     if loss_fn not in ("cross_entropy", "lovasz_softmax", "lovasz_hinge"):
@@ -623,6 +652,13 @@ def train_segmentation_model(loss_fn, run_id, lr=1e-4, num_epochs=10, batch_size
         model = build_segmentation_model(num_classes=2)
     model = model.to(device)
     optimizer = make_optimizer(model, lr=lr, kind=optimizer_kind, **(optimizer_kwargs or {}))
+    averaged = None
+    if ema is not None:
+        from ..ema import FlatEMA
+        num_classes = model.classifier[-1].out_channels if isinstance(model, SegmentationModel) else 2
+        teacher = build_segmentation_model(num_classes=num_classes, aux_loss=getattr(model, "aux_classifier", None) is not None)
+        averaged = FlatEMA(optimizer, model, teacher.to(device), **dict(ema))
+        model.ema = averaged                            # (a plain object: not a sub-module, not part of the state dict)
     final_loss = 0.0
     for epoch in range(num_epochs):
         model.train()
@@ -638,4 +674,8 @@ def train_segmentation_model(loss_fn, run_id, lr=1e-4, num_epochs=10, batch_size
             avg_iou, avg_acc = evaluate_model(model, val_loader, device=device, binarize="modular")
             if log:
                 log(f"[Run {run_id}] Validation IoU: {avg_iou:.4f}, Accuracy: {avg_acc:.4f}")
+            if averaged is not None:
+                t_iou, t_acc = evaluate_model(averaged.teacher, val_loader, device=device, binarize="modular")
+                if log:
+                    log(f"[Run {run_id}] EMA teacher validation IoU: {t_iou:.4f}, Accuracy: {t_acc:.4f}")
     return model, final_loss

@@ -3,7 +3,7 @@ from .ClassificationModel import FrozenResNetCAM, train_fc_only, evaluate_classi
 from .LayerCAM import LayerCAMGenerator, CAMGenerator, evaluate_layercam_on_test_set  # noqa: F401
 from .PsuedoMasks import (generate_pseudo_masks, keep_largest, generate, stage_handoff, generate_prototype_pseudo_masks,  # noqa: F401
                           prototype_cam)
-from .SegmentationModel import (SegmentationModel, build_segmentation_model, train_step, evaluate_model,  # noqa: F401
+from .SegmentationModel import (SegmentationModel, build_segmentation_model, train_step, train_step_mean_teacher, evaluate_model,  # noqa: F401
                                 train_segmentation_model, evaluate_boundary_iou, evaluate_surface_distances,
                                 predict_multiscale)
 from .AlternatingDirectionCutLoss import (  # noqa: F401

@@ -112,6 +112,9 @@ SIGNATURES = {
     "wsdl_grad_sqnorm_partials": (_i, [_vp, _sz, _vp, _vp]),
     "wsdl_grad_clip_finalize": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "wsdl_flat_step_dev": (_i, [_i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "wsdl_flat_ema": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "wsdl_ema_table": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "wsdl_teacher_targets": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _ll, _vp, _vp, _vp, _vp]),
     "wsdl_kth_workspace": (_sz, [_i]),
     "wsdl_kth_value": (_i, [_vp, _vp, _ll, _i, _i, _ll, C.c_double, _vp, _vp, _vp, _sz, _vp]),
     "wsdl_mining_valid": (_i, [_vp, _ll, _vp, _vp, _ll, _vp]),

@@ -47,7 +47,8 @@ class GraphedTrainStep:
         launch_key = getattr(self.opt, "launch_key", None)
         if launch_key is not None and launch_key() != (None, False, False):
             raise RuntimeError("GraphedTrainStep supports the default FlatAdam step only; with weight decay, FlatSGD, FlatAdamW, "
-                               "max_grad_norm or skip_nonfinite call train_step directly (its launch plan covers them)")
+                               "max_grad_norm, skip_nonfinite or an attached EMA (ema.FlatEMA) call train_step directly (its "
+                               "launch plan covers them)")
 
     def _eager(self, images, masks):
         return self._train_step(self.model, self.opt, images, masks, self.extra_loss)

@@ -4780,6 +4780,155 @@ def flat_step(algo, p, g, m, v, hyper_dev, step_dev, stats_dev=None, decay_block
                                    _p(step_dev), _p(stats_dev), _stream()))
 
 
+# ---- EMA teacher (csrc/ema.hip; include/wsdl_hip.h "EMA teacher") -----------------------------------------------------------
+TEACHER_MAX_CLASSES = 64                          # WSDL_TEACHER_MAX_CLASSES
+_TEACHER_MODES = {"replace": 0, "ignore": 1}
+_EMA_TABLE_MODES = {"ema": 0, "copy": 1}
+EMA_ENTRY_DTYPE = np.dtype([("dst", np.uint64), ("src", np.uint64), ("numel", np.int64)])      # wsdl_ema_entry
+
+
+def _ema_words(name, hyper_ema_dev, step_dev, start_dev, stats_dev):
+    _req(hyper_ema_dev, f"{name}: hyper_ema_dev")
+    _req(step_dev, f"{name}: step_dev", torch.int32)
+    _req(start_dev, f"{name}: start_dev", torch.int32)
+    if hyper_ema_dev.numel() < 2 or step_dev.numel() != 1 or start_dev.numel() != 1:
+        raise WsdlError(f"{name}: hyper_ema_dev of two floats (decay, warmup), step_dev and start_dev of one int32 each")
+    if stats_dev is not None and _req(stats_dev, f"{name}: stats_dev").numel() < FLAT_STATS:
+        raise WsdlError(f"{name}: stats_dev of {FLAT_STATS} floats")
+
+
+def flat_ema(e, p, hyper_ema_dev, step_dev, start_dev, stats_dev=None):
+    """In place, one launch: ``e <- float(fma(a, double(p) - double(e), double(e)))`` over dense float32 device buffers of one
+    size, ``a = 1 - d``, ``d = decay`` or, with warm-up, ``min(decay, float32((1 + k) / (10 + k)))`` for ``k = step_dev - start_dev - 1``
+    updates already applied (``d`` is a float32 either way: with a 53-bit ``9 / (10 + k)`` exact results land on float32 ties,
+    which a fused and an unfused multiply-add break differently).  ``hyper_ema_dev``: two device floats (decay, warmup); ``step_dev`` / ``start_dev``: one-element
+    int32 device tensors; ``stats_dev``: the flat optimiser's statistics - a skipped step leaves ``e`` untouched (None: no test).
+    Decay 0 copies.  A NaN or inf in ``p`` propagates.  No host read, bitwise reproducible.  Returns ``e``."""
+    for t, what in ((e, "e"), (p, "p")):
+        _req(t, f"flat_ema: {what}")
+        if not t.is_contiguous() or t.numel() != e.numel() or t.numel() == 0:
+            raise WsdlError("flat_ema: buffers must be dense, of one size and not empty")
+    if _shares_memory(e, p):
+        raise WsdlError("flat_ema: e shares memory with p")
+    _ema_words("flat_ema", hyper_ema_dev, step_dev, start_dev, stats_dev)
+    check(lib().wsdl_flat_ema(_p(e), _p(p), e.numel(), _p(hyper_ema_dev), _p(step_dev), _p(start_dev), _p(stats_dev), _stream()))
+    return e
+
+
+def ema_table_entries(pairs, device):
+    """The device table of ``ema_table`` for ``pairs`` = [(dst, src)] of dense float32 device tensors of equal size: a uint8
+    tensor holding one ``wsdl_ema_entry`` (dst, src, numel) per pair.  The caller keeps the tensors alive and at their
+    addresses."""
+    rows = np.zeros(len(pairs), dtype=EMA_ENTRY_DTYPE)
+    for i, (dst, src) in enumerate(pairs):
+        for t, what in ((dst, "dst"), (src, "src")):
+            _req(t, f"ema_table: {what}")
+            if not t.is_contiguous() or t.numel() == 0:
+                raise WsdlError(f"ema_table: {what} of entry {i} must be dense and not empty")
+        if dst.numel() != src.numel() or _shares_memory(dst, src):
+            raise WsdlError(f"ema_table: entry {i}: dst and src must have one size and share no memory")
+        rows[i] = (dst.data_ptr(), src.data_ptr(), dst.numel())
+    return torch.from_numpy(rows.view(np.uint8).copy()).to(device)
+
+
+def ema_table(table_dev, count, hyper_ema_dev, step_dev, start_dev, stats_dev=None, mode="ema"):
+    """One launch over the ``count`` tensors of ``table_dev`` (``ema_table_entries``): ``mode`` 'ema' - the update of ``flat_ema``
+    on every (dst, src) - or 'copy' - dst = src.  The same skip test as ``flat_ema``.  No host read, bitwise reproducible."""
+    if mode not in _EMA_TABLE_MODES:
+        raise WsdlError(f"ema_table: mode {mode!r}: 'ema' or 'copy'")
+    _req(table_dev, "ema_table: table", torch.uint8)
+    if count <= 0 or table_dev.numel() < count * EMA_ENTRY_DTYPE.itemsize or not table_dev.is_contiguous():
+        raise WsdlError(f"ema_table: a dense table of {count} entries of {EMA_ENTRY_DTYPE.itemsize} bytes")
+    _ema_words("ema_table", hyper_ema_dev, step_dev, start_dev, stats_dev)
+    check(lib().wsdl_ema_table(_p(table_dev), int(count), _p(hyper_ema_dev), _p(step_dev), _p(start_dev), _p(stats_dev),
+                               _EMA_TABLE_MODES[mode], _stream()))
+
+
+def check_teacher_targets_options(logits, labels, tau, mode, ignore_index, out, conf, counts, name="teacher_targets"):
+    """Host-side validation of ``teacher_targets``, before any device call.  WsdlError for: an unknown ``mode``; a ``tau`` that is
+    neither a number (not NaN) nor a one-element float32 tensor; an ``ignore_index`` that is not an int; ``logits`` not a (B,C,H,W)
+    float32 tensor with 1 <= C <= 64, ``labels`` not a (B,H,W) int64 tensor of its size, an empty dimension; ``out`` / a ``conf``
+    tensor / ``counts`` that is not a dense int64 (B,H,W) / float32 (B,H,W) / int64 (3,) tensor, or that shares memory with an
+    input or with another output; tensors that are not on one device."""
+    if mode not in _TEACHER_MODES:
+        raise WsdlError(f"{name}: mode {mode!r}: 'replace' or 'ignore'")
+    if torch.is_tensor(tau):
+        if tau.numel() != 1 or tau.dtype != torch.float32:
+            raise WsdlError(f"{name}: tau as a tensor must hold one float32")
+    elif isinstance(tau, bool) or not isinstance(tau, (int, float)) or tau != tau:
+        raise WsdlError(f"{name}: tau {tau!r} must be a number or a one-element float32 device tensor")
+    if isinstance(ignore_index, bool) or not isinstance(ignore_index, int):
+        raise WsdlError(f"{name}: ignore_index {ignore_index!r} must be an int")
+    if not isinstance(conf, bool) and not torch.is_tensor(conf):
+        raise WsdlError(f"{name}: conf must be True, False or a float32 (B,H,W) tensor to fill")
+    tensors = [(logits, "logits", 4, torch.float32), (labels, "labels", 3, torch.int64)]
+    for t, what, rank, dtype in tensors:
+        if not torch.is_tensor(t) or t.dim() != rank:
+            raise WsdlError(f"{name}: {what} must be a tensor of rank {rank}")
+        if t.dtype != dtype:
+            raise WsdlError(f"{name}: {what} must be {dtype}, got {t.dtype}")
+        if t.numel() == 0:
+            raise WsdlError(f"{name}: {what} {tuple(t.shape)} has an empty dimension")
+    B, Cc, H, W = logits.shape
+    if Cc > TEACHER_MAX_CLASSES:
+        raise WsdlError(f"{name}: logits {tuple(logits.shape)}: at most {TEACHER_MAX_CLASSES} classes")
+    if tuple(labels.shape) != (B, H, W):
+        raise WsdlError(f"{name}: labels {tuple(labels.shape)} must be {(B, H, W)}, the size of logits {tuple(logits.shape)}")
+    outs = []
+    for t, what, shape, dtype in ((out, "out", (B, H, W), torch.int64), (conf if torch.is_tensor(conf) else None, "conf", (B, H, W), torch.float32),
+                                  (counts, "counts", (3,), torch.int64)):
+        if t is None:
+            continue
+        if not (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and not t.requires_grad):
+            raise WsdlError(f"{name}: {what} must be a dense {dtype} {shape} tensor that needs no gradient")
+        inputs = [(logits, "logits"), (labels, "labels")] + ([(tau, "tau")] if torch.is_tensor(tau) else [])
+        for other, oname in inputs:
+            if _shares_memory(t, other):
+                raise WsdlError(f"{name}: {what} shares memory with {oname}")
+        for o, oname in outs:
+            if _shares_memory(t, o):
+                raise WsdlError(f"{name}: {what} shares memory with {oname}")
+        outs.append((t, what))
+        tensors.append((t, what, None, None))
+    if torch.is_tensor(tau):
+        tensors.append((tau, "tau", None, None))
+    device = None                                   # the place last: everything above can be refused without a device
+    for t, what, _rank, _dtype in tensors:
+        if not t.is_cuda:
+            raise WsdlError(f"{name}: {what}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
+        if device is None:
+            device = t.device
+        elif t.device != device:
+            raise WsdlError(f"{name}: {what} is on {t.device}, the other tensors on {device}")
+
+
+def teacher_targets(logits, labels, tau=0.9, mode="replace", ignore_index=-100, out=None, conf=False, counts=None):
+    """Label correction from a teacher's float32 device logits (B,C,H,W), C <= 64, and the current int64 labels (B,H,W), in one
+    pass: with ``t`` the first class of largest logit and ``p = float(1 / sum_c exp(double(l_c) - double(l_t)))`` a pixel is
+    CONFIDENT iff ``p >= tau`` (a pixel with a non-finite logit never is).  ``mode`` 'replace': a confident pixel with ``t != y``
+    takes ``t``; 'ignore': it takes ``ignore_index``; every other pixel - and every pixel that is ``ignore_index`` on input -
+    keeps its label.  Returns the corrected labels, or ``(labels, conf)`` with ``conf=True`` (or a float32 (B,H,W) tensor to
+    fill): ``p`` at every pixel that is not ignored on input, 0 there and at non-finite pixels.  ``tau``: a number, or a
+    one-element float32 device tensor (a schedule changes memory, a launch plan stays).  ``counts``: an int64 (3,) device tensor
+    that receives ``+= (kept, changed, ignored on input)`` (exact integer atomics).  ``out``: a dense int64 tensor to fill.  The
+    inputs are not modified; no host read; bitwise reproducible."""
+    check_teacher_targets_options(logits, labels, tau, mode, ignore_index, out, conf, counts)
+    logits = _dense(logits.detach(), "teacher_targets: logits")
+    labels = labels.detach().contiguous()
+    B, Cc, H, W = logits.shape
+    if not torch.is_tensor(tau):
+        tau = torch.full((1,), float(tau), device=logits.device, dtype=torch.float32)      # (a fill on the stream: no host read)
+    if out is None:
+        out = torch.empty_like(labels)
+    if conf is True:
+        conf = torch.empty(B, H, W, device=logits.device, dtype=torch.float32)
+    elif conf is False:
+        conf = None
+    check(lib().wsdl_teacher_targets(_p(logits), _p(labels), B, Cc, H, W, _p(tau), _TEACHER_MODES[mode], int(ignore_index), _p(out),
+                                     _p(conf), _p(counts), _stream()))
+    return out if conf is None else (out, conf)
+
+
 def softmax_channels(x):
     return _SoftmaxChannels.apply(x)
 

@@ -3,7 +3,8 @@ reference TraditionalModel/SegmentationModel.py:91) as ONE kernel launch over fl
 decay (L2 or decoupled: ``FlatAdamW``), SGD with momentum (``FlatSGD``), clipping by the global gradient norm, skipping of steps
 whose gradient is not finite, parameters without decay, and ``PolyLR`` - all of it read from device memory by the kernels of
 csrc/flat_optim.hip, so a launch plan of the step survives a schedule; with those arguments at their defaults the launches are
-the ones below, unchanged.
+the ones below, unchanged.  An ``ema.FlatEMA`` registers itself as ``optimizer.ema``: its average of the parameters is one
+more launch right behind every step launch, on that launch's range (``_launch_ema``); without one nothing is added.
 
 Parameters are re-homed into one contiguous fp32 buffer (``p.data`` become views) and so are their
 gradients (``p.grad`` views of one flat buffer), which is also what the data-parallel gradient
@@ -89,6 +90,7 @@ class FlatAdam:
     algorithm, but not the default launch bit for bit (``g += 0 * p`` makes the gradient of a parameter that is already inf
     a NaN, where the default kernel never multiplies the parameter)."""
     _early_step = False
+    ema = None                      # an ``ema.FlatEMA`` registers itself here: its launches follow every step launch
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, *, weight_decay=0.0, decoupled=False,
                  max_grad_norm=None, skip_nonfinite=False, no_decay=None):
@@ -254,6 +256,9 @@ class FlatAdam:
                 self.step_count += 1
                 ops.add_int(self.step_dev, 1)
             self._launch(lo, hi)
+            if self.ema is not None:
+                # the average of this segment right behind its step; the buffers once, behind the last segment
+                self._launch_ema(lo, hi, last=sum(self._stepped) == len(self.segments) - 1)
             if not self.capture_mode:
                 ev = self._seg_events[k]               # one event per segment, re-recorded step after step
                 if ev is None:
@@ -291,7 +296,8 @@ class FlatAdam:
 
     def launch_key(self):
         """What of the optimiser's settings selects LAUNCHES (not values in device memory): part of a launch plan's key."""
-        return (self.algo(), self.needs_norm(), self.decay_blocks is not None)
+        key = (self.algo(), self.needs_norm(), self.decay_blocks is not None)
+        return key if self.ema is None else key + (self.ema.launch_key(),)
 
     @property
     def early_step(self):
@@ -319,7 +325,8 @@ class FlatAdam:
     def state_tensors(self):
         """Every device tensor of the optimiser a step changes in place (a launch plan's verification compares and restores
         them): parameters, state buffers, the device step number, the norm / skip statistics."""
-        return [t for t in (self.flat_param, self.exp_avg, self.exp_avg_sq, self.step_dev, self.stats_dev) if t is not None]
+        own = [t for t in (self.flat_param, self.exp_avg, self.exp_avg_sq, self.step_dev, self.stats_dev) if t is not None]
+        return own if self.ema is None else own + self.ema.state_tensors()     # (the average, the teacher's buffers, start_dev)
 
     def _grad_norm_launches(self):
         ops.grad_norm(self.flat_grad, self.hyper_dev, self.step_dev, self.stats_dev, self._norm_partials)
@@ -339,6 +346,12 @@ class FlatAdam:
         if self.stats_dev is None:
             raise ops.WsdlError("skipped_steps: the optimiser is not on the device")
         return self.stats_dev[3]
+
+    def _launch_ema(self, lo, hi, last):
+        """The attached EMA's launches behind the step launch on [lo, hi) (``last``: no step launch follows in this step)."""
+        self.ema.launch(lo, hi)
+        if last:
+            self.ema.launch_buffers()
 
     def _launch(self, lo, hi):
         """The step launch on [lo, hi) of the flat buffers (the whole buffer, or one segment: ``lo`` on a parameter boundary)."""
@@ -364,6 +377,8 @@ class FlatAdam:
         replay, so the captured Adam node reads current values from ``hyper_dev``; a change that turns up while a capture is
         running is an error, not something to skip silently."""
         cur = self._hyper_values()
+        if self.ema is not None:
+            self.ema.sync_hyper()
         if self.hyper_dev is not None and cur != self._hyper_host:
             if self.hyper_dev.is_cuda and torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("FlatAdam.sync_hyper: a value of hyper_dev (lr, betas, eps, grad_scale, weight_decay, momentum, "
@@ -481,6 +496,8 @@ class FlatAdam:
                 # skip decision stay on the device, the step launch reads them
                 self._grad_norm_launches()
             self._launch(0, self.numel)
+            if self.ema is not None:
+                self._launch_ema(0, self.numel, last=True)
         else:
             raise ops.WsdlError("FlatAdam.step: parameters are not on the device; there is no CPU fallback")
         self._dirty = False                     # (joined above)

@@ -273,7 +273,9 @@ class PlannedTrainStep:
         host1 = (opt.step_count, [b._pending_steps for b in self._bns])
 
         probe_img = self.s_images * 0.75 + 0.1
-        probe_masks = 1 - torch.clamp(self.s_masks, max=1)
+        # (negative labels are ignore values - augmentation padding, a teacher's "ignore" corrections - and stay: flipped they
+        # would be labels no class has, the probe's loss NaN and the comparison below void)
+        probe_masks = torch.where(self.s_masks < 0, self.s_masks, 1 - torch.clamp(self.s_masks, max=1))
         red = getattr(opt, "_wsdl_reducer", None)
         if red is not None:
             red._local_only = True          # data parallel: the two verification steps exchange nothing (dp.GradBucketReducer)
