@@ -487,27 +487,28 @@ int wsdl_augment_batch(const void* src, int src_is_u8, const float* lut, const u
 
 /* ---- losses --------------------------------------------------------------------------------- */
 size_t wsdl_reduce_workspace(void);
-/* lovasz_softmax(probas, labels, classes, per_image=False, ignore) - the optional loss of train_segmentation_model
- * (TraditionalModel/SegmentationModel.py:103-105; LossFunctions/Lovasz-Softmax_Loss.py: lovasz_grad :11-23,
+/* ---- LossFunctions/Lovasz-Softmax_Loss.py (csrc/lovasz_seg.hip) ----
+ * One segmented pipeline for the hinge and for every form of Lovasz-softmax.  A segment is an image (per_image) or the
+ * batch, times a class: ONE device-wide stable radix sort (rocPRIM) of the order-preserving bits of the error - 32-bit keys
+ * for one segment, 64-bit keys with the segment id above them otherwise -, ONE scan of the packed counts, one pass with the
+ * Jaccard differences in fp32, the reference's arithmetic (a class list: one sort of all its entries; 'present' / 'all':
+ * class after class).  Bitwise reproducible; ties are ranked by pixel index.  Refused on the host, before anything is
+ * launched: 2^30 pixels or 2^32 sorted elements or more in all, a null pointer and, for the hinge and the class list, a
+ * segment of 2^24 pixels or more.  ignore_label: pixels with that label take no part (pass a value no label has, e.g. -1,
+ * for None).
+ *
+ * lovasz_softmax(probas, labels, classes='present' | 'all', per_image, ignore) - the optional loss of
+ * train_segmentation_model (TraditionalModel/SegmentationModel.py:103-105; lovasz_grad :11-23, lovasz_softmax :146-161,
  * lovasz_softmax_flat :164-192, flatten_probas :195-211).  probas (B,C,H,W) class probabilities, labels int64 (B,H,W).
  * *loss = mean over the classes that occur (classes_all = 0, 'present') or over all C (classes_all = 1, 'all') of
- * <errors sorted descending, Jaccard-gradient of the sorted foreground>; dprobas (optional, (B,C,H,W)) = d loss / d probas
- * (the Jaccard gradient is a constant of the sort order, as in the reference).  ignore_label: pixels with that label take
- * no part (pass a value no label has, e.g. -1, for None).  One stable radix sort (rocPRIM) + one scan + one pass per class;
- * bitwise reproducible; ties in the errors are ranked by pixel index. */
-size_t wsdl_lovasz_softmax_workspace(int B, int C, int H, int W);
+ * <errors sorted descending, Jaccard-gradient of the sorted foreground>, of the batch or, per_image, its mean over the
+ * images, each with its own classes (an image without a valid pixel is a zero term that counts); dprobas (optional,
+ * (B,C,H,W)) = d loss / d probas (the Jaccard gradient is a constant of the sort order, as in the reference). */
+size_t wsdl_lovasz_softmax_workspace(int B, int C, int H, int W, int per_image);
 int wsdl_lovasz_softmax_fwd_bwd(const float* probas, const int64_t* labels, float* loss, float* dprobas, int B, int C,
-                                int H, int W, int classes_all, long long ignore_label, void* ws, size_t ws_bytes,
-                                wsdl_stream_t stream);
-
-/* ---- the rest of LossFunctions/Lovasz-Softmax_Loss.py (csrc/lovasz_seg.hip) ----
- * One segmented pipeline for the hinge and for Lovasz-softmax over a class list: ONE device-wide stable radix sort
- * (rocPRIM) of 64-bit keys (segment id above the order-preserving bits of the error), ONE scan of the packed counts, one
- * pass with the Jaccard differences in the fp32 arithmetic of wsdl_lovasz_softmax_fwd_bwd.  Bitwise reproducible; ties
- * are ranked by pixel index.  Refused on the host: a segment (image, or batch) of 2^24 pixels or more, 2^30 pixels or
- * 2^32 sorted elements or more in all, a null pointer.
- *
- * lovasz_hinge(logits, labels, per_image=True, ignore=None) - LossFunctions/Lovasz-Softmax_Loss.py:71-119 (lovasz_hinge
+                                int H, int W, int classes_all, int per_image, long long ignore_label, void* ws,
+                                size_t ws_bytes, wsdl_stream_t stream);
+/* lovasz_hinge(logits, labels, per_image=True, ignore=None) - LossFunctions/Lovasz-Softmax_Loss.py:71-119 (lovasz_hinge
  * :71-84, lovasz_hinge_flat :87-104, flatten_binary_scores :107-119; lovasz_grad :11-23).  logits (B,H,W) fp32
  * (channels = 1) or (B,2,H,W) (channels = 2: the binary logit is plane 1 - plane 0), labels int64 (B,H,W) in {0, 1,
  * ignore_label}.  e = 1 - logit * (2 label - 1); *loss = mean over the segments (per_image: the images; else the one

@@ -1,7 +1,7 @@
 """fp32 torch-CPU oracle for the multi-class Lovasz-softmax with a FIXED tie order: oracle/losses.py::lovasz_softmax restated,
 the same operations in the same order, with one difference - the sort is ``torch.sort(..., descending=True, stable=True)``,
 applied after the void pixels have been removed.  Equal errors then stay in pixel order, which is the order the kernels
-document (csrc/lovasz.hip, csrc/lovasz_seg.hip: a stable radix sort over the pixel index), so the WHOLE gradient is
+document (csrc/lovasz_seg.hip: a stable radix sort over the pixel index), so the WHOLE gradient is
 comparable, the pixels inside a tie included.  The loss does not depend on the order inside a tie; the gradient does.
 
 The Jaccard terms stay in float32 on purpose: tests/lovasz_binary_oracle.py explains why a float64 restatement is the wrong

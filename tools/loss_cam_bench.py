@@ -48,14 +48,13 @@ def main():
         pl = torch.softmax(preds, 1).requires_grad_()
         us = timeit(lambda: ops.lovasz_softmax(pl, lab))
         print(f"{'lovasz-softmax fwd+bwd ' + name:44s} {us:9.1f} {24 * px / us / 1e3:9.1f}  24 B/px (8 probas + 8 int64 label + 8 grad; "
-              "2 sorts of (key, index) pairs + 2 scans in between)")
+              "C = 2 sorts of (32-bit key, index) pairs, a scan after each)")
         us = timeit(lambda: ops.lovasz_softmax(pl, lab, per_image=True))
-        print(f"{'lovasz-softmax per image (loop) ' + name:44s} {us:9.1f} {24 * px / us / 1e3:9.1f}  24 B/px ({2 * B} sorts of one image each)")
-        # the segmented pipeline (csrc/lovasz_seg.hip): one device-wide sort with the images / list entries as segments
+        print(f"{'lovasz-softmax per image ' + name:44s} {us:9.1f} {24 * px / us / 1e3:9.1f}  24 B/px (C = 2 sorts of {B} segments)")
         hz = preds[:, 1].contiguous().requires_grad_()
         us = timeit(lambda: ops.lovasz_hinge(hz, lab, per_image=False))
         print(f"{'lovasz-hinge whole batch fwd+bwd ' + name:44s} {us:9.1f} {16 * px / us / 1e3:9.1f}  16 B/px (4 logit + 8 int64 label + 4 grad; "
-              "1 sort of (64-bit key, index) pairs + 1 scan)")
+              "1 sort of (32-bit key, index) pairs + 1 scan)")
         us = timeit(lambda: ops.lovasz_hinge(hz, lab, per_image=True))
         print(f"{'lovasz-hinge per image fwd+bwd ' + name:44s} {us:9.1f} {16 * px / us / 1e3:9.1f}  16 B/px ({B} segments in 1 sort)")
         us = timeit(lambda: ops.lovasz_hinge(lg, lab, per_image=True))

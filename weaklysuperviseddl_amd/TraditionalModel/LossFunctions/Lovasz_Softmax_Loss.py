@@ -6,8 +6,8 @@ All fourteen names of that file with their positional signatures and defaults:
 
 - losses: ``lovasz_hinge`` / ``lovasz_hinge_flat`` (binary hinge), ``lovasz_softmax`` / ``lovasz_softmax_flat`` (``classes``
   'present', 'all' or a list of classes), ``binary_xloss`` / ``StableBCELoss``, ``xloss``.  Sorting, the Jaccard gradient
-  and the dot products run on the device (csrc/lovasz.hip for 'present' / 'all', csrc/lovasz_seg.hip for the hinge and for
-  class lists: the images and list entries are segments of ONE sort); ties between equal errors are ranked by pixel
+  and the dot products run on the device (csrc/lovasz_seg.hip: the images and list entries are segments of ONE sort,
+  'present' / 'all' sort class after class); ties between equal errors are ranked by pixel
   index, the loss does not depend on that order.  The flat variants are the same kernels at B = 1, H = 1, W = P.
 - metrics: ``iou_binary`` / ``iou`` - the counts come from the device in one copy, the divisions, the mean and the x 100
   are done on the host with Python floats as in the reference, so the results can be exactly equal.

@@ -73,8 +73,8 @@ SIGNATURES = {
     "wsdl_softmax_ce_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _ll, _vp, _sz, _vp]),
     "wsdl_softmax_ce_ex_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _ll, _vp, _vp, _f, _i, _vp, _sz, _vp]),
     "wsdl_scale_by_pixel": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "wsdl_lovasz_softmax_workspace": (_sz, [_i, _i, _i, _i]),
-    "wsdl_lovasz_softmax_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _ll, _vp, _sz, _vp]),
+    "wsdl_lovasz_softmax_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "wsdl_lovasz_softmax_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _ll, _vp, _sz, _vp]),
     "wsdl_lovasz_hinge_workspace": (_sz, [_i, _i, _i, _i]),
     "wsdl_lovasz_hinge_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _ll, _vp, _sz, _vp]),
     "wsdl_lovasz_softmax_classes_workspace": (_sz, [_i, _i, _i, _i, _i, _i]),

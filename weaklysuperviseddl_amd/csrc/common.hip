@@ -109,7 +109,7 @@ const char* wsdl_last_launches(void) {      // this thread's launches since the 
 }
 
 const char* wsdl_last_error(void) { return wsdl::g_err; }
-int wsdl_version(void) { return 200; }
+int wsdl_version(void) { return 201; }
 const char* wsdl_target_arch(void) { return "gfx950"; }
 
 const char* wsdl_prof_class_name(int cls) {

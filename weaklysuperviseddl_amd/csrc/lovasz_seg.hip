@@ -1,25 +1,34 @@
-// lovasz_seg.hip - the rest of the reference's Lovasz file (TraditionalModel/LossFunctions/Lovasz-Softmax_Loss.py):
-// the binary Lovasz hinge (lovasz_hinge :71-104, flatten_binary_scores :107-119), Lovasz-softmax over an explicit class
-// list, whole-batch or per image (lovasz_softmax :146-192), the void-aware IoU counts (iou_binary / iou :26-65) and the
-// stable binary cross entropy (StableBCELoss / binary_xloss :122-140).
+// lovasz_seg.hip - the reference's Lovasz file (TraditionalModel/LossFunctions/Lovasz-Softmax_Loss.py): Lovasz-softmax over
+// the classes that occur ('present'), all of them or an explicit list, whole-batch or per image (lovasz_grad :11-23,
+// lovasz_softmax :146-192, flatten_probas :195-211; the optional loss of train_segmentation_model, SegmentationModel.py:103-105),
+// the binary Lovasz hinge (lovasz_hinge :71-104, flatten_binary_scores :107-119), the void-aware IoU counts (iou_binary / iou
+// :26-65) and the stable binary cross entropy (StableBCELoss / binary_xloss :122-140).
 //
-// Both losses are ONE segmented pipeline.  A segment is what the reference sorts on its own: an image or the whole batch
-// (hinge), times a class-list entry (softmax).  All S segments have the same length L (the pixels of an image / of the
+// All Lovasz losses are ONE segmented pipeline.  A segment is what the reference sorts on its own: an image or the whole batch
+// (hinge), times a class (softmax).  All S segments of a sort have the same length L (the pixels of an image / of the
 // batch), element n = s * L + j.  Per segment: errors sorted descending, G = #foreground, running counts F_k / N_k,
-// J_k = 1 - (G - F_k) / (G + N_k) in fp32 exactly as jaccard() of lovasz.hip (the reference's own arithmetic - a float64
-// restatement lies up to 3.7e-2 of max|grad| away from it at 4 x 512 x 512, J sits a few ulps under 1), g_k = J_k - J_{k-1},
+// J_k = 1 - (G - F_k) / (G + N_k) in fp32 (the reference's own arithmetic - a float64 restatement lies up to 3.7e-2 of
+// max|grad| away from it at 4 x 512 x 512, J sits a few ulps under 1), g_k = J_k - J_{k-1} (constants of the sort order),
 //   hinge:    e = 1 - logit * sign,   loss_s = sum_k relu(e_(k)) g_k,   d loss_s / d logit = -sign g_k  where e > 0, else 0
 //   softmax:  e = |fg - p_c|,         loss_s = sum_k e_(k) g_k,         d loss_s / d p_c   = -sgn(fg - p_c) g_k
-// and the result is the mean over the segments (a segment without a valid pixel is a zero term that still counts).
+// and the result is the weighted sum of the segments: the mean over them (hinge, class list: a segment without a valid
+// pixel is a zero term that still counts), or per image / batch the mean over the classes that take part ('present', 'all').
 //
-// On the device: ONE device-wide stable radix sort (rocPRIM: a sort is library work, see lovasz.hip) of
-//   64-bit key = (S - 1 - s) << 32 | order-preserving bits of e  (the hinge error is signed: sign-flip transform),
-//   value      = pixel index + foreground / valid flags,
-// descending over bits [0, 32 + bits(S)), so segment 0 comes first and every segment stays in place; ONE inclusive scan
-// of the packed (F, N) counts read straight from the sorted values; one pass that subtracts the count at the segment's
-// start, forms the Jaccard differences, the dot product (double, fixed order: bitwise reproducible) and scatters the
-// gradient.  rocPRIM's segmented sort would put each 65 536-pixel image on one workgroup; the device-wide sort keeps the
-// whole chip busy at any batch size.  Ignored pixels get the smallest key of their segment and count for neither F nor N.
+// On the device: ONE device-wide stable radix sort (rocPRIM: a sort is library work, like a plain GEMM) of
+//   key   = order-preserving bits of e (the hinge error is signed: sign-flip transform), with (S - 1 - s) << 32 above them
+//           when there is more than one segment - one segment sorts 32-bit keys, 8 instead of 12 bytes per element and pass,
+//   value = pixel index + foreground / valid flags,
+// descending, so segment 0 comes first and every segment stays in place; ONE inclusive scan of the packed (F, N) counts
+// read straight from the sorted values; one pass that subtracts the count at the segment's start, forms the Jaccard
+// differences, the dot product (double, fixed order: bitwise reproducible) and scatters the gradient.  rocPRIM's segmented
+// sort would put each 65 536-pixel image on one workgroup; the device-wide sort keeps the whole chip busy at any batch size.
+// A class list is one sort of all its entries; 'present' / 'all' sort class after class (the workspace stays ~32 bytes per
+// pixel whatever C is, and C is not bound by the list's 1024 entries).
+// Ignored pixels (label == ignore) get key bits 0, which no valid pixel has (order_bits() sets the sign bit of e >= 0):
+// they sort strictly behind EVERY valid pixel of their segment, one with e == 0 included, and count for neither F nor N -
+// the same as removing them (flatten_probas).  So the sorted prefix in front of a valid pixel is empty or holds a valid
+// pixel, and no J is formed from G + N == 0 (1 - 0 / 0 = NaN).  Ties in e are ordered by pixel index (the reference:
+// whatever torch.sort does); the loss does not depend on the order inside a tie.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -37,6 +46,8 @@ constexpr int kThreadsS = 256;
 constexpr unsigned kFg = 0x80000000u, kValid = 0x40000000u, kIdx = 0x3fffffffu;
 constexpr int kMaxParts = 2048;       // partial sums of one call (all segments together), when S allows it
 constexpr int kMaxClasses = 1024;     // entries of a class list
+constexpr long long kExactCumsum = 1ll << 24;      // segment cap of the hinge and the class list
+constexpr long long kAllPixels = 1ll << 30;        // segment cap of 'present' / 'all': none below the pixel limit
 
 typedef unsigned long long u64;
 
@@ -55,23 +66,39 @@ struct SegGeom {
     int S, K, HW, C;    // segments, class-list entries per image / batch (hinge: 1), pixels per image, channels
 };
 
+// Key = unsigned: the call has ONE segment, the whole batch; Key = u64: the segment id rides above the error bits.
+// f(Key()) for the key type of S segments
+template <typename F>
+auto by_key(int S, F f) {
+    return S == 1 ? f(0u) : f(0ull);
+}
+
 // element n -> segment s, pixel i of the batch
+template <typename Key>
 __device__ __forceinline__ void seg_locate(const SegGeom& g, long long n, int& s, long long& i) {
+    if (sizeof(Key) == 4) {
+        s = 0;
+        i = n;
+        return;
+    }
     s = (int)(n / g.L);
     i = (long long)(s / g.K) * g.L + (n - (long long)s * g.L);
 }
 
-__device__ __forceinline__ u64 seg_key(const SegGeom& g, int s, bool valid, float e) {
-    return ((u64)(unsigned)(g.S - 1 - s) << 32) | (valid ? order_bits(e) : 0u);
+template <typename Key>
+__device__ __forceinline__ Key seg_key(const SegGeom& g, int s, bool valid, float e) {
+    const unsigned bits = valid ? order_bits(e) : 0u;
+    return sizeof(Key) == 4 ? (Key)bits : (Key)(((u64)(unsigned)(g.S - 1 - s) << 32) | bits);
 }
 
 // hinge keys.  logits: (B,HW) for two_ch = 0, (B,2,HW) for two_ch = 1 (binary logit = plane 1 - plane 0)
+template <typename Key>
 __global__ void seg_hinge_keys_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, SegGeom g,
-                                      int two_ch, long long ignore, u64* __restrict__ keys, unsigned* __restrict__ vals) {
+                                      int two_ch, long long ignore, Key* __restrict__ keys, unsigned* __restrict__ vals) {
     for (long long n = blockIdx.x * (long long)blockDim.x + threadIdx.x; n < g.total; n += (long long)gridDim.x * blockDim.x) {
         int s;
         long long i;
-        seg_locate(g, n, s, i);
+        seg_locate<Key>(g, n, s, i);
         const long long l = labels[i];
         float x;
         if (two_ch) {
@@ -83,20 +110,21 @@ __global__ void seg_hinge_keys_kernel(const float* __restrict__ logits, const in
         const bool valid = l != ignore;
         const bool fg = valid && l == 1;
         const float e = 1.f - x * (fg ? 1.f : -1.f);
-        keys[n] = seg_key(g, s, valid, e);
+        keys[n] = seg_key<Key>(g, s, valid, e);
         vals[n] = (unsigned)i | (fg ? kFg : 0u) | (valid ? kValid : 0u);
     }
 }
 
 // softmax keys for the class list cls[0..K): entry kk of a segment compares channel cls[kk] (channel 0 when C == 1, the
 // sigmoid form) with labels == cls[kk]
+template <typename Key>
 __global__ void seg_class_keys_kernel(const float* __restrict__ probas, const int64_t* __restrict__ labels, SegGeom g,
-                                      const int* __restrict__ cls, long long ignore, u64* __restrict__ keys,
+                                      const int* __restrict__ cls, long long ignore, Key* __restrict__ keys,
                                       unsigned* __restrict__ vals) {
     for (long long n = blockIdx.x * (long long)blockDim.x + threadIdx.x; n < g.total; n += (long long)gridDim.x * blockDim.x) {
         int s;
         long long i;
-        seg_locate(g, n, s, i);
+        seg_locate<Key>(g, n, s, i);
         const int c = cls[s % g.K];
         const int ch = g.C == 1 ? 0 : c;
         const long long l = labels[i];
@@ -105,8 +133,64 @@ __global__ void seg_class_keys_kernel(const float* __restrict__ probas, const in
         const bool valid = l != ignore;
         const bool fg = valid && l == c;
         const float e = fabsf((fg ? 1.f : 0.f) - p);
-        keys[n] = seg_key(g, s, valid, e);
+        keys[n] = seg_key<Key>(g, s, valid, e);
         vals[n] = (unsigned)i | (fg ? kFg : 0u) | (valid ? kValid : 0u);
+    }
+}
+
+// ---- 'present' / 'all': which classes take part in which group (image, or the batch), and with what weight -------------
+// counts[g * C + c] = pixels of class c in group g (labels outside [0, C) and the ignored label are in no class).  One
+// workgroup per (group, part), one global atomic per class and workgroup: per-thread counters for up to 8 classes (a
+// pixel-wise atomic onto two addresses took 16 ms for two million pixels), a workgroup histogram in LDS beyond that.
+__global__ void seg_hist_kernel(const int64_t* __restrict__ labels, long long L, int bpg, int C, long long ignore,
+                                int* __restrict__ counts) {
+    __shared__ int h[1024];
+    const int grp = blockIdx.x / bpg, part = blockIdx.x - grp * bpg;
+    labels += (long long)grp * L;
+    counts += (long long)grp * C;
+    const bool small = C <= 8;
+    int mine[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (!small)
+        for (int c = threadIdx.x; c < C && c < 1024; c += blockDim.x) h[c] = 0;
+    __syncthreads();
+    for (long long i = part * (long long)blockDim.x + threadIdx.x; i < L; i += (long long)bpg * blockDim.x) {
+        const long long l = labels[i];
+        if (l < 0 || l >= C || l == ignore) continue;
+        if (small) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) mine[c] += (l == c) ? 1 : 0;
+        } else if (l < 1024) {
+            atomicAdd(&h[(int)l], 1);
+        } else {
+            atomicAdd(&counts[(int)l], 1);
+        }
+    }
+    if (small) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            int v = mine[c];
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+            if ((threadIdx.x & 63) == 0 && c < C && v) atomicAdd(&counts[c], v);
+        }
+    } else {
+        __syncthreads();
+        for (int c = threadIdx.x; c < C && c < 1024; c += blockDim.x)
+            if (h[c]) atomicAdd(&counts[c], h[c]);
+    }
+}
+
+// norm[c * groups + g] = the weight of class c's segment g: 1 / (classes averaged over in group g * groups) if c takes part
+// there, else 0 (a group without a class is a zero term that still counts); ids[c] = c, pass c's one-entry class list
+__global__ void seg_norm_kernel(const int* __restrict__ counts, int groups, int C, int all, float* __restrict__ norm,
+                                int* __restrict__ ids) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    for (int c = t; c < C; c += stride) ids[c] = c;
+    for (int g = t; g < groups; g += stride) {
+        const int* row = counts + (long long)g * C;
+        int n = 0;
+        for (int c = 0; c < C; ++c) n += (all || row[c] > 0) ? 1 : 0;
+        const float inv = n > 0 ? 1.f / (float)((long long)n * groups) : 0.f;
+        for (int c = 0; c < C; ++c) norm[(long long)c * groups + g] = (all || row[c] > 0) ? inv : 0.f;
     }
 }
 
@@ -115,7 +199,6 @@ struct PackFlags {
     __host__ __device__ u64 operator()(unsigned v) const { return (v & kFg) ? 1ull : ((v & kValid) ? (1ull << 32) : 0ull); }
 };
 
-// the fp32 formula and operation order of jaccard() in lovasz.hip
 __device__ __forceinline__ float seg_jaccard(u64 cum, float G) {
     const float F = (float)(unsigned)(cum & 0xffffffffull), N = (float)(unsigned)(cum >> 32);
     return 1.f - (G - F) / (G + N);
@@ -123,12 +206,13 @@ __device__ __forceinline__ float seg_jaccard(u64 cum, float G) {
 
 // One workgroup per (segment, part): a contiguous run of the segment's sorted positions.  parts[s * pps + part] = its
 // share of the segment's dot product.  cum runs over ALL segments: the count at the segment's start is subtracted (both
-// halves of the packed word only grow, so the packed difference never borrows).  flag: hinge - the logits have two
-// planes; softmax - a class is listed more than once.
-template <bool kHinge>
-__global__ void seg_apply_kernel(const u64* __restrict__ keys, const unsigned* __restrict__ vals, const u64* __restrict__ cum,
-                                 SegGeom g, int pps, float w, int flag, const int* __restrict__ cls,
-                                 const float* __restrict__ probas, float* __restrict__ grad, double* __restrict__ parts) {
+// halves of the packed word only grow, so the packed difference never borrows).  The segment's weight is wseg[s], or w for
+// all of them without wseg.  flag: hinge - the logits have two planes; softmax - a class is listed more than once.
+template <bool kHinge, typename Key>
+__global__ void seg_apply_kernel(const Key* __restrict__ keys, const unsigned* __restrict__ vals, const u64* __restrict__ cum,
+                                 SegGeom g, int pps, float w, const float* __restrict__ wseg, int flag,
+                                 const int* __restrict__ cls, const float* __restrict__ probas, float* __restrict__ grad,
+                                 double* __restrict__ parts) {
     __shared__ double sm[16];
     const int s = blockIdx.x / pps, part = blockIdx.x - s * pps;
     const long long first = (long long)s * g.L;
@@ -136,6 +220,7 @@ __global__ void seg_apply_kernel(const u64* __restrict__ keys, const unsigned* _
     const float G = (float)(unsigned)((cum[first + g.L - 1] - base) & 0xffffffffull);
     const long long per = (g.L + pps - 1) / pps;
     const long long lo = part * per, hi = lo + per < g.L ? lo + per : g.L;
+    if (wseg) w = wseg[s];
     int ch = 0;
     if (!kHinge) ch = g.C == 1 ? 0 : cls[s % g.K];
     double acc = 0.0;
@@ -187,33 +272,40 @@ __global__ void seg_apply_kernel(const u64* __restrict__ keys, const unsigned* _
     }
 }
 
-// loss = w * sum of all parts, added in one fixed order (strided per thread, then across the workgroup)
-__global__ void seg_finalize_kernel(const double* __restrict__ parts, long long nparts, float w, float* __restrict__ loss) {
+// loss (add: += - the classes of 'present' / 'all' follow one another on the stream) = w * sum of all parts, or the sum of
+// the parts times their segment's weight, added in one fixed order (strided per thread, then across the workgroup)
+__global__ void seg_finalize_kernel(const double* __restrict__ parts, int nparts, int pps, float w,
+                                    const float* __restrict__ wseg, int add, float* __restrict__ loss) {
     __shared__ double sm[16];
     double mine = 0.0;
-    for (long long p = threadIdx.x; p < nparts; p += blockDim.x) mine += parts[p];
+    if (wseg)
+        for (int p = threadIdx.x; p < nparts; p += blockDim.x) mine += parts[p] * (double)wseg[p / pps];
+    else
+        for (int p = threadIdx.x; p < nparts; p += blockDim.x) mine += parts[p];
     mine = block_sum_d(mine, sm);
-    if (threadIdx.x == 0) *loss = (float)(mine * (double)w);
+    if (threadIdx.x == 0) *loss = (add ? *loss : 0.f) + (float)(wseg ? mine : mine * (double)w);
 }
 
 struct SegLayout {
-    size_t keys_in, keys_out, vals_in, vals_out, cum, parts, cls, temp, temp_bytes, total;
+    size_t keys_in, keys_out, vals_in, vals_out, cum, parts, cls, counts, norm, temp, temp_bytes, total;
     int pps, end_bit;
 };
 
 typedef rocprim::transform_iterator<const unsigned*, PackFlags, u64> FlagIter;
 
-int seg_layout(long long total, long long L, int S, int K, SegLayout* o) {
+// n_cls class-list entries; n_norm (group, class) counts and weights ('present' / 'all')
+template <typename Key>
+int seg_layout(const SegGeom& g, int n_cls, size_t n_norm, SegLayout* o) {
     int sbits = 0;
-    while (sbits < 31 && (1ll << sbits) < S) ++sbits;
+    while (sbits < 31 && (1ll << sbits) < g.S) ++sbits;
     o->end_bit = 32 + sbits;
-    o->pps = (int)std::max<long long>(1, std::min<long long>((L + 1023) / 1024, kMaxParts / S));
+    o->pps = (int)std::max<long long>(1, std::min<long long>((g.L + 1023) / 1024, kMaxParts / g.S));
     size_t sort_bytes = 0, scan_bytes = 0;
-    if (rocprim::radix_sort_pairs_desc(nullptr, sort_bytes, (u64*)nullptr, (u64*)nullptr, (unsigned*)nullptr,
-                                       (unsigned*)nullptr, (size_t)total, 0, (unsigned)o->end_bit, nullptr) != hipSuccess)
+    if (rocprim::radix_sort_pairs_desc(nullptr, sort_bytes, (Key*)nullptr, (Key*)nullptr, (unsigned*)nullptr,
+                                       (unsigned*)nullptr, (size_t)g.total, 0, (unsigned)o->end_bit, nullptr) != hipSuccess)
         return -1;
     if (rocprim::inclusive_scan(nullptr, scan_bytes, FlagIter((const unsigned*)nullptr, PackFlags()), (u64*)nullptr,
-                                (size_t)total, rocprim::plus<u64>(), nullptr) != hipSuccess)
+                                (size_t)g.total, rocprim::plus<u64>(), nullptr) != hipSuccess)
         return -1;
     size_t at = 0;
     auto take = [&](size_t bytes) {
@@ -221,28 +313,30 @@ int seg_layout(long long total, long long L, int S, int K, SegLayout* o) {
         at += wsdl::align_up(bytes, 256);
         return here;
     };
-    o->keys_in = take((size_t)total * 8);
-    o->keys_out = take((size_t)total * 8);
-    o->vals_in = take((size_t)total * 4);
-    o->vals_out = take((size_t)total * 4);
-    o->cum = take((size_t)total * 8);
-    o->parts = take((size_t)S * o->pps * sizeof(double));
-    o->cls = take((size_t)std::max(K, 1) * sizeof(int));
+    o->keys_in = take((size_t)g.total * sizeof(Key));
+    o->keys_out = take((size_t)g.total * sizeof(Key));
+    o->vals_in = take((size_t)g.total * 4);
+    o->vals_out = take((size_t)g.total * 4);
+    o->cum = take((size_t)g.total * 8);
+    o->parts = take((size_t)g.S * o->pps * sizeof(double));
+    o->cls = take((size_t)n_cls * sizeof(int));
+    o->counts = take(n_norm * sizeof(int));
+    o->norm = take(n_norm * sizeof(float));
     o->temp_bytes = std::max(sort_bytes, scan_bytes);
     o->temp = take(o->temp_bytes);
     o->total = at;
     return 0;
 }
 
-// what the kernels cannot do is refused here; 0 = fine
-const char* seg_limits(int B, int H, int W, int K, int per_image, SegGeom* g) {
+// what the kernels cannot do is refused here; 0 = fine.  seg_cap: the length a segment must stay below
+const char* seg_limits(int B, int H, int W, int K, int per_image, long long seg_cap, SegGeom* g) {
     if (B <= 0 || H <= 0 || W <= 0 || K <= 0) return "bad shape";
     const long long HW = (long long)H * W, P = (long long)B * HW;
     if (HW >= (1ll << 31)) return "an image of 2^31 pixels or more";
     if (P >= (1ll << 30)) return "at most 2^30 - 1 pixels (the pixel index shares a word with two flags)";
     const long long L = per_image ? HW : P;
     const long long S = (long long)(per_image ? B : 1) * K;
-    if (L >= (1ll << 24)) return "a segment of 2^24 elements or more (the reference's float cumsum stops being exact there)";
+    if (L >= seg_cap) return "a segment of 2^24 elements or more (the reference's float cumsum stops being exact there)";
     if (S >= (1ll << 31) || S * L >= (1ll << 32)) return "2^32 elements or more in all (the packed running counts are 32 bits each)";
     g->L = L;
     g->total = S * L;
@@ -253,17 +347,27 @@ const char* seg_limits(int B, int H, int W, int K, int per_image, SegGeom* g) {
     return nullptr;
 }
 
+// the workspace's layout, or why it does not do: nothing has been launched yet
+template <typename Key>
+int seg_prepare(const char* who, const SegGeom& g, int n_cls, size_t n_norm, size_t ws_bytes, SegLayout* L) {
+    WSDL_REQUIRE(seg_layout<Key>(g, n_cls, n_norm, L) == 0, "%s: rocPRIM size query failed", who);
+    if (ws_bytes < L->total) {
+        wsdl::set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, L->total);
+        return WSDL_EWORKSPACE;
+    }
+    return WSDL_OK;
+}
+
 // keys are in keys_in / vals_in: sort, scan, apply, finalize
-template <bool kHinge>
-int seg_run(const SegGeom& g, const SegLayout& L, char* base, float w, int flag, const float* probas, float* grad, float* loss,
-            hipStream_t s) {
-    u64* keys_in = reinterpret_cast<u64*>(base + L.keys_in);
-    u64* keys_out = reinterpret_cast<u64*>(base + L.keys_out);
+template <bool kHinge, typename Key>
+int seg_run(const SegGeom& g, const SegLayout& L, char* base, float w, const float* wseg, int flag, const int* cls, int add,
+            const float* probas, float* grad, float* loss, hipStream_t s) {
+    Key* keys_in = reinterpret_cast<Key*>(base + L.keys_in);
+    Key* keys_out = reinterpret_cast<Key*>(base + L.keys_out);
     unsigned* vals_in = reinterpret_cast<unsigned*>(base + L.vals_in);
     unsigned* vals_out = reinterpret_cast<unsigned*>(base + L.vals_out);
     u64* cum = reinterpret_cast<u64*>(base + L.cum);
     double* parts = reinterpret_cast<double*>(base + L.parts);
-    const int* cls = reinterpret_cast<const int*>(base + L.cls);
     void* temp = base + L.temp;
     size_t tb = L.temp_bytes;
     WSDL_HIP_CHECK(rocprim::radix_sort_pairs_desc(temp, tb, keys_in, keys_out, vals_in, vals_out, (size_t)g.total, 0,
@@ -271,11 +375,19 @@ int seg_run(const SegGeom& g, const SegLayout& L, char* base, float w, int flag,
     tb = L.temp_bytes;
     WSDL_HIP_CHECK(rocprim::inclusive_scan(temp, tb, FlagIter(vals_out, PackFlags()), cum, (size_t)g.total,
                                            rocprim::plus<u64>(), s));
-    hipLaunchKernelGGL(seg_apply_kernel<kHinge>, dim3(g.S * L.pps), dim3(kThreadsS), 0, s, keys_out, vals_out, cum, g, L.pps, w,
-                       flag, cls, probas, grad, parts);
-    hipLaunchKernelGGL(seg_finalize_kernel, dim3(1), dim3(kThreadsS), 0, s, (const double*)parts, (long long)g.S * L.pps, w, loss);
+    hipLaunchKernelGGL((seg_apply_kernel<kHinge, Key>), dim3(g.S * L.pps), dim3(kThreadsS), 0, s, (const Key*)keys_out,
+                       (const unsigned*)vals_out, (const u64*)cum, g, L.pps, w, wseg, flag, cls, probas, grad, parts);
+    hipLaunchKernelGGL(seg_finalize_kernel, dim3(1), dim3(kThreadsS), 0, s, (const double*)parts, g.S * L.pps, L.pps,
+                       w, wseg, add, loss);
     WSDL_LAUNCH_CHECK();
     return WSDL_OK;
+}
+
+size_t seg_workspace(const SegGeom& g, int n_cls, size_t n_norm) {
+    return by_key(g.S, [&](auto key) -> size_t {
+        SegLayout L;
+        return seg_layout<decltype(key)>(g, n_cls, n_norm, &L) ? 0 : L.total;
+    });
 }
 
 int key_blocks(long long total) { return (int)std::min<long long>((total + kThreadsS - 1) / kThreadsS, 4096); }
@@ -392,11 +504,56 @@ __global__ void bce_finalize_kernel(const double* __restrict__ part, int blocks,
 
 extern "C" {
 
+size_t wsdl_lovasz_softmax_workspace(int B, int C, int H, int W, int per_image) {
+    SegGeom g;
+    if (C <= 0 || seg_limits(B, H, W, 1, per_image, kAllPixels, &g)) return 0;
+    return seg_workspace(g, C, (size_t)g.S * C);
+}
+
+int wsdl_lovasz_softmax_fwd_bwd(const float* probas, const int64_t* labels, float* loss, float* dprobas, int B, int C,
+                                int H, int W, int classes_all, int per_image, long long ignore_label, void* ws,
+                                size_t ws_bytes, wsdl_stream_t stream) {
+    WSDL_REQUIRE(probas && labels && loss && ws, "lovasz_softmax: null pointer");
+    WSDL_REQUIRE(C > 0, "lovasz_softmax: bad shape");
+    SegGeom g;
+    const char* why = seg_limits(B, H, W, 1, per_image, kAllPixels, &g);
+    WSDL_REQUIRE(!why, "lovasz_softmax: %s", why);
+    g.C = C;
+    return by_key(g.S, [&](auto key) -> int {
+        typedef decltype(key) Key;
+        const size_t n_norm = (size_t)g.S * C;                 // a segment of every sort is a group: an image, or the batch
+        SegLayout L;
+        if (int rc = seg_prepare<Key>("lovasz_softmax", g, C, n_norm, ws_bytes, &L)) return rc;
+        wsdl::plan_poison("wsdl_lovasz_softmax_fwd_bwd sorts and scans through rocPRIM, whose launches a plan does not see");
+        hipStream_t s = wsdl::as_stream(stream);
+        char* base = static_cast<char*>(ws);
+        int* ids = reinterpret_cast<int*>(base + L.cls);
+        int* counts = reinterpret_cast<int*>(base + L.counts);
+        float* norm = reinterpret_cast<float*>(base + L.norm);
+        WSDL_HIP_CHECK(hipMemsetAsync(counts, 0, n_norm * sizeof(int), s));
+        if (dprobas) WSDL_HIP_CHECK(hipMemsetAsync(dprobas, 0, (size_t)g.total * C * sizeof(float), s));
+        const int bpg = (int)std::max<long long>(1, std::min<long long>((g.L + kThreadsS - 1) / kThreadsS, 1024 / g.S));
+        hipLaunchKernelGGL(seg_hist_kernel, dim3(g.S * bpg), dim3(kThreadsS), 0, s, labels, g.L, bpg, C, ignore_label, counts);
+        hipLaunchKernelGGL(seg_norm_kernel, dim3(std::min((std::max(g.S, C) + kThreadsS - 1) / kThreadsS, 1024)), dim3(kThreadsS), 0,
+                           s, (const int*)counts, g.S, C, classes_all, norm, ids);
+        WSDL_LAUNCH_CHECK();
+        // class after class: the one-entry list [c], its segments weighted by norm[c], its loss added to the classes before
+        for (int c = 0; c < C; ++c) {
+            hipLaunchKernelGGL(seg_class_keys_kernel<Key>, dim3(key_blocks(g.total)), dim3(kThreadsS), 0, s, probas, labels, g,
+                               (const int*)(ids + c), ignore_label, reinterpret_cast<Key*>(base + L.keys_in),
+                               reinterpret_cast<unsigned*>(base + L.vals_in));
+            WSDL_LAUNCH_CHECK();
+            if (int rc = seg_run<false, Key>(g, L, base, 0.f, norm + (size_t)c * g.S, 0, ids + c, c > 0, probas, dprobas, loss, s))
+                return rc;
+        }
+        return WSDL_OK;
+    });
+}
+
 size_t wsdl_lovasz_hinge_workspace(int B, int H, int W, int per_image) {
     SegGeom g;
-    SegLayout L;
-    if (seg_limits(B, H, W, 1, per_image, &g) || seg_layout(g.total, g.L, g.S, 1, &L)) return 0;
-    return L.total;
+    if (seg_limits(B, H, W, 1, per_image, kExactCumsum, &g)) return 0;
+    return seg_workspace(g, 0, 0);
 }
 
 int wsdl_lovasz_hinge_fwd_bwd(const float* logits, const int64_t* labels, float* loss, float* dlogits, int B, int channels,
@@ -405,32 +562,28 @@ int wsdl_lovasz_hinge_fwd_bwd(const float* logits, const int64_t* labels, float*
     WSDL_REQUIRE(logits && labels && loss && ws, "lovasz_hinge: null pointer");
     WSDL_REQUIRE(channels == 1 || channels == 2, "lovasz_hinge: logits are (B,H,W) (channels = 1) or (B,2,H,W) (channels = 2)");
     SegGeom g;
-    const char* why = seg_limits(B, H, W, 1, per_image, &g);
+    const char* why = seg_limits(B, H, W, 1, per_image, kExactCumsum, &g);
     WSDL_REQUIRE(!why, "lovasz_hinge: %s", why);
-    SegLayout L;
-    WSDL_REQUIRE(seg_layout(g.total, g.L, g.S, 1, &L) == 0, "lovasz_hinge: rocPRIM size query failed");
-    if (ws_bytes < L.total) {
-        wsdl::set_error("lovasz_hinge: workspace %zu < %zu bytes", ws_bytes, L.total);
-        return WSDL_EWORKSPACE;
-    }
-    hipStream_t s = wsdl::as_stream(stream);
-    char* base = static_cast<char*>(ws);
-    const int two_ch = channels == 2;
-    wsdl::plan_poison("wsdl_lovasz_hinge_fwd_bwd sorts and scans through rocPRIM, whose launches a plan does not see");
-    if (dlogits) WSDL_HIP_CHECK(hipMemsetAsync(dlogits, 0, (size_t)g.total * channels * sizeof(float), s));
-    hipLaunchKernelGGL(seg_hinge_keys_kernel, dim3(key_blocks(g.total)), dim3(kThreadsS), 0, s, logits, labels, g, two_ch,
-                       ignore_label, reinterpret_cast<u64*>(base + L.keys_in), reinterpret_cast<unsigned*>(base + L.vals_in));
-    WSDL_LAUNCH_CHECK();
-    return seg_run<true>(g, L, base, 1.f / (float)g.S, two_ch, nullptr, dlogits, loss, s);
+    return by_key(g.S, [&](auto key) -> int {
+        typedef decltype(key) Key;
+        SegLayout L;
+        if (int rc = seg_prepare<Key>("lovasz_hinge", g, 0, 0, ws_bytes, &L)) return rc;
+        wsdl::plan_poison("wsdl_lovasz_hinge_fwd_bwd sorts and scans through rocPRIM, whose launches a plan does not see");
+        hipStream_t s = wsdl::as_stream(stream);
+        char* base = static_cast<char*>(ws);
+        const int two_ch = channels == 2;
+        if (dlogits) WSDL_HIP_CHECK(hipMemsetAsync(dlogits, 0, (size_t)g.total * channels * sizeof(float), s));
+        hipLaunchKernelGGL(seg_hinge_keys_kernel<Key>, dim3(key_blocks(g.total)), dim3(kThreadsS), 0, s, logits, labels, g, two_ch,
+                           ignore_label, reinterpret_cast<Key*>(base + L.keys_in), reinterpret_cast<unsigned*>(base + L.vals_in));
+        WSDL_LAUNCH_CHECK();
+        return seg_run<true, Key>(g, L, base, 1.f / (float)g.S, nullptr, two_ch, nullptr, 0, nullptr, dlogits, loss, s);
+    });
 }
 
 size_t wsdl_lovasz_softmax_classes_workspace(int B, int C, int H, int W, int n_classes, int per_image) {
     SegGeom g;
-    SegLayout L;
-    if (C <= 0 || n_classes > kMaxClasses || seg_limits(B, H, W, n_classes, per_image, &g) ||
-        seg_layout(g.total, g.L, g.S, n_classes, &L))
-        return 0;
-    return L.total;
+    if (C <= 0 || n_classes > kMaxClasses || seg_limits(B, H, W, n_classes, per_image, kExactCumsum, &g)) return 0;
+    return seg_workspace(g, n_classes, 0);
 }
 
 int wsdl_lovasz_softmax_classes_fwd_bwd(const float* probas, const int64_t* labels, float* loss, float* dprobas, int B, int C,
@@ -443,30 +596,30 @@ int wsdl_lovasz_softmax_classes_fwd_bwd(const float* probas, const int64_t* labe
         WSDL_REQUIRE(C == 1 || (classes[k] >= 0 && classes[k] < C), "lovasz_softmax_classes: class %d is not a channel of %d",
                      classes[k], C);
     SegGeom g;
-    const char* why = seg_limits(B, H, W, n_classes, per_image, &g);
+    const char* why = seg_limits(B, H, W, n_classes, per_image, kExactCumsum, &g);
     WSDL_REQUIRE(!why, "lovasz_softmax_classes: %s", why);
     WSDL_REQUIRE((long long)B * C * H * W < (1ll << 40), "lovasz_softmax_classes: probas too large");
     g.C = C;
-    SegLayout L;
-    WSDL_REQUIRE(seg_layout(g.total, g.L, g.S, n_classes, &L) == 0, "lovasz_softmax_classes: rocPRIM size query failed");
-    if (ws_bytes < L.total) {
-        wsdl::set_error("lovasz_softmax_classes: workspace %zu < %zu bytes", ws_bytes, L.total);
-        return WSDL_EWORKSPACE;
-    }
-    hipStream_t s = wsdl::as_stream(stream);
-    char* base = static_cast<char*>(ws);
-    int* cls = reinterpret_cast<int*>(base + L.cls);
-    wsdl::plan_poison("wsdl_lovasz_softmax_classes_fwd_bwd sorts and scans through rocPRIM, whose launches a plan does not see");
-    // the list is a host array of the caller: a pageable copy returns once the array has been read
-    WSDL_HIP_CHECK(hipMemcpyAsync(cls, classes, (size_t)n_classes * sizeof(int), hipMemcpyHostToDevice, s));
-    if (dprobas) WSDL_HIP_CHECK(hipMemsetAsync(dprobas, 0, (size_t)B * C * H * W * sizeof(float), s));
-    hipLaunchKernelGGL(seg_class_keys_kernel, dim3(key_blocks(g.total)), dim3(kThreadsS), 0, s, probas, labels, g, (const int*)cls,
-                       ignore_label, reinterpret_cast<u64*>(base + L.keys_in), reinterpret_cast<unsigned*>(base + L.vals_in));
-    WSDL_LAUNCH_CHECK();
-    int repeated = 0;
-    for (int k = 1; k < n_classes && !repeated; ++k)
-        for (int j = 0; j < k; ++j) repeated |= classes[j] == classes[k];
-    return seg_run<false>(g, L, base, 1.f / (float)g.S, repeated, probas, dprobas, loss, s);
+    return by_key(g.S, [&](auto key) -> int {
+        typedef decltype(key) Key;
+        SegLayout L;
+        if (int rc = seg_prepare<Key>("lovasz_softmax_classes", g, n_classes, 0, ws_bytes, &L)) return rc;
+        wsdl::plan_poison("wsdl_lovasz_softmax_classes_fwd_bwd sorts and scans through rocPRIM, whose launches a plan does not see");
+        hipStream_t s = wsdl::as_stream(stream);
+        char* base = static_cast<char*>(ws);
+        int* cls = reinterpret_cast<int*>(base + L.cls);
+        // the list is a host array of the caller: a pageable copy returns once the array has been read
+        WSDL_HIP_CHECK(hipMemcpyAsync(cls, classes, (size_t)n_classes * sizeof(int), hipMemcpyHostToDevice, s));
+        if (dprobas) WSDL_HIP_CHECK(hipMemsetAsync(dprobas, 0, (size_t)B * C * H * W * sizeof(float), s));
+        hipLaunchKernelGGL(seg_class_keys_kernel<Key>, dim3(key_blocks(g.total)), dim3(kThreadsS), 0, s, probas, labels, g,
+                           (const int*)cls, ignore_label, reinterpret_cast<Key*>(base + L.keys_in),
+                           reinterpret_cast<unsigned*>(base + L.vals_in));
+        WSDL_LAUNCH_CHECK();
+        int repeated = 0;
+        for (int k = 1; k < n_classes && !repeated; ++k)
+            for (int j = 0; j < k; ++j) repeated |= classes[j] == classes[k];
+        return seg_run<false, Key>(g, L, base, 1.f / (float)g.S, nullptr, repeated, cls, 0, probas, dprobas, loss, s);
+    });
 }
 
 int wsdl_iou_counts(const int64_t* preds, const int64_t* labels, long long* counts, int B, int HW, int C, int per_image,

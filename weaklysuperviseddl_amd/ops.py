@@ -2485,32 +2485,6 @@ def cross_entropy_mined(logits, labels, ignore_index=-100, *, mode, thresh=None,
     return _cross_entropy_ex(logits, labels, ignore_index, weight, label_smoothing, reduction, m, keep_zeros=True)
 
 
-class _LovaszSoftmax(torch.autograd.Function):
-    """lovasz_softmax(probas, labels, classes, per_image=False, ignore) - reference
-    TraditionalModel/LossFunctions/Lovasz-Softmax_Loss.py:146-192; loss and d loss / d probas in one call (a stable
-    radix sort, a scan and one pass per class on the device)."""
-
-    @staticmethod
-    def forward(ctx, probas, labels, classes_all, ignore):
-        probas = _dense(probas, "probas")
-        labels = _req(labels, "labels", torch.int64).contiguous()
-        B, Cc, H, W = probas.shape
-        if tuple(labels.shape) != (B, H, W):
-            raise WsdlError(f"lovasz_softmax: labels {tuple(labels.shape)} do not match probas {tuple(probas.shape)}")
-        loss = torch.empty((), device=probas.device, dtype=torch.float32)
-        dp = torch.empty_like(probas) if probas.requires_grad else None
-        ws = workspace(lib().wsdl_lovasz_softmax_workspace(B, Cc, H, W), probas.device)
-        check(lib().wsdl_lovasz_softmax_fwd_bwd(_p(probas), _p(labels), _p(loss), _p(dp), B, Cc, H, W, int(classes_all),
-                                                int(ignore), _p(ws), ws.numel(), _stream()))
-        ctx.save_for_backward(dp)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        (dp,) = ctx.saved_tensors
-        return dp * g, None, None, None
-
-
 _NO_LABEL = -(1 << 62)         # "ignore=None": a value no label has
 
 
@@ -2518,9 +2492,11 @@ def _ignore(ignore):
     return _NO_LABEL if ignore is None else int(ignore)
 
 
-class _LovaszSoftmaxClasses(torch.autograd.Function):
-    """lovasz_softmax with an explicit class list (reference Lovasz-Softmax_Loss.py:146-211): every (image or batch) x
-    (list entry) is a segment of ONE device-wide sort (csrc/lovasz_seg.hip)."""
+class _LovaszSoftmax(torch.autograd.Function):
+    """lovasz_softmax(probas, labels, classes, per_image, ignore) - reference
+    TraditionalModel/LossFunctions/Lovasz-Softmax_Loss.py:146-211; loss and d loss / d probas in one call.  Every (image
+    or batch) x class is a segment of a device-wide sort (csrc/lovasz_seg.hip): a class list (``classes``) is ONE sort of
+    all its entries; 'present' / 'all' (``classes`` a bool: all) sort class after class."""
 
     @staticmethod
     def forward(ctx, probas, labels, classes, per_image, ignore):
@@ -2529,14 +2505,19 @@ class _LovaszSoftmaxClasses(torch.autograd.Function):
         B, Cc, H, W = probas.shape
         if tuple(labels.shape) != (B, H, W):
             raise WsdlError(f"lovasz_softmax: labels {tuple(labels.shape)} do not match probas {tuple(probas.shape)}")
-        cls = (C.c_int * len(classes))(*classes)
         loss = torch.empty((), device=probas.device, dtype=torch.float32)
         dp = torch.empty_like(probas) if ctx.needs_input_grad[0] else None       # (a copy made dense above requires no grad)
-        ws = workspace(_ws_bytes("wsdl_lovasz_softmax_classes_workspace", B, Cc, H, W, len(classes), int(per_image)),
-                       probas.device)
-        check(lib().wsdl_lovasz_softmax_classes_fwd_bwd(_p(probas), _p(labels), _p(loss), _p(dp), B, Cc, H, W,
-                                                        C.cast(cls, C.c_void_p), len(classes), int(per_image), int(ignore),
-                                                        _p(ws), ws.numel(), _stream()))
+        if isinstance(classes, bool):
+            ws = workspace(_ws_bytes("wsdl_lovasz_softmax_workspace", B, Cc, H, W, int(per_image)), probas.device)
+            check(lib().wsdl_lovasz_softmax_fwd_bwd(_p(probas), _p(labels), _p(loss), _p(dp), B, Cc, H, W, int(classes),
+                                                    int(per_image), int(ignore), _p(ws), ws.numel(), _stream()))
+        else:
+            cls = (C.c_int * len(classes))(*classes)
+            ws = workspace(_ws_bytes("wsdl_lovasz_softmax_classes_workspace", B, Cc, H, W, len(classes), int(per_image)),
+                           probas.device)
+            check(lib().wsdl_lovasz_softmax_classes_fwd_bwd(_p(probas), _p(labels), _p(loss), _p(dp), B, Cc, H, W,
+                                                            C.cast(cls, C.c_void_p), len(classes), int(per_image), int(ignore),
+                                                            _p(ws), ws.numel(), _stream()))
         ctx.save_for_backward(dp)
         return loss
 
@@ -2554,20 +2535,17 @@ def lovasz_softmax(probas, labels, classes="present", per_image=False, ignore=No
     returns an empty tensor there)."""
     if probas.dim() == 3:
         probas = probas.unsqueeze(1)
-    ign = _ignore(ignore)
     if not isinstance(classes, str):
         classes = [int(c) for c in classes]
         if not classes:
             raise WsdlError("lovasz_softmax: an empty class list")
         if probas.shape[1] == 1 and len(classes) > 1:
             raise ValueError("Sigmoid output possible only with 1 class")
-        return _LovaszSoftmaxClasses.apply(probas, labels, classes, bool(per_image), ign)
-    if classes not in ("present", "all"):
+    elif classes in ("present", "all"):
+        classes = classes == "all"
+    else:
         raise WsdlError("lovasz_softmax: classes must be 'present', 'all' or a list of classes")
-    if per_image:
-        vals = [_LovaszSoftmax.apply(probas[b:b + 1], labels[b:b + 1], classes == "all", ign) for b in range(probas.shape[0])]
-        return torch.stack(vals).mean()
-    return _LovaszSoftmax.apply(probas, labels, classes == "all", ign)
+    return _LovaszSoftmax.apply(probas, labels, classes, bool(per_image), _ignore(ignore))
 
 
 class _LovaszHinge(torch.autograd.Function):
