@@ -761,6 +761,76 @@ int wsdl_ema_table(const wsdl_ema_entry* table_dev, int count, const float* hype
 int wsdl_teacher_targets(const float* logits, const long long* labels, int B, int C, int H, int W, const float* tau_dev, int mode,
                          long long ignore_index, long long* out_labels, float* out_conf, long long* counts, wsdl_stream_t stream);
 
+/* ---- view consistency: warps of score / label maps and the consistency loss (csrc/consistency.hip) ----
+ * The reference has no counterpart.  A prediction made on one view of an image is compared with the prediction on another
+ * view: warp one onto the other by the augmentation's affine map, compare two per-pixel class distributions where the warp is
+ * valid and the teacher is confident, differentiate.
+ *
+ * THE COORDINATE RULE is the one of wsdl_augment_batch above, word for word (csrc/warp_coords.h): params is B x 8 float32,
+ * a00 a01 a02 a10 a11 a12 gain bias, mapping output pixel (ox, oy) to the source point xs, ys with u = ox + 0.5f, every
+ * operation float32 and rounded on its own; both fills; bilinear taps x0, x0 + 1, y0, y0 + 1 clamped (replicate), fractions
+ * fx, fy; the nearest tap min(floor(xs), W - 1).  One rule is added: a NON-FINITE xs or ys (after the reflection, which keeps a
+ * non-finite value non-finite) is "not inside" under both fills.  The value rule is top = v00 + fx * (v01 - v00),
+ * bot = v10 + fx * (v11 - v10), val = top + fy * (bot - top), float32, unfused - where a fraction is 0 its lerp is skipped
+ * and the first tap taken as it is, so with fx = fy = 0 the value is v00 bit for bit, +-inf included, whatever the unused taps hold.
+ *
+ * wsdl_warp_scores_fwd: src (B,C,h,w) float32, 1 <= C <= WSDL_CONSISTENCY_MAX_CLASSES -> out (B,C,out_h,out_w):
+ * inside ? (photometric ? gain * val + bias : val) : pad_value; valid (B,out_h,out_w) uint8, may be NULL, receives `inside`.
+ * wsdl_warp_labels: src (B,h,w) int64 -> out (B,out_h,out_w): inside ? src[nearest tap] : pad_label.
+ * Both: one launch, no atomics, no workspace, 64-bit offsets, results independent of B; sides 1..16384.
+ *
+ * wsdl_warp_scores_bwd: the adjoint of wsdl_warp_scores_fwd with respect to src for fill = ignore: dsrc (B,C,h,w) =
+ * sum over the inside output pixels of (weight of the tap (j,i)) * dy, the weights (1 - fx)(1 - fy), fx (1 - fy), (1 - fx) fy,
+ * fx fy formed in double from the forward's float32 fx, fy (taps that the clamp merges add up; times gain with photometric).
+ * A gather - per source pixel the candidates are the output pixels in the bounding box of the inverse image (in double) of
+ * [i - 0.5, i + 1.5] x [j - 0.5, j + 1.5] clipped to the image, widened by 2 pixels plus the forward's float32 rounding
+ * carried through the inverse; each candidate recomputes the forward's taps; the sum runs in double in raster order and is
+ * rounded once.  No atomics: bitwise reproducible.  A row with a non-finite coefficient has no inside pixel and gives zeros at
+ * once; a finite singular row (or one whose inverse overflows) takes the whole output as its box, so the result never depends
+ * on the magnification - only the time does: small boxes for magnifications in [1/4, 4], (h w) x (out_h out_w) tap evaluations
+ * per chunk of 8 channels for the whole-output box (2^36 at 512 x 512 on both sides: a degenerate view, not a training case).
+ * Source pixels
+ * nothing taps receive exact zeros.  fill = reflect is refused: its adjoint is not built.
+ *
+ * wsdl_consistency_fwd_bwd: student (B,C,H,W) logits z; teacher (B,C,ht,wt), logits or probabilities (teacher_is); params
+ * (B,8) the map from the STUDENT's pixel grid to the teacher's - the teacher is sampled at every student pixel by the rule
+ * above (the float32 value wsdl_warp_scores_fwd would write, bit for bit; never materialised) - or NULL: same size, direct
+ * read, no interpolation.  knobs: three floats in device memory, tau lam T.  Per pixel, in double:
+ *   q = softmax(t / T) for logits; q = t / sum t for probabilities (T is not used);  s = softmax(z);  conf = max q
+ *   counted = warp inside and every teacher value t_c and student logit finite (probabilities: and t_c >= 0, sum t > 0)
+ *             and conf >= tau;      w = counted ? pixel_weight (B,H,W; NULL: 1) : 0
+ *   kl:   l = sum_c q_c (log q_c - log s_c)                 dl/dz = s - q
+ *   mse:  l = (1/C) sum_c (s_c - q_c)^2                     dl/dz_k = (2/C) s_k ((s_k - q_k) - sum_c s_c (s_c - q_c))
+ *   hard: target = the first class of largest t, l = -log s_target   dl/dz = s - onehot(target)
+ * loss = lam / N * sum_p w_p l_p, N = B H W (WSDL_CONSISTENCY_ALL) or sum_p w_p (WSDL_CONSISTENCY_COUNTED); dlogits (may be
+ * NULL) receives the gradient of that loss, lam / N included, rounded once; with no counted pixel the loss is 0 and the
+ * gradient exact zeros.  counts (2 int64, may be NULL) = {pixels inside, pixels counted}; weight_out (B,H,W) float32 = w;
+ * target_out (B,H,W) int64 = the hard target at counted pixels, -100 elsewhere (both may be NULL).  A "finite teacher value"
+ * is the interpolated one: a tap that the zero-fraction rule leaves unused may hold anything.
+ * normalize = all: one fused pass and a one-workgroup finalize; normalize = counted with dlogits: a sums pass, the finalize,
+ * a gradient pass.  Double partials per workgroup added in fixed order, no atomics: two calls give the same bits.  No host
+ * read, every parameter by value or in device memory: a launch plan can hold the call.  C = 2 and 3 are held in registers,
+ * any other C re-reads its pixel's values per pass (no per-lane array: no scratch).  ws: wsdl_consistency_workspace() bytes. */
+#define WSDL_CONSISTENCY_MAX_CLASSES 64
+#define WSDL_CONSISTENCY_KL 0
+#define WSDL_CONSISTENCY_MSE 1
+#define WSDL_CONSISTENCY_HARD 2
+#define WSDL_CONSISTENCY_LOGITS 0
+#define WSDL_CONSISTENCY_PROBS 1
+#define WSDL_CONSISTENCY_ALL 0
+#define WSDL_CONSISTENCY_COUNTED 1
+int wsdl_warp_scores_fwd(const float* src, const float* params, int B, int C, int h, int w, int out_h, int out_w, int fill,
+                         float pad_value, int photometric, float* out, uint8_t* valid, wsdl_stream_t stream);
+int wsdl_warp_labels(const int64_t* src, const float* params, int B, int h, int w, int out_h, int out_w, int fill,
+                     long long pad_label, int64_t* out, wsdl_stream_t stream);
+int wsdl_warp_scores_bwd(const float* dy, const float* params, int B, int C, int h, int w, int out_h, int out_w, int fill,
+                         int photometric, float* dsrc, wsdl_stream_t stream);
+size_t wsdl_consistency_workspace(void);
+int wsdl_consistency_fwd_bwd(const float* student, const float* teacher, const float* params, const float* pixel_weight,
+                             const float* knobs, int B, int C, int H, int W, int ht, int wt, int kind, int teacher_is,
+                             int normalize, int fill, float* loss, float* dlogits, long long* counts, float* weight_out,
+                             long long* target_out, void* ws, size_t ws_bytes, wsdl_stream_t stream);
+
 /* ---- pixel mining: selecting pixels by their loss without a host read (csrc/pixel_mining.hip) -
  * wsdl_kth_value: x holds `segments` runs of n_per_segment floats.  The candidates of segment s are the x[s*n + i] that are
  * not NaN and, when `valid` (one byte per element) is given, have valid[s*n + i] != 0; n_valid[s] receives their number n.

@@ -429,6 +429,36 @@ def train_step_mean_teacher(model, ema, optimizer, images, masks, criterion=None
     return train_step(model, optimizer, images, labels, criterion=criterion)
 
 
+def train_step_consistency(model, ema, optimizer, images, masks, rows, criterion=None, *, consistency, photometric=True):
+    """One view-consistency iteration: the EMA teacher (``ema.FlatEMA`` attached to ``optimizer``) predicts on ``images`` as they
+    are, the student trains on an augmented VIEW of them, and ``consistency`` (a ``wnn.ConsistencyLoss``) adds the cost of the
+    student disagreeing with the teacher's prediction warped onto that view; returns the loss tensor of ``train_step``.
+
+    ``rows`` (B,8) float32 on the device: the view's parameter rows, ``Augment.draw(B, hw, hw)`` uploaded once per epoch as the
+    loaders do - the map from the view's pixels to the pixels of ``images``, and so also the map from the student's grid to
+    the teacher's.  Steps: (1) the teacher's eval-mode forward on ``images`` under ``no_grad`` (eager); (2) the view:
+    ``ops.warp_scores(images, rows, photometric=photometric)`` and ``ops.warp_labels(masks, rows)`` - pixels the view takes from
+    outside the image carry the label -100, which the cross entropy ignores, and are "not inside" for the consistency term;
+    (3) ``consistency.set_teacher(teacher_logits, rows)``; (4) ``train_step(model, optimizer, view, labels,
+    extra_loss=consistency, criterion=criterion)``.  The student's step is the same call every time, so from its third
+    occurrence it replays one launch plan - view and labels are copied into the plan's inputs, the teacher buffer keeps its
+    address - and ``consistency.set_lam`` ramps the weight without a new one.  The teacher's forward, the two warps, the
+    ``masks.long()`` conversion and ``set_teacher``'s copies are issued eagerly on every call, in front of the plan."""
+    if ema is None or getattr(optimizer, "ema", None) is not ema or ema.model is not model:
+        raise ValueError("train_step_consistency: ema must be the FlatEMA attached to this optimizer for this model")
+    if not isinstance(consistency, wnn.ConsistencyLoss):
+        raise ValueError("train_step_consistency: consistency must be a wnn.ConsistencyLoss")
+    with torch.no_grad():
+        logits = ema.teacher(images)["out"]
+        if tuple(logits.shape[-2:]) != tuple(images.shape[-2:]):
+            raise ValueError(f"train_step_consistency: the teacher's logits {tuple(logits.shape[-2:])} are not at the images' size "
+                             f"{tuple(images.shape[-2:])}: the view's rows would not map onto them")
+        view = ops.warp_scores(images, rows, photometric=photometric)
+        labels = ops.warp_labels(masks.long(), rows)
+    consistency.set_teacher(logits, rows)
+    return train_step(model, optimizer, view, labels, extra_loss=consistency, criterion=criterion)
+
+
 def make_optimizer(model, lr=1e-4, early_step=None, *, kind="adam", **optimizer_kwargs):
     """torch.optim.Adam(model.parameters(), lr) semantics on one flat buffer.  ``kind``: 'adam' (optim.FlatAdam), 'adamw'
     (optim.FlatAdamW) or 'sgd' (optim.FlatSGD); ``optimizer_kwargs`` go to that class (weight_decay, momentum, nesterov,

@@ -115,6 +115,11 @@ SIGNATURES = {
     "wsdl_flat_ema": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "wsdl_ema_table": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "wsdl_teacher_targets": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _ll, _vp, _vp, _vp, _vp]),
+    "wsdl_warp_scores_fwd": (_i, [_vp, _vp] + [_i] * 7 + [_f, _i, _vp, _vp, _vp]),
+    "wsdl_warp_labels": (_i, [_vp, _vp] + [_i] * 6 + [_ll, _vp, _vp]),
+    "wsdl_warp_scores_bwd": (_i, [_vp, _vp] + [_i] * 8 + [_vp, _vp]),
+    "wsdl_consistency_workspace": (_sz, []),
+    "wsdl_consistency_fwd_bwd": (_i, [_vp] * 5 + [_i] * 10 + [_vp] * 6 + [_sz, _vp]),
     "wsdl_kth_workspace": (_sz, [_i]),
     "wsdl_kth_value": (_i, [_vp, _vp, _ll, _i, _i, _ll, C.c_double, _vp, _vp, _vp, _sz, _vp]),
     "wsdl_mining_valid": (_i, [_vp, _ll, _vp, _vp, _ll, _vp]),

@@ -124,4 +124,34 @@ def affine_row(angle_deg, src_hw, out_hw=None, scale=1.0, flip=False, gain=1.0, 
     return Augment.compose(sample, src_hw, src_hw if out_hw is None else out_hw)[0]
 
 
-__all__ = ["Augment", "IDENTITY_ROW", "affine_row"]
+def relative_rows(student_rows, teacher_rows=None):
+    """(n,8) float32 rows of ``T^-1 o S``: the map from a STUDENT view's output pixel to the pixel of the TEACHER's view, for two
+    views of the same source drawn as ``student_rows`` (S) and ``teacher_rows`` (T), each mapping its output to source pixel
+    coordinates.  What ``ops.consistency_loss(student_logits, teacher, rows)`` and ``ops.warp_scores(teacher, rows)`` take to
+    bring a teacher's prediction onto the student's grid.  ``teacher_rows=None``: the teacher sees the source as it is, the
+    result is the affine part of ``student_rows``.  Composed in float64 with tensor operations on whatever device the rows
+    live on and cast once; the gain / bias columns are ``1 0`` (a prediction is not re-coloured).  A singular teacher row gives
+    a non-finite row, which the kernels treat as "nowhere inside"."""
+    s = torch.as_tensor(student_rows)
+    if s.dim() != 2 or s.shape[1] != 8:
+        raise ValueError(f"relative_rows: student_rows must be (n,8), got {tuple(s.shape)}")
+    s = s.to(torch.float64)
+    if teacher_rows is None:
+        a = s[:, :6]
+    else:
+        t = torch.as_tensor(teacher_rows)
+        if tuple(t.shape) != tuple(s.shape) or t.device != s.device:
+            raise ValueError(f"relative_rows: teacher_rows must be {tuple(s.shape)} on {s.device}, got {tuple(t.shape)} on {t.device}")
+        t = t.to(torch.float64)
+        t00, t01, t02, t10, t11, t12 = t[:, :6].unbind(1)
+        det = t00 * t11 - t01 * t10
+        i00, i01, i10, i11 = t11 / det, -(t01 / det), -(t10 / det), t00 / det           # T's linear part inverted
+        s00, s01, s02, s10, s11, s12 = s[:, :6].unbind(1)
+        dx, dy = s02 - t02, s12 - t12
+        a = torch.stack([i00 * s00 + i01 * s10, i00 * s01 + i01 * s11, i00 * dx + i01 * dy,
+                         i10 * s00 + i11 * s10, i10 * s01 + i11 * s11, i10 * dx + i11 * dy], dim=1)
+    ones, zeros = torch.ones_like(a[:, :1]), torch.zeros_like(a[:, :1])
+    return (torch.cat([a, ones, zeros], dim=1) + 0.0).to(torch.float32)
+
+
+__all__ = ["Augment", "IDENTITY_ROW", "affine_row", "relative_rows"]

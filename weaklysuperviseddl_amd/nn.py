@@ -778,6 +778,109 @@ class SeededRegionGrowingLoss(_Criterion):
                 f"weight={self.weight is not None}")
 
 
+class ConsistencyLoss(_Criterion):
+    """The consistency loss of ``ops.consistency_loss`` between the student's logits and a teacher prediction this object
+    holds - the consistency cost of a mean teacher, FixMatch's confident pseudo-targets (``kind="hard"``, ``tau``) or an
+    equivariance term - shaped as an ``extra_loss`` of ``train_step``: ``forward(student_logits, images=None)``.
+
+    ``set_teacher(teacher, rows=None)`` copies the teacher's (B,C,h,w) prediction - and the (B,8) rows that map the student's
+    pixel grid to the teacher's (``augment.relative_rows``; None: same grid, direct read) - into buffers this object owns,
+    allocated anew only when a shape changes, so the addresses a launch plan freezes stay put while the contents change every
+    step.  ``tau``, ``lam`` and the temperature live in ONE three-float device buffer (``knobs``) the kernel reads:
+    ``set_tau`` / ``set_lam`` / ``set_temperature`` write it WITHOUT a new plan (a ramp of the consistency weight is a ``set_lam``
+    per step).  ``kind``, ``teacher_is``, ``normalize``, ``fill``, every address and the shapes are plain attributes, so
+    ``plan.host_scalars`` puts them into the plan key: another ``kind`` records another plan.  ``counts`` (int64 (2,), on the
+    device) holds ``(pixels inside, pixels counted)`` of the last call.
+
+        cons = wnn.ConsistencyLoss(kind="kl", tau=0.7, lam=0.0).to(device)
+        cons.set_teacher(teacher_logits, rows); cons.set_lam(ramp(step))
+        loss = train_step(model, optimizer, view, labels, extra_loss=cons)
+    """
+
+    _pointers = ("teacher", "rows", "knobs", "counts", "pixel_weight")
+    _shapes = ("teacher", "pixel_weight")
+
+    def __init__(self, kind="kl", temperature=1.0, tau=0.0, lam=1.0, normalize="all", fill="ignore", teacher_is="logits"):
+        super().__init__()
+        self._check(kind, teacher_is, normalize, fill, temperature, tau, lam)
+        self.kind, self.teacher_is, self.normalize, self.fill = kind, teacher_is, normalize, fill
+        for name in ("teacher", "rows", "pixel_weight"):
+            self.register_buffer(name, None, persistent=False)
+        self.register_buffer("knobs", torch.tensor([float(tau), float(lam), float(temperature)], dtype=torch.float32),
+                             persistent=False)
+        self.register_buffer("counts", torch.zeros(2, dtype=torch.int64), persistent=False)
+        self._refresh_pointers()
+
+    @staticmethod
+    def _check(kind, teacher_is, normalize, fill, temperature=1.0, tau=0.0, lam=1.0):
+        for v, table, what in ((kind, ops.CONSISTENCY_KINDS, "kind"), (teacher_is, ops.CONSISTENCY_TEACHER, "teacher_is"),
+                               (normalize, ops.CONSISTENCY_NORMALIZE, "normalize"), (fill, ops.AUGMENT_FILLS, "fill")):
+            if not isinstance(v, str) or v not in table:
+                raise ValueError(f"ConsistencyLoss: {what} {v!r}: one of {sorted(table)}")
+        if not ops._knob_ok(temperature, 0.0, None, True):
+            raise ValueError(f"ConsistencyLoss: temperature {temperature!r} must be a finite number > 0")
+        if not ops._knob_ok(tau, 0.0, 1.0):
+            raise ValueError(f"ConsistencyLoss: tau {tau!r} must be a number in [0, 1]")
+        if not ops._knob_ok(lam):
+            raise ValueError(f"ConsistencyLoss: lam {lam!r} must be a finite number")
+
+    def _own(self, name, t):
+        """Copy ``t`` into the buffer ``name`` (allocated anew only when shape or device change); None drops it."""
+        if t is None:
+            setattr(self, name, None)
+            return
+        cur = getattr(self, name)
+        if cur is None or cur.shape != t.shape or cur.device != t.device:
+            cur = torch.empty(t.shape, device=t.device, dtype=torch.float32)
+            setattr(self, name, cur)
+        cur.copy_(t.detach())
+
+    def set_teacher(self, teacher, rows=None):
+        if not torch.is_tensor(teacher) or teacher.dim() != 4:
+            raise ValueError("ConsistencyLoss.set_teacher: teacher must be a (B,C,h,w) tensor")
+        if rows is not None and (not torch.is_tensor(rows) or tuple(rows.shape) != (teacher.shape[0], 8)):
+            raise ValueError(f"ConsistencyLoss.set_teacher: rows must be a {(teacher.shape[0], 8)} tensor or None")
+        for t, what in ((teacher, "teacher"), (rows, "rows")):              # (the copy below would cast silently)
+            if t is not None and t.dtype != torch.float32:
+                raise ValueError(f"ConsistencyLoss.set_teacher: {what} must be float32, got {t.dtype}")
+        self._own("teacher", teacher)
+        self._own("rows", rows)
+        self._refresh_pointers()
+        return self
+
+    set_pixel_weight = _Criterion._set_pixel_weight
+
+    def set_tau(self, tau):
+        self._check(self.kind, self.teacher_is, self.normalize, self.fill, tau=tau)
+        self.knobs[0:1].fill_(float(tau))           # a stream-ordered fill; the buffer keeps its address
+        return self
+
+    def set_lam(self, lam):
+        self._check(self.kind, self.teacher_is, self.normalize, self.fill, lam=lam)
+        self.knobs[1:2].fill_(float(lam))
+        return self
+
+    def set_temperature(self, temperature):
+        self._check(self.kind, self.teacher_is, self.normalize, self.fill, temperature=temperature)
+        self.knobs[2:3].fill_(float(temperature))
+        return self
+
+    def forward(self, student_logits, images=None):
+        # (options may have been assigned since the constructor checked them)
+        self._check(self.kind, self.teacher_is, self.normalize, self.fill)
+        if self.teacher is None:
+            raise ValueError("ConsistencyLoss: set_teacher(teacher, rows) before the loss is taken")
+        self._refresh_pointers()
+        k = self.knobs
+        return ops.consistency_loss(student_logits, self.teacher, self.rows, kind=self.kind, teacher_is=self.teacher_is,
+                                    temperature=k[2:3], tau=k[0:1], lam=k[1:2], normalize=self.normalize, fill=self.fill,
+                                    pixel_weight=self.pixel_weight, counts=self.counts)
+
+    def extra_repr(self):
+        return (f"kind={self.kind!r}, teacher_is={self.teacher_is!r}, normalize={self.normalize!r}, fill={self.fill!r}, "
+                f"teacher={None if self.teacher is None else tuple(self.teacher.shape)}")
+
+
 class PAMR(nn.Module):
     """Pixel-adaptive mask refinement (Araslanov & Roth, CVPR 2020) as a module without parameters: ``forward(images,
     scores)`` is ``ops.pamr(images, scores, num_iter, dilations)`` - scores (B,C,H,W) propagated ``num_iter`` times over

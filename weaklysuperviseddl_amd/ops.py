@@ -4907,6 +4907,282 @@ def teacher_targets(logits, labels, tau=0.9, mode="replace", ignore_index=-100, 
     return out if conf is None else (out, conf)
 
 
+# ---- view consistency: warps of score / label maps, the consistency loss (csrc/consistency.hip) --------------------------------
+CONSISTENCY_MAX_CLASSES = 64                        # WSDL_CONSISTENCY_MAX_CLASSES
+CONSISTENCY_KINDS = {"kl": 0, "mse": 1, "hard": 2}
+CONSISTENCY_TEACHER = {"logits": 0, "probs": 1}
+CONSISTENCY_NORMALIZE = {"all": 0, "counted": 1}
+
+
+def _warp_front(name, src, rows, out_size, fill, rank, dtype):
+    """The checks the two warps share -> (out_h, out_w).  ``src``: a device tensor of ``rank`` and ``dtype`` without an empty
+    dimension; ``rows``: dense float32 (B,8) on its device."""
+    if not torch.is_tensor(src) or src.dim() != rank:
+        raise WsdlError(f"{name}: the map must be a tensor of rank {rank}")
+    if src.dtype != dtype:
+        raise WsdlError(f"{name}: the map must be {dtype}, got {src.dtype}")
+    if src.numel() == 0:
+        raise WsdlError(f"{name}: the map {tuple(src.shape)} has an empty dimension")
+    if rank == 4 and src.shape[1] > CONSISTENCY_MAX_CLASSES:
+        raise WsdlError(f"{name}: C = {src.shape[1]}, at most {CONSISTENCY_MAX_CLASSES} channels")
+    B = src.shape[0]
+    if not torch.is_tensor(rows) or rows.dtype != torch.float32 or tuple(rows.shape) != (B, 8):
+        raise WsdlError(f"{name}: rows must be a float32 {(B, 8)} tensor (a00 a01 a02 a10 a11 a12 gain bias per item)")
+    if fill not in AUGMENT_FILLS:
+        raise WsdlError(f"{name}: fill {fill!r}: 'ignore' or 'reflect'")
+    h, w = src.shape[-2:]
+    out_h, out_w = (h, w) if out_size is None else (int(v) for v in out_size)
+    for a, b, what in ((h, w, "the map"), (out_h, out_w, "out_size")):
+        if not (1 <= a <= AUGMENT_MAX_SIDE and 1 <= b <= AUGMENT_MAX_SIDE):
+            raise WsdlError(f"{name}: {what} {(a, b)}: side lengths 1..{AUGMENT_MAX_SIDE}")
+    if not src.is_cuda:
+        raise WsdlError(f"{name}: the HIP path needs a device tensor (got {src.device}); there is no CPU fallback")
+    if rows.device != src.device:
+        raise WsdlError(f"{name}: rows are on {rows.device}, the map on {src.device}")
+    return out_h, out_w
+
+
+def _warp_out(name, out, shape, dtype, src):
+    if out is None:
+        return torch.empty(shape, device=src.device, dtype=dtype)
+    if not (torch.is_tensor(out) and out.dtype == dtype and tuple(out.shape) == tuple(shape) and out.is_contiguous()
+            and out.device == src.device and not out.requires_grad):
+        raise WsdlError(f"{name}: out must be a dense {dtype} {tuple(shape)} tensor on {src.device} that needs no gradient")
+    if _shares_memory(out, src):
+        raise WsdlError(f"{name}: out shares memory with the input")
+    return out
+
+
+def _warp_scores_fwd(x, rows, out_hw, fill, pad_value, photometric, valid, out):
+    B, Cc, h, w = x.shape
+    check(lib().wsdl_warp_scores_fwd(_p(x), _p(rows), B, Cc, h, w, out_hw[0], out_hw[1], AUGMENT_FILLS[fill], float(pad_value),
+                                     int(bool(photometric)), _p(out), _p(valid), _stream()))
+
+
+class _WarpScores(torch.autograd.Function):
+    """wsdl_warp_scores_fwd and, for the gradient into the source, its adjoint wsdl_warp_scores_bwd."""
+
+    @staticmethod
+    def forward(ctx, scores, rows, out_hw, fill, pad_value, photometric, valid, out):
+        _warp_scores_fwd(scores.detach().contiguous(), rows, out_hw, fill, pad_value, photometric, valid, out)
+        ctx.mark_dirty(out)                     # (an argument filled in place, the caller's or a new one)
+        ctx.save_for_backward(rows)
+        ctx.geom = (tuple(scores.shape), out_hw, fill, bool(photometric))
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        (rows,) = ctx.saved_tensors
+        (B, Cc, h, w), out_hw, fill, photometric = ctx.geom
+        if fill != "ignore":
+            raise WsdlError("warp_scores: the gradient for fill='reflect' is not built (the adjoint exists for fill='ignore')")
+        dy = _dense(dy, "warp_scores: gradient")
+        dsrc = torch.empty(B, Cc, h, w, device=dy.device, dtype=torch.float32)
+        check(lib().wsdl_warp_scores_bwd(_p(dy), _p(rows), B, Cc, h, w, out_hw[0], out_hw[1], AUGMENT_FILLS[fill], int(photometric),
+                                         _p(dsrc), _stream()))
+        return (dsrc,) + (None,) * 7
+
+
+def warp_scores(scores, rows, out_size=None, *, fill="ignore", pad_value=0.0, photometric=False, valid=False, out=None):
+    """Warp a float32 (B,C,h,w) map - logits, probabilities, CAMs, images - C <= 64, by the affine rows of an augmentation, in
+    one launch (wsdl_warp_scores_fwd).  ``rows`` (B,8) float32 on the device are ``augment.Augment.draw``'s: ``a00 a01 a02 a10
+    a11 a12 gain bias``, the map from OUTPUT to source pixel coordinates, applied by exactly the arithmetic of
+    ``augment_batch`` (include/wsdl_hip.h), so a prediction is warped as the image it was made from: four clamped taps,
+    float32, unfused; ``fill`` "ignore" writes ``pad_value`` where the source point lies outside, "reflect" mirrors the source; a
+    non-finite source point is outside under both.  ``photometric=True`` applies ``gain * value + bias`` (the student's IMAGE
+    view; leave it off for predictions).  ``out_size`` (out_h, out_w), default the source's.  ``valid=True``: returns ``(out,
+    valid)`` with the uint8 (B,out_h,out_w) plane of inside pixels.  ``out``: a dense float32 tensor to fill.
+
+    Differentiable in ``scores`` for ``fill="ignore"``: the backward is the adjoint kernel (wsdl_warp_scores_bwd), a gather in
+    double without atomics, bitwise reproducible.  A backward through ``fill="reflect"`` raises.  The input is not modified; no
+    host read; results do not depend on B."""
+    if not _finite_number(pad_value) and not (isinstance(pad_value, float) and pad_value != pad_value):
+        raise WsdlError(f"warp_scores: pad_value {pad_value!r} must be a finite number or NaN")
+    out_hw = _warp_front("warp_scores", scores, rows, out_size, fill, 4, torch.float32)
+    B, Cc = scores.shape[:2]
+    rows = rows.detach().contiguous()
+    out = _warp_out("warp_scores", out, (B, Cc) + tuple(out_hw), torch.float32, scores)
+    vplane = torch.empty((B,) + tuple(out_hw), device=scores.device, dtype=torch.uint8) if valid else None
+    if torch.is_grad_enabled() and scores.requires_grad:
+        res = _WarpScores.apply(scores, rows, tuple(out_hw), fill, pad_value, photometric, vplane, out)
+    else:
+        _warp_scores_fwd(scores.detach().contiguous(), rows, tuple(out_hw), fill, pad_value, photometric, vplane, out)
+        res = out
+    return (res, vplane) if valid else res
+
+
+def warp_labels(labels, rows, out_size=None, *, fill="ignore", pad_label=-100, out=None):
+    """Warp an int64 (B,h,w) label map by the affine rows of an augmentation (``warp_scores``): the nearest tap
+    ``min(floor(xs), w - 1)``, ``pad_label`` where the source point lies outside (the default -100 survives
+    ``clamp_max_labels`` and is the cross entropy's default ignore value).  One launch (wsdl_warp_labels); ``out``: a dense int64
+    tensor to fill."""
+    if isinstance(pad_label, bool) or not isinstance(pad_label, int):
+        raise WsdlError(f"warp_labels: pad_label {pad_label!r} must be an int")
+    out_hw = _warp_front("warp_labels", labels, rows, out_size, fill, 3, torch.int64)
+    B, h, w = labels.shape
+    src = labels.detach().contiguous()
+    rows = rows.detach().contiguous()
+    out = _warp_out("warp_labels", out, (B,) + tuple(out_hw), torch.int64, labels)
+    check(lib().wsdl_warp_labels(_p(src), _p(rows), B, h, w, out_hw[0], out_hw[1], AUGMENT_FILLS[fill], int(pad_label), _p(out),
+                                 _stream()))
+    return out
+
+
+def _knob_ok(v, lo=None, hi=None, open_lo=False):
+    """A host number inside its range (a device float is checked by nobody: it is read by the kernel)."""
+    if not _finite_number(v):
+        return False
+    if lo is not None and (v <= lo if open_lo else v < lo):
+        return False
+    return hi is None or v <= hi
+
+
+def check_consistency_options(student_logits, teacher, rows=None, *, kind="kl", teacher_is="logits", temperature=1.0, tau=0.0,
+                              lam=1.0, normalize="all", fill="ignore", pixel_weight=None, counts=None, weight_out=None,
+                              target_out=None, name="consistency_loss"):
+    """Host-side validation of ``consistency_loss``, before any device call; every refusal is a WsdlError naming its cause:
+    an unknown ``kind`` / ``teacher_is`` / ``normalize`` / ``fill``; ``temperature`` not a finite number > 0, ``tau`` not a number
+    in [0, 1], ``lam`` not a finite number (each may instead be a one-element float32 tensor); ``student_logits`` / ``teacher``
+    not float32 tensors of rank 4, an empty dimension, more than 64 classes, different B or C; ``rows`` not a float32 (B,8)
+    tensor, or ``rows=None`` with a teacher of another size; ``pixel_weight`` not float32 (B,H,W); ``counts`` / ``weight_out`` /
+    ``target_out`` not a dense int64 (2,) / float32 (B,H,W) / int64 (B,H,W) tensor without a gradient, or sharing memory with an
+    input or with one another; tensors that are not all on one device - checked last, so everything above is refused without
+    a device."""
+    for v, table, what in ((kind, CONSISTENCY_KINDS, "kind"), (teacher_is, CONSISTENCY_TEACHER, "teacher_is"),
+                           (normalize, CONSISTENCY_NORMALIZE, "normalize"), (fill, AUGMENT_FILLS, "fill")):
+        if not isinstance(v, str) or v not in table:
+            raise WsdlError(f"{name}: {what} {v!r}: one of {sorted(table)}")
+    knobs = []
+    for v, what, ok, rule in ((temperature, "temperature", lambda x: _knob_ok(x, 0.0, None, True), "a finite number > 0"),
+                              (tau, "tau", lambda x: _knob_ok(x, 0.0, 1.0), "a number in [0, 1]"),
+                              (lam, "lam", _knob_ok, "a finite number")):
+        if torch.is_tensor(v):
+            if v.numel() != 1 or v.dtype != torch.float32:
+                raise WsdlError(f"{name}: {what} as a tensor must hold one float32")
+            knobs.append((v, what))
+        elif not ok(v):
+            raise WsdlError(f"{name}: {what} {v!r} must be {rule} or a one-element float32 device tensor")
+    tensors = [(student_logits, "student_logits"), (teacher, "teacher")]
+    for t, what in tensors:
+        if not torch.is_tensor(t) or t.dim() != 4:
+            raise WsdlError(f"{name}: {what} must be a (B,C,H,W) tensor")
+        if t.dtype != torch.float32:
+            raise WsdlError(f"{name}: {what} must be float32, got {t.dtype} (fp16 / bf16 maps are not built)")
+        if t.numel() == 0:
+            raise WsdlError(f"{name}: {what} {tuple(t.shape)} has an empty dimension")
+    B, Cc, H, W = student_logits.shape
+    if Cc > CONSISTENCY_MAX_CLASSES:
+        raise WsdlError(f"{name}: student_logits {tuple(student_logits.shape)}: at most {CONSISTENCY_MAX_CLASSES} classes")
+    if tuple(teacher.shape[:2]) != (B, Cc):
+        raise WsdlError(f"{name}: teacher {tuple(teacher.shape)} must have B = {B} and C = {Cc} of student_logits {tuple(student_logits.shape)}")
+    for a, b, what in ((H, W, "student_logits"), (teacher.shape[2], teacher.shape[3], "teacher")):
+        if a > AUGMENT_MAX_SIDE or b > AUGMENT_MAX_SIDE:
+            raise WsdlError(f"{name}: {what} {(a, b)}: side lengths 1..{AUGMENT_MAX_SIDE}")
+    if rows is None:
+        if tuple(teacher.shape) != (B, Cc, H, W):
+            raise WsdlError(f"{name}: rows=None reads the teacher directly: its size {tuple(teacher.shape[2:])} must be the "
+                            f"student's {(H, W)}; pass rows (augment.relative_rows) to sample it")
+    else:
+        if not torch.is_tensor(rows) or rows.dtype != torch.float32 or tuple(rows.shape) != (B, 8):
+            raise WsdlError(f"{name}: rows must be a float32 {(B, 8)} tensor or None")
+        tensors.append((rows, "rows"))
+    if pixel_weight is not None:
+        if not torch.is_tensor(pixel_weight) or pixel_weight.dtype != torch.float32 or tuple(pixel_weight.shape) != (B, H, W):
+            raise WsdlError(f"{name}: pixel_weight must be a float32 {(B, H, W)} tensor or None")
+        tensors.append((pixel_weight, "pixel_weight"))
+    inputs = list(tensors) + knobs
+    outs = []
+    for t, what, shape, dtype in ((counts, "counts", (2,), torch.int64), (weight_out, "weight_out", (B, H, W), torch.float32),
+                                  (target_out, "target_out", (B, H, W), torch.int64)):
+        if t is None:
+            continue
+        if not (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and not t.requires_grad):
+            raise WsdlError(f"{name}: {what} must be a dense {dtype} {shape} tensor that needs no gradient")
+        for other, oname in inputs + outs:
+            if _shares_memory(t, other):
+                raise WsdlError(f"{name}: {what} shares memory with {oname}")
+        outs.append((t, what))
+    device = None
+    for t, what in inputs + outs:
+        if not t.is_cuda:
+            raise WsdlError(f"{name}: {what}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
+        if device is None:
+            device = t.device
+        elif t.device != device:
+            raise WsdlError(f"{name}: {what} is on {t.device}, the other tensors on {device}")
+
+
+def _consistency_knobs(tau, lam, temperature, device):
+    """The three-float device buffer ``tau lam T`` the kernel reads.  Three one-element views of ONE buffer in this order
+    (``wnn.ConsistencyLoss``) are used as they are - no launch, the address stays; anything else is assembled with the tensor
+    library's own kernels (which a launch plan does not see: inside a planned step use the module)."""
+    vals = (tau, lam, temperature)
+    if all(torch.is_tensor(v) for v in vals) and lam.data_ptr() == tau.data_ptr() + 4 and temperature.data_ptr() == tau.data_ptr() + 8 \
+            and tau.untyped_storage().data_ptr() == temperature.untyped_storage().data_ptr():
+        return tau.detach()
+    parts = [v.detach().reshape(1) if torch.is_tensor(v) else torch.full((1,), float(v), device=device, dtype=torch.float32)
+             for v in vals]
+    return torch.cat(parts)
+
+
+class _ConsistencyLoss(torch.autograd.Function):
+    """wsdl_consistency_fwd_bwd: the loss and its gradient (lam / N included) from one call; the backward multiplies by the
+    upstream gradient (``_scaled_grad``)."""
+
+    @staticmethod
+    def forward(ctx, z, teacher, rows, pixel_weight, knobs, kind, teacher_is, normalize, fill, counts, weight_out, target_out):
+        need = z.requires_grad
+        z = _dense(z, "student_logits")
+        B, Cc, H, W = z.shape
+        loss = torch.empty((), device=z.device, dtype=torch.float32)
+        dl = torch.empty_like(z) if need else None
+        ws = workspace(lib().wsdl_consistency_workspace(), z.device)
+        check(lib().wsdl_consistency_fwd_bwd(_p(z), _p(teacher), _p(rows), _p(pixel_weight), _p(knobs), B, Cc, H, W,
+                                             teacher.shape[2], teacher.shape[3], CONSISTENCY_KINDS[kind],
+                                             CONSISTENCY_TEACHER[teacher_is], CONSISTENCY_NORMALIZE[normalize], AUGMENT_FILLS[fill],
+                                             _p(loss), _p(dl), _p(counts), _p(weight_out), _p(target_out), _p(ws), ws.numel(),
+                                             _stream()))
+        ctx.save_for_backward(dl)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dl,) = ctx.saved_tensors
+        return (_scaled_grad(dl, g),) + (None,) * 11
+
+
+def consistency_loss(student_logits, teacher, rows=None, *, kind="kl", teacher_is="logits", temperature=1.0, tau=0.0, lam=1.0,
+                     normalize="all", fill="ignore", pixel_weight=None, counts=None, weight_out=None, target_out=None):
+    """The consistency loss between a student's (B,C,H,W) float32 logits and a teacher's prediction, fused with the teacher's
+    warp and with its gradient (wsdl_consistency_fwd_bwd) - a 0-dim float32 tensor.  Mean teacher with a consistency cost,
+    FixMatch's confident pseudo-targets and SEAM's equivariant regularisation are this one call.
+
+    ``teacher`` (B,C,h_t,w_t): logits (``teacher_is="logits"``: ``q = softmax(t / temperature)``) or probabilities (``"probs"``:
+    ``q = t / sum t``, the temperature is not used).  ``rows`` (B,8): the map from the STUDENT's pixel grid to the teacher's
+    (``augment.relative_rows``); the teacher is sampled at every student pixel by ``warp_scores``' rule - bit for bit the value
+    ``warp_scores(teacher, rows)`` would hold - read once and never materialised.  ``rows=None``: same size, direct read.
+
+    A pixel is COUNTED iff the warp is inside (``fill``), the teacher's values and the student's logits there are finite, and the
+    teacher's confidence ``max q >= tau``; its weight is ``w = counted * pixel_weight`` (float32 (B,H,W), default 1).  ``kind``:
+    "kl" ``sum_c q_c (log q_c - log s_c)``; "mse" ``mean_c (s_c - q_c)^2`` on the two softmaxes; "hard" ``-log s_t`` with ``t``
+    the first class of largest ``q`` (FixMatch in one pass).  The loss is ``lam / N * sum_p w_p l_p`` with ``N = B H W``
+    (``normalize="all"``) or ``sum_p w_p`` ("counted"); with no counted pixel it is 0 with exact zero gradients.
+
+    ``tau``, ``lam`` and ``temperature`` are numbers or one-element float32 device tensors - the kernel reads them from
+    device memory, so a schedule changes floats and a launch plan stays (``wnn.ConsistencyLoss``).  ``counts``: an int64 (2,)
+    tensor that receives ``(pixels inside, pixels counted)``; ``weight_out`` float32 (B,H,W) receives ``w``; ``target_out`` int64
+    (B,H,W) the hard target at counted pixels and -100 elsewhere.  The gradient flows into ``student_logits`` only: the teacher
+    is a constant.  Softmaxes, loss and gradient are evaluated in double and rounded once; no atomics, no host read; two
+    calls give the same bits."""
+    check_consistency_options(student_logits, teacher, rows, kind=kind, teacher_is=teacher_is, temperature=temperature, tau=tau,
+                              lam=lam, normalize=normalize, fill=fill, pixel_weight=pixel_weight, counts=counts,
+                              weight_out=weight_out, target_out=target_out)
+    dense = lambda t: None if t is None else t.detach().contiguous()          # noqa: E731
+    knobs = _consistency_knobs(tau, lam, temperature, student_logits.device)
+    return _ConsistencyLoss.apply(student_logits, dense(teacher), dense(rows), dense(pixel_weight), knobs, kind, teacher_is,
+                                  normalize, fill, counts, weight_out, target_out)
+
+
 def softmax_channels(x):
     return _SoftmaxChannels.apply(x)
 
