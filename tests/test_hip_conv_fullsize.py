@@ -25,13 +25,11 @@ import time
 
 import pytest
 import torch
-import torch.nn.functional as F
 
-from conftest import report_line
+from conv_oracle import ARITHMETICS, DEFAULTS, TOL, Table as _Table, chan_err as _chan_err, config_key as _config_key, \
+    dgrad64 as _dgrad64, fwd64 as _fwd64, set_options as _set, wgrad64 as _wgrad64
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-4          # north_star: 1e-3 relative; the kernels measure ~1e-6
 
 # (Cin, Cout, k, stride, dilation, input-map side at a 256 x 256 image, name, which passes)
 SHAPES = [
@@ -69,59 +67,12 @@ SHAPES = [
 ]
 CONFIGS = {"cfg2": (16, 1), "cfg3": (32, 1), "cfg5": (8, 2)}          # batch, scale of the 256 x 256 image
 
-# (label, library options, passes it applies to)
-ARITHMETICS = [
-    ("fp16x2", dict(conv_split=1, wgrad_split=1, conv_arith=1, conv_il=1), "fdw"),
-    ("fp16x2 plain loop", dict(conv_split=1, wgrad_split=1, conv_arith=1, conv_il=0), "fd"),     # only where the trace says il=1
-    ("fp16x2s (guard)", dict(conv_split=1, wgrad_split=1, conv_arith=2, conv_il=1), "fd"),
-    ("bf16x3", dict(conv_split=1, wgrad_split=1, conv_arith=0, conv_il=1), "fdw"),
-    ("fp32 MFMA", dict(conv_split=0, wgrad_split=0, conv_arith=1, conv_il=1), "fdw"),
-]
-DEFAULTS = dict(conv_split=1, wgrad_split=1, conv_arith=1, conv_il=1)
-
 
 @pytest.fixture(scope="module")
 def dev():
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     return torch.device("cuda:0")
-
-
-def _set(ops, opts):
-    for k, v in opts.items():
-        ops.set_option(k, v)
-
-
-def _chan_err(got, ref64, dim):
-    """max over the other dims of |got - ref| per index of ``dim``, relative to that slice's own max |ref| -> worst slice."""
-    dims = [d for d in range(ref64.dim()) if d != dim]
-    diff = (got.double() - ref64).abs().amax(dim=dims)
-    mag = ref64.abs().amax(dim=dims)
-    top = mag.max()
-    # a slice that is all (or nearly) zero - a dead tap's column of dW - is judged against the tensor's maximum
-    return (diff / torch.maximum(mag, 1e-6 * top)).max().item()
-
-
-def _config_key(trace):
-    """The launch descriptions without their grid extents: the kernel configuration."""
-    return re.sub(r" (grid|workgroups)=[0-9x]+", "", trace)
-
-
-class _Table:
-    def __init__(self):
-        self.rows = {}          # (config key, pass, arithmetic) -> [worst error, example shape, count]
-
-    def add(self, key, pas, arith, err, example):
-        r = self.rows.setdefault((key, pas, arith), [0.0, example, 0])
-        if err >= r[0]:
-            r[0], r[1] = err, example
-        r[2] += 1
-
-    def report(self, title, seconds):
-        report_line(f"{title}: {len(self.rows)} (kernel configuration, pass, arithmetic) combinations against the float64 host oracle "
-                    f"in {seconds:.0f} s; worst per-channel max-norm error {max(r[0] for r in self.rows.values()):.2e}")
-        for (key, pas, arith), (err, ex, n) in sorted(self.rows.items(), key=lambda kv: (kv[0][1], kv[0][0], kv[0][2])):
-            report_line(f"    {pas:5s} {arith:18s} {err:.2e}  x{n:<2d} e.g. {ex:22s} {key}")
 
 
 _VERIFIED = set()       # (configuration, pass, map side, layer): compared with float64 at another batch size already in this process
@@ -154,30 +105,14 @@ def _run_shape(ops, dev, table, B, scale, shape, g, timing):
     _VERIFIED.update(keys)
     t_ref = time.time()
     x64, w64 = x.double(), w.double()
-    if k == 1:
-        # a 1x1 convolution is three matrix products (the float64 GEMM of the host's BLAS is several times faster than ATen's
-        # float64 convolution paths, which this test's time goes into): y[b] = W x[b], dx[b] = W^T dy[b], dW = sum_b dy[b] x[b]^T
-        xs_ = x64[:, :, ::s, ::s].contiguous()
-        OH, OW = xs_.shape[2], xs_.shape[3]
-        w2 = w64.view(Cout, Cin)
-        y64 = torch.matmul(w2, xs_.view(B, Cin, OH * OW)).view(B, Cout, OH, OW)
-        dy = torch.randn(y64.shape, generator=g)
-        dy64 = dy.double()
-        ref = {"f": y64.to(dev)}
-        if "d" in passes:
-            dxs = torch.matmul(w2.t(), dy64.view(B, Cout, OH * OW)).view(B, Cin, OH, OW)
-            dx64 = torch.zeros(x.shape, dtype=torch.float64)
-            dx64[:, :, ::s, ::s] = dxs
-            ref["d"] = dx64.to(dev)
-        ref["w"] = torch.einsum("bop,bip->oi", dy64.view(B, Cout, OH * OW), xs_.view(B, Cin, OH * OW)).view(Cout, Cin, 1, 1).to(dev)
-    else:
-        y64 = F.conv2d(x64, w64, None, s, pad, d)
-        dy = torch.randn(y64.shape, generator=g)
-        dy64 = dy.double()
-        ref = {"f": y64.to(dev)}
-        if "d" in passes:
-            ref["d"] = torch.nn.grad.conv2d_input(x.shape, w64, dy64, s, pad, d).to(dev)
-        ref["w"] = torch.nn.grad.conv2d_weight(x64, w.shape, dy64, s, pad, d).to(dev)
+    # (1x1 convolutions as the three float64 matrix products they are: conv_oracle.py)
+    y64 = _fwd64(x64, w64, s, pad, d)
+    dy = torch.randn(y64.shape, generator=g)
+    dy64 = dy.double()
+    ref = {"f": y64.to(dev)}
+    if "d" in passes:
+        ref["d"] = _dgrad64(x.shape, w64, dy64, s, pad, d).to(dev)
+    ref["w"] = _wgrad64(x64, w.shape, dy64, s, pad, d).to(dev)
     del x64, w64, y64, dy64
     timing["host_oracle_s"] += time.time() - t_ref
     xd, wd_, dyd = x.to(dev), w.to(dev), dy.to(dev)
@@ -255,14 +190,10 @@ def test_aspp_grouped_forward_and_multi_source_dgrad_vs_float64_at_full_size(dev
     x64 = x.double()
     t0 = time.time()
     def fwd64(w, k, d):
-        if k == 1:
-            return torch.matmul(w.double().view(Co, C), x64.view(B, C, H * H)).view(B, Co, H, H)
-        return F.conv2d(x64, w.double(), None, 1, d * (k - 1) // 2, d)
+        return _fwd64(x64, w.double(), 1, d * (k - 1) // 2, d)
 
     def dgrad64(w, dy, k, d):
-        if k == 1:
-            return torch.matmul(w.double().view(Co, C).t(), dy.double().view(B, Co, H * H)).view(B, C, H, H)
-        return torch.nn.grad.conv2d_input(x.shape, w.double(), dy.double(), 1, d * (k - 1) // 2, d)
+        return _dgrad64(x.shape, w.double(), dy.double(), 1, d * (k - 1) // 2, d)
 
     y64 = [fwd64(w, k, d).to(dev) for w, k, d in zip(ws, ks, dils)]
     dx64 = sum(dgrad64(w, dy, k, d) for w, dy, k, d in zip(ws, dys, ks, dils)).to(dev)

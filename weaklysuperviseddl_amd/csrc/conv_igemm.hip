@@ -1973,7 +1973,9 @@ int wsdl_conv2d_prep_weights(const float* w, void* wt_fwd, void* wt_dgrad, int C
             // into the other layout's trailer
             const float* amax = w_amax;
             if (!amax) {
-                const long long body = split_layout_bytes(1, (long long)T * Cin, Cout) - 16;
+                // (the trailer of THAT layout: the two bodies differ in size when only the dgrad layout is a split one)
+                const long long body = f8 ? split_layout_bytes(1, (long long)T * Cin, Cout) - 16
+                                          : split_layout_bytes(1, (long long)T * Cout, Cin) - 16;
                 float* tr = reinterpret_cast<float*>((f8 ? f8 : d8) + body);
                 WSDL_HIP_CHECK(hipMemsetAsync(tr, 0, 16, wsdl::as_stream(stream)));
                 hipLaunchKernelGGL(amax_kernel, dim3((int)std::min<long long>((total + 1023) / 1024, 1024)), dim3(256), 0,

@@ -742,9 +742,11 @@ __device__ __forceinline__ void prep_weights_split_body(const float* __restrict_
         int e;
         ws = pow2_scale(*amax, e);
         if (bx == 0 && by == 0 && tid == 0) {
-            const long long body = split_layout_bytes(AR, (long long)T * Cin, Cout) - 16;     // same for both layouts
-            if (fwd) *reinterpret_cast<float*>(fwd + body) = *amax;
-            if (dg) *reinterpret_cast<float*>(dg + body) = *amax;
+            // each layout's own body: (T * Cin / 16) * Cout and (T * Cout / 16) * Cin k16 slabs are the same number only when both
+            // channel counts are multiples of 16 - a weight with Cin % 16 != 0 has a split dgrad layout alone, and its trailer is
+            // where the convolution kernel reads it: behind (T * Cout / 16) * Cin slabs
+            if (fwd) *reinterpret_cast<float*>(fwd + split_layout_bytes(AR, (long long)T * Cin, Cout) - 16) = *amax;
+            if (dg) *reinterpret_cast<float*>(dg + split_layout_bytes(AR, (long long)T * Cout, Cin) - 16) = *amax;
         }
     }
     for (int r = tid >> 5; r < nco; r += 8) {
