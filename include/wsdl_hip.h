@@ -831,6 +831,50 @@ int wsdl_consistency_fwd_bwd(const float* student, const float* teacher, const f
                              int normalize, int fill, float* loss, float* dlogits, long long* counts, float* weight_out,
                              long long* target_out, void* ws, size_t ws_bytes, wsdl_stream_t stream);
 
+/* ---- batch mixing: CutMix / ClassMix / copy-paste as a selection (csrc/mix.hip) ----
+ * The reference has no such step.  A batch has B items with planes of H x W (sides 1..16384).  partner (B) int32: item b is mixed
+ * with item partner[b]; a value outside [0, B) leaves item b UNMIXED (its mask is 0 everywhere) - the value is tested before it
+ * indexes anything; self-partners and duplicates are legal.  The mask M[b,y,x] in {0,1}, 1 = "take the partner's pixel":
+ *   WSDL_MIX_BOX    boxes (B,R,4) int32, 1 <= R <= WSDL_MIX_MAX_BOXES, rows (y0, x0, y1, x1) half-open in pixels: M = 1 inside the
+ *                   union of the R boxes; y1 <= y0 or x1 <= x0 contributes nothing; coordinates outside the image clip implicitly.
+ *   WSDL_MIX_CLASS  M = 1 iff class_labels[partner[b],y,x] (int64) is a class of the 64-bit set sel[partner[b]]; a label outside
+ *                   [0, 64) is never selected, and wsdl_mix_class_select sets no bit from C on, so neither is one outside [0, C).
+ *   WSDL_MIX_MASK   mask (B,H,W) uint8: M = mask[b] != 0.
+ * invert = 1 flips M for mixed items only.
+ *
+ * wsdl_mix_class_select: the ClassMix choice on the device, C <= WSDL_MIX_MAX_CLASSES.  Item i uses seeds[i] (int64) for its own
+ * label map: present_i = the classes c < C with bit c of `candidates` set and some pixel class_labels[i] == c; n = |present_i|,
+ * k = ceil(n / 2); key(c) = fmix(uint64(seeds[i]) + (c + 1) * 0x9E3779B97F4A7C15) modulo 2^64, fmix the splitmix64 finaliser
+ * (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31); sel_i = the k present classes of
+ * smallest (key, c), as a bit set; n = 0 gives the empty set.  present and sel (B) int64 receive the two sets.  A memset of
+ * `present`, a presence launch (one 64-bit integer atomic OR per workgroup) and a one-wave-per-image selection launch.
+ *
+ * wsdl_mix_apply: for each of the n_tensors <= WSDL_MIX_MAX_TENSORS tensors (B, channels, H, W) of 4- or 8-byte elements,
+ * dst[b,c,y,x] = M[b,y,x] ? src[partner[b],c,y,x] : src[b,c,y,x] - ONE launch for all of them, the mask evaluated once per pixel.
+ * The outputs are bit copies (values move as integer words); inputs are never modified.  mask_out (B,H,W) uint8 and count_out (B)
+ * int64 may be NULL: M itself, and the number of pixels with M = 1 (zeroed by a memset in front of the launch, then one integer
+ * atomic per workgroup: exact, order-independent).  An output that overlaps an input or another output in memory is refused
+ * (item b reads item partner[b]: in-place use is a race).  Four pixels per lane with 16-byte accesses where W % 4 == 0 and
+ * every base is 16-byte aligned (mask, mask_out: 4-byte), one pixel per lane otherwise.  No host read, every parameter by value
+ * or in device memory: a launch plan can hold both calls; two calls give the same bits. */
+#define WSDL_MIX_MAX_CLASSES 64
+#define WSDL_MIX_MAX_BOXES 8
+#define WSDL_MIX_MAX_TENSORS 4
+#define WSDL_MIX_BOX 0
+#define WSDL_MIX_CLASS 1
+#define WSDL_MIX_MASK 2
+typedef struct wsdl_mix_tensor {
+    const void* src;
+    void* dst;
+    int channels;
+    int elem_bytes;
+} wsdl_mix_tensor;
+int wsdl_mix_class_select(const int64_t* class_labels, const int64_t* seeds, int B, int C, int H, int W, unsigned long long candidates,
+                          int64_t* present, int64_t* sel, wsdl_stream_t stream);
+int wsdl_mix_apply(const wsdl_mix_tensor* tensors, int n_tensors, const int32_t* partner, int kind, const int32_t* boxes, int R,
+                   const int64_t* class_labels, const int64_t* sel, const uint8_t* mask, int invert, int B, int H, int W,
+                   uint8_t* mask_out, int64_t* count_out, wsdl_stream_t stream);
+
 /* ---- pixel mining: selecting pixels by their loss without a host read (csrc/pixel_mining.hip) -
  * wsdl_kth_value: x holds `segments` runs of n_per_segment floats.  The candidates of segment s are the x[s*n + i] that are
  * not NaN and, when `valid` (one byte per element) is given, have valid[s*n + i] != 0; n_valid[s] receives their number n.

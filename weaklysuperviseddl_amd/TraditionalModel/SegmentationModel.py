@@ -27,6 +27,7 @@ import torch.nn as nn
 from .. import nn as wnn
 from .. import ops
 from .. import plan
+from ..augment import Mix
 from ..optim import FlatAdam, FlatAdamW, FlatSGD
 from .ExtraUtilities import compute_iou_and_acc
 
@@ -457,6 +458,60 @@ def train_step_consistency(model, ema, optimizer, images, masks, rows, criterion
         labels = ops.warp_labels(masks.long(), rows)
     consistency.set_teacher(logits, rows)
     return train_step(model, optimizer, view, labels, extra_loss=consistency, criterion=criterion)
+
+
+def train_step_mixed(model, ema, optimizer, images, masks, mix, params, criterion=None, *, tau=0.9, weight_by_conf=False,
+                     consistency=None):
+    """One iteration on a MIXED batch - CutMix, ClassMix or copy-paste (``augment.Mix``), the strong perturbation of the
+    teacher / student recipes (CutMix-Seg, ClassMix, DACS, UniMatch); returns the loss tensor of ``train_step``.
+
+    ``mix``: an ``augment.Mix``; ``params``: this step's slice of its ``epoch_params`` (``Mix.step_params(params, i)``: partner,
+    boxes, seeds on the device).  Steps:
+    (1) the labels.  With ``ema`` (the ``ema.FlatEMA`` attached to ``optimizer``): the teacher's eval-mode forward on ``images``
+        under ``no_grad``, then ``ops.teacher_targets(teacher logits, masks clamped to {0, 1}, tau, mode="replace",
+        conf=weight_by_conf)``.  With ``ema=None``: ``masks`` as they are - plain CutMix or copy-paste on pseudo masks.
+    (2) "classmix" / "copy_paste": ``ops.mix_class_select`` on those labels (``ema=None``: clamped to {0, 1}, as ``train_step``
+        will see them), over the teacher's channel count of classes (2 without a teacher).
+    (3) ONE ``ops.mix_batch`` over the images, the labels, the teacher's confidence as ``pixel_weight`` (``weight_by_conf``) and
+        the teacher's logits as ``scores`` (``consistency``).
+    (4) ``weight_by_conf``: ``criterion.set_pixel_weight(mixed confidence)`` - ``criterion`` must be a ``wnn.CrossEntropyLoss``, as
+        for ``train_step_mean_teacher``.  ``consistency`` (a ``wnn.ConsistencyLoss``): ``consistency.set_teacher(mixed teacher
+        logits)`` and it becomes the ``extra_loss`` - the mixed-teacher target of French et al.  Both need ``ema``.
+    (5) ``train_step(model, optimizer, mixed images, mixed labels, ...)``: the same call every time, so from its third
+        occurrence it replays one launch plan.  The teacher's forward and the mixing launches are issued eagerly on every
+        call, in front of the plan, like the warps of ``train_step_consistency``.
+    An item whose partner is -1 is unmixed: with every partner -1 the step equals ``train_step_mean_teacher(mode="replace")``
+    (``ema=None``: ``train_step``) bit for bit."""
+    if not isinstance(mix, Mix):
+        raise ValueError("train_step_mixed: mix must be an augment.Mix")
+    if ema is not None and (getattr(optimizer, "ema", None) is not ema or ema.model is not model):
+        raise ValueError("train_step_mixed: ema must be the FlatEMA attached to this optimizer for this model (or None)")
+    if ema is None and (weight_by_conf or consistency is not None):
+        raise ValueError("train_step_mixed: weight_by_conf and consistency need the teacher (ema)")
+    if weight_by_conf and not isinstance(criterion, wnn.CrossEntropyLoss):
+        raise ValueError("train_step_mixed: weight_by_conf needs criterion=wnn.CrossEntropyLoss(...) (set_pixel_weight)")
+    if consistency is not None and not isinstance(consistency, wnn.ConsistencyLoss):
+        raise ValueError("train_step_mixed: consistency must be a wnn.ConsistencyLoss")
+    labels, logits, conf, class_labels = masks.long(), None, None, None
+    if ema is not None:
+        with torch.no_grad():
+            logits = ema.teacher(images)["out"]
+        labels = ops.clamp_max_labels(labels, 1)
+        if weight_by_conf:
+            labels, conf = ops.teacher_targets(logits, labels, tau, "replace", conf=True)
+        else:
+            labels = ops.teacher_targets(logits, labels, tau, "replace")
+    elif mix.kind != "cutmix":
+        class_labels = ops.clamp_max_labels(labels, 1)
+    mixed = mix.apply(images, labels, params, class_labels=class_labels, num_classes=2 if logits is None else int(logits.shape[1]),
+                      pixel_weight=conf,
+                      scores=logits if consistency is not None else None)
+    if weight_by_conf:
+        criterion.set_pixel_weight(mixed.pixel_weight)
+    if consistency is not None:
+        consistency.set_teacher(mixed.scores)
+        return train_step(model, optimizer, mixed.images, mixed.labels, extra_loss=consistency, criterion=criterion)
+    return train_step(model, optimizer, mixed.images, mixed.labels, criterion=criterion)
 
 
 def make_optimizer(model, lr=1e-4, early_step=None, *, kind="adam", **optimizer_kwargs):

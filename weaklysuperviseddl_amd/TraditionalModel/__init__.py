@@ -5,7 +5,7 @@ from .PsuedoMasks import (generate_pseudo_masks, keep_largest, generate, stage_h
                           prototype_cam)
 from .SegmentationModel import (SegmentationModel, build_segmentation_model, train_step, train_step_mean_teacher, evaluate_model,  # noqa: F401
                                 train_segmentation_model, evaluate_boundary_iou, evaluate_surface_distances,
-                                predict_multiscale, train_step_consistency)
+                                predict_multiscale, train_step_consistency, train_step_mixed)
 from .AlternatingDirectionCutLoss import (  # noqa: F401
     LocalNormalizedCutLoss, compute_affinities, refine_pseudo_mask, refine_pseudo_masks_batched, train_model,
     refine_dataset, run_alternating_training, network_soft_prediction, apply_dense_crf,

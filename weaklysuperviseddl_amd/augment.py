@@ -15,6 +15,8 @@ so cross entropy ignores the padding as it is; the Lovasz losses need ``train_st
 ``fill="reflect"``: the source is mirrored about its borders, every output pixel is valid and nothing needs ignoring - the
 mode to use with the NCut and boundary terms, which would otherwise see an edge at the pad border.
 """
+import math
+
 import torch
 
 IDENTITY_ROW = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 1.0, 0.0)
@@ -154,4 +156,121 @@ def relative_rows(student_rows, teacher_rows=None):
     return (torch.cat([a, ones, zeros], dim=1) + 0.0).to(torch.float32)
 
 
-__all__ = ["Augment", "IDENTITY_ROW", "affine_row", "relative_rows"]
+_MIX_KINDS = ("cutmix", "classmix", "copy_paste")
+
+
+class Mix:
+    """Batch mixing - CutMix, ClassMix, copy-paste - for teacher / student training.  Like ``Augment`` a ``Mix`` only DRAWS
+    parameters; ``ops.mix_class_select`` and ``ops.mix_batch`` apply them on the device (``apply``).
+
+    ``kind``     "cutmix": item b takes a box (the union of ``boxes`` boxes) from its partner;
+                 "classmix": it takes the pixels of half of the classes present in the partner's label map, chosen on the device
+                 from the item's seed;
+                 "copy_paste": it takes the partner's pixels of class 1, the foreground (``candidates = (1,)``).
+    ``prob``     probability that an item is mixed at all; an unmixed item has the partner -1.
+    ``area``     (low, high) fraction of the image one box covers, uniform;
+    ``aspect``   (low, high) width / height of a box, log-uniform;
+    ``boxes``    R, boxes per item, 1..8;
+    ``partner``  "roll": one shift s per batch, item b is mixed with item (b + s) mod B, s in [1, B - 1] - never itself;
+                 "permute": a random permutation per batch (fixed points mix an item with itself, which changes nothing).
+
+    Draw order (``draw``), everything for all ``n_batches`` at once and each component only if it can vary:
+      1. partners - "roll" with B >= 3: ``torch.randint(1, B, (n_batches,))`` (B = 2 has the one shift 1, B = 1 the shift 0:
+         nothing is drawn); "permute" with B >= 2: ``torch.randperm(B)`` once per batch;
+      2. 0 < ``prob`` < 1: ``torch.rand(n_batches, B)`` float64, an item is mixed where the draw is below ``prob``;
+      3. "cutmix" only, each as ``torch.rand(n_batches, B, R)`` float64: the area fraction (unless ``area`` is one point), the
+         aspect (unless ``aspect`` is one point), the row position, the column position;
+      4. "classmix" only: the seeds, ``torch.randint(0, 2**32, (n_batches, B, 2))`` joined to one int64 each.
+    Whatever is not drawn is zeros: ``boxes`` of empty boxes, ``seeds`` of 0 (copy-paste's single candidate is taken whenever
+    it is present: no seed can change that)."""
+
+    def __init__(self, kind="cutmix", prob=1.0, area=(0.25, 0.5), aspect=(0.5, 2.0), boxes=1, partner="roll"):
+        if kind not in _MIX_KINDS:
+            raise ValueError(f"Mix: kind {kind!r}: 'cutmix', 'classmix' or 'copy_paste'")
+        if partner not in ("roll", "permute"):
+            raise ValueError(f"Mix: partner {partner!r}: 'roll' or 'permute'")
+        self.kind, self.partner, self.prob = kind, partner, float(prob)
+        if not 0.0 <= self.prob <= 1.0:
+            raise ValueError(f"Mix: prob {prob!r} is a probability")
+        self.area, self.aspect = _pair(area, "area"), _pair(aspect, "aspect")
+        if self.area[1] > 1.0:
+            raise ValueError(f"Mix: area {area!r}: fractions of the image, at most 1")
+        if isinstance(boxes, bool) or not isinstance(boxes, int) or not 1 <= boxes <= 8:
+            raise ValueError(f"Mix: boxes {boxes!r}: an int in 1..8")
+        self.boxes = boxes
+        self.candidates = (1,) if kind == "copy_paste" else None          # the class list of ops.mix_class_select
+
+    def draw(self, n_batches, B, hw, generator=None):
+        """The parameters of ``n_batches`` batches of B items with planes of ``hw`` = (H, W), as CPU tensors: ``{"partner": int32
+        (n_batches,B), "boxes": int32 (n_batches,B,R,4), "seeds": int64 (n_batches,B)}``.  Boxes are rows ``(y0, x0, y1, x1)``,
+        half-open: with f the area fraction and r the aspect, ``h = sqrt(f H W / r)``, ``w = sqrt(f H W r)`` in float64, each
+        rounded once and clamped to [1, H] / [1, W]; the position is uniform over the places where the box fits, so every box
+        lies inside the image with at least one pixel."""
+        n, B = int(n_batches), int(B)
+        H, W = (int(v) for v in hw)
+        if n < 0 or B < 1 or H < 1 or W < 1:
+            raise ValueError(f"Mix.draw: n_batches {n_batches!r}, B {B!r}, hw {hw!r}")
+        R = self.boxes
+        f64 = torch.float64
+        item = torch.arange(B, dtype=torch.int64)
+        if self.partner == "roll":
+            if B >= 3:
+                shift = torch.randint(1, B, (n,), generator=generator, dtype=torch.int64)
+            else:
+                shift = torch.full((n,), B - 1, dtype=torch.int64)
+            partner = (item[None, :] + shift[:, None]) % B
+        elif B >= 2:
+            partner = torch.stack([torch.randperm(B, generator=generator) for _ in range(n)]) if n else torch.zeros(0, B, dtype=torch.int64)
+        else:
+            partner = torch.zeros(n, B, dtype=torch.int64)
+        if 0.0 < self.prob < 1.0:
+            mixed = torch.rand(n, B, generator=generator, dtype=f64) < self.prob
+        else:
+            mixed = torch.full((n, B), self.prob == 1.0)
+        partner = torch.where(mixed, partner, torch.full_like(partner, -1)).to(torch.int32)
+
+        boxes = torch.zeros(n, B, R, 4, dtype=torch.int32)
+        if self.kind == "cutmix":
+            def uniform(lo, hi):
+                if lo == hi:
+                    return torch.full((n, B, R), lo, dtype=f64)
+                return lo + (hi - lo) * torch.rand(n, B, R, generator=generator, dtype=f64)
+            frac = uniform(*self.area)
+            aspect = torch.exp(uniform(math.log(self.aspect[0]), math.log(self.aspect[1])))
+            uy = torch.rand(n, B, R, generator=generator, dtype=f64)
+            ux = torch.rand(n, B, R, generator=generator, dtype=f64)
+            h = torch.sqrt(frac * (H * W) / aspect).round().clamp(1, H).to(torch.int64)
+            w = torch.sqrt(frac * (H * W) * aspect).round().clamp(1, W).to(torch.int64)
+            y0 = torch.minimum((uy * (H - h + 1).to(f64)).floor().to(torch.int64), H - h)
+            x0 = torch.minimum((ux * (W - w + 1).to(f64)).floor().to(torch.int64), W - w)
+            boxes = torch.stack([y0, x0, y0 + h, x0 + w], dim=-1).to(torch.int32)
+        seeds = torch.zeros(n, B, dtype=torch.int64)
+        if self.kind == "classmix":
+            words = torch.randint(0, 2 ** 32, (n, B, 2), generator=generator, dtype=torch.int64)
+            seeds = (words[..., 0] - 2 ** 31) * 2 ** 32 + words[..., 1]
+        return {"partner": partner, "boxes": boxes, "seeds": seeds}
+
+    def epoch_params(self, n_batches, B, hw, device, generator=None):
+        """The parameters of a whole epoch, drawn now and uploaded once; step i takes ``step_params(params, i)``."""
+        return {k: v.to(device) for k, v in self.draw(n_batches, B, hw, generator).items()}
+
+    @staticmethod
+    def step_params(params, i):
+        """Slice ``[i]`` of every tensor of ``epoch_params``: views, no copy and no host -> device traffic."""
+        return {k: v[i] for k, v in params.items()}
+
+    def apply(self, images, labels, params_i, *, class_labels=None, num_classes=2, pixel_weight=None, scores=None, want_mask=False,
+              want_count=False, out=None):
+        """Mix one batch with the parameters of its step (``step_params``) -> ``ops.MixResult``.  "cutmix": one
+        ``ops.mix_batch(kind="box")``; "classmix" / "copy_paste": ``ops.mix_class_select`` on ``class_labels`` (default: ``labels``)
+        with ``num_classes`` and this object's ``candidates``, then ``ops.mix_batch(kind="class")``."""
+        from . import ops
+        kw = dict(pixel_weight=pixel_weight, scores=scores, want_mask=want_mask, want_count=want_count, out=out)
+        if self.kind == "cutmix":
+            return ops.mix_batch(images, labels, params_i["partner"], kind="box", boxes=params_i["boxes"], **kw)
+        cls = labels if class_labels is None else class_labels
+        sel, _ = ops.mix_class_select(cls, num_classes, params_i["seeds"], candidates=self.candidates)
+        return ops.mix_batch(images, labels, params_i["partner"], kind="class", class_labels=cls, sel=sel, **kw)
+
+
+__all__ = ["Augment", "IDENTITY_ROW", "Mix", "affine_row", "relative_rows"]

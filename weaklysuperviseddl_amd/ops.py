@@ -2,6 +2,7 @@
 kernels of libwsdl_hip.so.  Every arithmetic step runs in the library; torch here only allocates
 buffers and orders calls on the current stream.  No CPU fallback: non-device tensors raise.
 """
+import collections
 import ctypes as C
 
 import os
@@ -5181,6 +5182,260 @@ def consistency_loss(student_logits, teacher, rows=None, *, kind="kl", teacher_i
     knobs = _consistency_knobs(tau, lam, temperature, student_logits.device)
     return _ConsistencyLoss.apply(student_logits, dense(teacher), dense(rows), dense(pixel_weight), knobs, kind, teacher_is,
                                   normalize, fill, counts, weight_out, target_out)
+
+
+# ---- batch mixing: CutMix / ClassMix / copy-paste (csrc/mix.hip; include/wsdl_hip.h "batch mixing") ----------------------------
+MIX_MAX_CLASSES = 64                                # WSDL_MIX_MAX_CLASSES
+MIX_MAX_BOXES = 8                                   # WSDL_MIX_MAX_BOXES
+MIX_KINDS = {"box": 0, "class": 1, "mask": 2}       # WSDL_MIX_BOX / _CLASS / _MASK
+MixResult = collections.namedtuple("MixResult", "images labels pixel_weight scores mask mixed_count")
+_MIX_OUT_KEYS = ("images", "labels", "pixel_weight", "scores", "mask", "mixed_count")
+
+
+class _MixTensor(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("channels", C.c_int), ("elem_bytes", C.c_int)]       # wsdl_mix_tensor
+
+
+def _mix_tensor(name, t, what, rank, dtype, shape=None):
+    if not torch.is_tensor(t) or t.dim() != rank:
+        raise WsdlError(f"{name}: {what} must be a tensor of rank {rank}")
+    if t.dtype != dtype:
+        raise WsdlError(f"{name}: {what} must be {dtype}, got {t.dtype}")
+    if t.numel() == 0:
+        raise WsdlError(f"{name}: {what} {tuple(t.shape)} has an empty dimension")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise WsdlError(f"{name}: {what} {tuple(t.shape)} must be {tuple(shape)}")
+
+
+def _mix_one_device(name, tensors):
+    """The place last: everything before can be refused without a device."""
+    device = None
+    for t, what in tensors:
+        if not t.is_cuda:
+            raise WsdlError(f"{name}: {what}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
+        if device is None:
+            device = t.device
+        elif t.device != device:
+            raise WsdlError(f"{name}: {what} is on {t.device}, the other tensors on {device}")
+
+
+def _mix_outs(name, out, keys, specs, inputs):
+    """``out``: None or a dict whose entries (of ``keys``) are dense tensors of the wanted shape and type that share no memory
+    with an input or with each other -> [(tensor, what)] of the entries given."""
+    if out is None:
+        return []
+    if not isinstance(out, dict) or any(k not in keys for k in out):
+        raise WsdlError(f"{name}: out must be a dict with keys from {keys}")
+    given = []
+    for key, t in out.items():
+        if key not in specs:
+            raise WsdlError(f"{name}: out[{key!r}] is given but the call does not produce it")
+        shape, dtype = specs[key]
+        what = f"out[{key!r}]"
+        if not (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous() and not t.requires_grad):
+            raise WsdlError(f"{name}: {what} must be a dense {dtype} {tuple(shape)} tensor that needs no gradient")
+        for other, oname in inputs + given:
+            if _shares_memory(t, other):
+                raise WsdlError(f"{name}: {what} shares memory with {oname}")
+        given.append((t, what))
+    return given
+
+
+def _mix_candidates(name, candidates, num_classes):
+    """The class list as a 64-bit set (None: every class)."""
+    if candidates is None:
+        return (1 << num_classes) - 1
+    word = 0
+    try:
+        cands = [c for c in candidates]
+    except TypeError:
+        raise WsdlError(f"{name}: candidates {candidates!r} must be None or a list of classes") from None
+    for c in cands:
+        if isinstance(c, bool) or not isinstance(c, int) or not 0 <= c < num_classes:
+            raise WsdlError(f"{name}: candidates {candidates!r}: every entry must be an int in [0, {num_classes})")
+        word |= 1 << c
+    return word
+
+
+def check_mix_select_options(class_labels, num_classes, seeds, candidates=None, out=None, name="mix_class_select"):
+    """Host-side validation of ``mix_class_select``, before any device call.  WsdlError for: ``num_classes`` not an int in
+    [1, 64]; ``class_labels`` not an int64 (B,H,W) tensor, ``seeds`` not an int64 (B,) tensor, an empty dimension, a side over
+    16384; ``candidates`` that is neither None nor a list of ints in [0, num_classes); ``out`` that is not a dict of dense int64
+    (B,) tensors under 'sel' / 'present', or that shares memory with an input; tensors that are not on one device.  Returns the
+    candidates as a 64-bit set."""
+    if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 1 <= num_classes <= MIX_MAX_CLASSES:
+        raise WsdlError(f"{name}: num_classes {num_classes!r} must be an int in [1, {MIX_MAX_CLASSES}] (the selected set is one 64-bit word)")
+    _mix_tensor(name, class_labels, "class_labels", 3, torch.int64)
+    B, H, W = class_labels.shape
+    if H > AUGMENT_MAX_SIDE or W > AUGMENT_MAX_SIDE:
+        raise WsdlError(f"{name}: class_labels {tuple(class_labels.shape)}: side lengths 1..{AUGMENT_MAX_SIDE}")
+    _mix_tensor(name, seeds, "seeds", 1, torch.int64, (B,))
+    word = _mix_candidates(name, candidates, num_classes)
+    inputs = [(class_labels, "class_labels"), (seeds, "seeds")]
+    given = _mix_outs(name, out, ("sel", "present"), {"sel": ((B,), torch.int64), "present": ((B,), torch.int64)}, inputs)
+    _mix_one_device(name, inputs + given)
+    return word
+
+
+def mix_class_select(class_labels, num_classes, seeds, *, candidates=None, out=None):
+    """The ClassMix class choice, on the device: for every item i of the int64 (B,H,W) label map ``class_labels`` the classes that
+    are PRESENT and half of them SELECTED, as two int64 (B,) tensors of 64-bit sets -> ``(sel, present)``; ``num_classes`` <= 64.
+
+    ``present_i`` = the candidates c (``candidates``: a list of classes, default all of ``range(num_classes)``) for which some
+    pixel has ``class_labels[i] == c`` - a label outside ``[0, num_classes)`` (-100, 255) counts for nothing; n = |present_i|,
+    k = ceil(n / 2); ``key(c) = fmix(uint64(seeds[i]) + (c + 1) * 0x9E3779B97F4A7C15)`` modulo 2^64, ``fmix`` the splitmix64
+    finaliser; ``sel_i`` = the k present classes with the smallest ``(key, c)``; n = 0 gives the empty set.  With two classes this
+    picks background or foreground with equal probability; ``candidates=(1,)`` is copy-paste: the foreground whenever present.
+    ``seeds``: an int64 (B,) device tensor (``augment.Mix.draw``), item i uses ``seeds[i]`` for its own label map.
+
+    ``out``: a dict with dense int64 (B,) tensors under 'sel' / 'present' to fill.  ``mix_launches("class", select=True)`` says
+    what is issued: a memset of ``present``, the presence launch (one 64-bit integer atomic OR per workgroup) and the selection
+    launch.  No host read, bitwise reproducible, the inputs are not modified; a launch plan can hold the call."""
+    word = check_mix_select_options(class_labels, num_classes, seeds, candidates, out)
+    labels = class_labels.detach().contiguous()
+    seeds = seeds.detach().contiguous()
+    B, H, W = labels.shape
+    out = out or {}
+    sel, present = (out.get(k) if out.get(k) is not None else torch.empty(B, dtype=torch.int64, device=labels.device)
+                    for k in ("sel", "present"))
+    check(lib().wsdl_mix_class_select(_p(labels), _p(seeds), B, int(num_classes), H, W, word, _p(present), _p(sel), _stream()))
+    return sel, present
+
+
+def check_mix_options(images, labels, partner, *, kind, boxes=None, class_labels=None, sel=None, mask=None, invert=False,
+                      pixel_weight=None, scores=None, want_mask=False, want_count=False, out=None, name="mix_batch"):
+    """Host-side validation of ``mix_batch``, before any device call.  WsdlError - naming the argument - for: an unknown ``kind``;
+    ``images`` not a float32 (B,Ci,H,W) tensor, ``labels`` not int64 (B,H,W), ``pixel_weight`` not float32 (B,H,W), ``scores`` not
+    float32 (B,Cs,H,W) with Cs <= 64, ``partner`` not int32 (B,); a side over 16384, an empty dimension; ``kind="box"`` without
+    ``boxes`` or with boxes that are not int32 (B,R,4), 1 <= R <= 8; ``kind="class"`` without ``class_labels`` (int64 (B,H,W)) or
+    without ``sel`` (int64 (B,)); ``kind="mask"`` without ``mask`` (uint8 (B,H,W)); a source argument of another kind; ``invert``,
+    ``want_mask``, ``want_count`` that are not bools; ``out`` that is not a dict of dense tensors of the results' shapes and types,
+    that names a result the call does not produce, or whose entry shares memory with an input or with another entry (item b
+    reads item ``partner[b]``: in-place use is a race); tensors that are not on one device."""
+    if kind not in MIX_KINDS:
+        raise WsdlError(f"{name}: kind {kind!r}: 'box', 'class' or 'mask'")
+    for v, what in ((invert, "invert"), (want_mask, "want_mask"), (want_count, "want_count")):
+        if not isinstance(v, bool):
+            raise WsdlError(f"{name}: {what} {v!r} must be True or False")
+    _mix_tensor(name, images, "images", 4, torch.float32)
+    B, _, H, W = images.shape
+    if H > AUGMENT_MAX_SIDE or W > AUGMENT_MAX_SIDE:
+        raise WsdlError(f"{name}: images {tuple(images.shape)}: side lengths 1..{AUGMENT_MAX_SIDE}")
+    _mix_tensor(name, labels, "labels", 3, torch.int64, (B, H, W))
+    _mix_tensor(name, partner, "partner", 1, torch.int32, (B,))
+    inputs = [(images, "images"), (labels, "labels"), (partner, "partner")]
+    specs = {"images": (tuple(images.shape), torch.float32), "labels": ((B, H, W), torch.int64)}
+    if pixel_weight is not None:
+        _mix_tensor(name, pixel_weight, "pixel_weight", 3, torch.float32, (B, H, W))
+        inputs.append((pixel_weight, "pixel_weight"))
+        specs["pixel_weight"] = ((B, H, W), torch.float32)
+    if scores is not None:
+        _mix_tensor(name, scores, "scores", 4, torch.float32)
+        if scores.shape[1] > MIX_MAX_CLASSES:
+            raise WsdlError(f"{name}: scores {tuple(scores.shape)}: C = {scores.shape[1]}, at most {MIX_MAX_CLASSES} channels")
+        if (scores.shape[0],) + tuple(scores.shape[2:]) != (B, H, W):
+            raise WsdlError(f"{name}: scores {tuple(scores.shape)} must be (B,Cs,H,W) of the images' {(B, H, W)}")
+        inputs.append((scores, "scores"))
+        specs["scores"] = (tuple(scores.shape), torch.float32)
+    sources = {"box": (("boxes", boxes),), "class": (("class_labels", class_labels), ("sel", sel)), "mask": (("mask", mask),)}
+    for k, args in sources.items():
+        for what, t in args:
+            if k == kind and t is None:
+                raise WsdlError(f"{name}: kind={kind!r} needs {what}" + (" (ops.mix_class_select)" if what == "sel" else ""))
+            if k != kind and t is not None:
+                raise WsdlError(f"{name}: {what} belongs to kind={k!r}, not to kind={kind!r}")
+    if kind == "box":
+        _mix_tensor(name, boxes, "boxes", 3, torch.int32)
+        if boxes.shape[0] != B or boxes.shape[2] != 4:
+            raise WsdlError(f"{name}: boxes {tuple(boxes.shape)} must be (B,R,4) with B = {B}: rows (y0, x0, y1, x1)")
+        if boxes.shape[1] > MIX_MAX_BOXES:
+            raise WsdlError(f"{name}: boxes {tuple(boxes.shape)}: R = {boxes.shape[1]}, at most {MIX_MAX_BOXES} boxes per item")
+        inputs.append((boxes, "boxes"))
+    elif kind == "class":
+        _mix_tensor(name, class_labels, "class_labels", 3, torch.int64, (B, H, W))
+        _mix_tensor(name, sel, "sel", 1, torch.int64, (B,))
+        inputs += [(class_labels, "class_labels"), (sel, "sel")]
+    else:
+        _mix_tensor(name, mask, "mask", 3, torch.uint8, (B, H, W))
+        inputs.append((mask, "mask"))
+    if want_mask:
+        specs["mask"] = ((B, H, W), torch.uint8)
+    if want_count:
+        specs["mixed_count"] = ((B,), torch.int64)
+    given = _mix_outs(name, out, _MIX_OUT_KEYS, specs, inputs)
+    _mix_one_device(name, inputs + given)
+
+
+def mix_launches(kind, *, select=False, want_count=False):
+    """What one ``mix_batch`` call of ``kind`` issues, as ``{"kernels": n, "memsets": m}`` (the keys of a launch plan's
+    ``stats``): ONE kernel, plus a memset of the counts with ``want_count``.  ``select=True`` (``kind="class"`` only) adds the
+    ``mix_class_select`` call in front of it: a memset of ``present``, the presence launch and the selection launch."""
+    if kind not in MIX_KINDS:
+        raise WsdlError(f"mix_launches: kind {kind!r}: 'box', 'class' or 'mask'")
+    if select and kind != "class":
+        raise WsdlError(f"mix_launches: select=True belongs to kind='class', not to kind={kind!r}")
+    return {"kernels": 1 + (2 if select else 0), "memsets": (1 if want_count else 0) + (1 if select else 0)}
+
+
+def mix_batch(images, labels, partner, *, kind, boxes=None, class_labels=None, sel=None, mask=None, invert=False, pixel_weight=None,
+              scores=None, want_mask=False, want_count=False, out=None):
+    """CutMix / ClassMix / copy-paste as ONE launch (wsdl_mix_apply): every tensor handed in is mixed by the same binary mask,
+    ``out_T[b,...,y,x] = M[b,y,x] ? T[partner[b],...,y,x] : T[b,...,y,x]``.  Returns a ``MixResult`` named tuple ``(images, labels,
+    pixel_weight, scores, mask, mixed_count)``, None where nothing was asked for.
+
+    Tensors (all on one device): ``images`` float32 (B,Ci,H,W); ``labels`` int64 (B,H,W); optional ``pixel_weight`` float32
+    (B,H,W); optional ``scores`` float32 (B,Cs,H,W), Cs <= 64 (a teacher's logits: the mixed-teacher target).
+    ``partner`` int32 (B,): item b is mixed with item ``partner[b]``; a value outside ``[0, B)`` (``augment.Mix`` draws -1) leaves
+    item b unmixed - its mask is 0 everywhere; the kernel tests the value before it indexes anything.  Self-partners and
+    duplicates are legal.
+
+    The mask ``M[b,y,x]`` in {0,1}, 1 = "take the partner's pixel", by ``kind``:
+      "box"    ``boxes`` int32 (B,R,4), 1 <= R <= 8, rows ``(y0, x0, y1, x1)`` half-open in pixels: M = 1 inside the union of the R
+               boxes; a box with ``y1 <= y0`` or ``x1 <= x0`` contributes nothing; coordinates outside the image clip implicitly,
+               negative ones included.
+      "class"  M = 1 iff ``class_labels[partner[b],y,x]`` (int64 (B,H,W)) is a class of the partner's selected set
+               ``sel[partner[b]]`` (int64 (B,) of 64-bit sets: ``mix_class_select``); a label outside ``[0, C)`` is never selected.
+      "mask"   ``mask`` uint8 (B,H,W): M = ``mask[b] != 0`` (PAMR labels, superpixel-snapped masks ... drive the mix).
+    ``invert=True`` flips M for mixed items only; unmixed items stay unmixed.
+
+    ``want_mask``: M itself, uint8 (B,H,W).  ``want_count``: ``mixed_count`` int64 (B,), the pixels with M = 1 (a memset, then one
+    integer atomic per workgroup: exact and independent of order).  ``out``: a dict of dense tensors to fill under the results'
+    names; an entry that shares memory with an input is refused (item b reads item ``partner[b]``: in-place use is a race).
+
+    The outputs are bit copies of the inputs, NaN payloads included; inputs are never modified; non-dense inputs are made dense
+    first (a copy by the tensor library).  Where W is a multiple of 4 and every base is 16-byte aligned a lane moves four pixels
+    with 16-byte accesses, otherwise one.  No host read and every parameter in device memory: a launch plan can hold the call
+    (``mix_launches``); two calls give the same bits.  Not differentiable: the results carry no graph."""
+    check_mix_options(images, labels, partner, kind=kind, boxes=boxes, class_labels=class_labels, sel=sel, mask=mask, invert=invert,
+                      pixel_weight=pixel_weight, scores=scores, want_mask=want_mask, want_count=want_count, out=out)
+    dense = lambda t: None if t is None else t.detach().contiguous()          # noqa: E731
+    images, labels, partner, pixel_weight, scores = (dense(t) for t in (images, labels, partner, pixel_weight, scores))
+    boxes, class_labels, sel, mask = (dense(t) for t in (boxes, class_labels, sel, mask))
+    B, _, H, W = images.shape
+    out = out or {}
+
+    def result(key, like=None, shape=None, dtype=None):
+        t = out.get(key)
+        if t is None:
+            t = torch.empty_like(like) if like is not None else torch.empty(shape, dtype=dtype, device=images.device)
+        return t
+    res = {"images": result("images", images), "labels": result("labels", labels)}
+    pairs = [(images, res["images"]), (labels, res["labels"])]
+    for key, t in (("pixel_weight", pixel_weight), ("scores", scores)):
+        res[key] = None
+        if t is not None:
+            res[key] = result(key, t)
+            pairs.append((t, res[key]))
+    res["mask"] = result("mask", shape=(B, H, W), dtype=torch.uint8) if want_mask else None
+    res["mixed_count"] = result("mixed_count", shape=(B,), dtype=torch.int64) if want_count else None
+    arr = (_MixTensor * len(pairs))()
+    for i, (src, dst) in enumerate(pairs):
+        arr[i].src, arr[i].dst = _p(src), _p(dst)
+        arr[i].channels, arr[i].elem_bytes = (src.shape[1] if src.dim() == 4 else 1), src.element_size()
+    check(lib().wsdl_mix_apply(C.cast(arr, C.c_void_p), len(pairs), _p(partner), MIX_KINDS[kind], _p(boxes),
+                               0 if boxes is None else boxes.shape[1], _p(class_labels), _p(sel), _p(mask), int(invert), B, H, W,
+                               _p(res["mask"]), _p(res["mixed_count"]), _stream()))
+    return MixResult(**res)
 
 
 def softmax_channels(x):
