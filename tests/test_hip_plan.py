@@ -198,6 +198,80 @@ def test_weighted_pairwise_losses_through_the_library_are_plannable(dev):
         assert torch.equal(a, b)
 
 
+RAMP = (0.05, 0.1, 0.2, 0.4)          # the extra loss's weight: a new value every second step
+_ramp_refs = {}
+
+
+def _ramp_losses(dev, kind):
+    """kind -> (loss(o, i, w), batches): "library" is plannable (every launch the library's), "torch" is not."""
+    from weaklysuperviseddl_amd import ops
+    from weaklysuperviseddl_amd.TraditionalModel import LocalNormalizedCutLoss
+    g = torch.Generator().manual_seed(33)
+    img = torch.rand(4, 3, 64, 64, generator=g).to(dev)
+    masks = (torch.rand(4, 64, 64, generator=g) > 0.5).long().to(dev)
+    batches = [(img, masks), (img.flip(0).contiguous(), masks.flip(0).contiguous())]
+    if kind == "library":
+        ncut = LocalNormalizedCutLoss(0.1, 5)
+        return (lambda o, i, w: ops.scale_mean(ncut(o, i), w)), batches
+    return (lambda o, i, w: w * (o * o).mean()), batches
+
+
+def _run_ramped(dev, planned, loss, batches, form, weights, steps=8):
+    """``steps`` calls of train_step whose ``extra_loss`` is a NEW function object on every call, holding this call's weight
+    (``weights[i // 2]``) as a default argument ("lambda") or in a closure cell ("factory")."""
+    from weaklysuperviseddl_amd import plan
+    from weaklysuperviseddl_amd.TraditionalModel import train_step
+
+    def make(w):
+        def extra(o, i):
+            return loss(o, i, w)
+        return extra
+
+    old = plan.PLAN_STEP[0]
+    plan.PLAN_STEP[0] = planned
+    try:
+        model, opt = _model_and_opt(dev, 5)
+        torch.manual_seed(1234)
+        losses = []
+        for i in range(steps):
+            w = weights[i // 2]
+            extra = (lambda o, i, w=w: loss(o, i, w)) if form == "lambda" else make(w)
+            losses.append(train_step(model, opt, *batches[i % len(batches)], extra_loss=extra))
+        torch.cuda.synchronize()
+        table = opt.__dict__.get("_wsdl_planned", {})
+        assert len(table) <= 1, "every rebuilt function maps onto one planned step (plan.loss_tag)"
+        return [float(l) for l in losses], _state(model, opt), next(iter(table.values()), None)
+    finally:
+        plan.PLAN_STEP[0] = old
+
+
+@pytest.mark.parametrize("form", ["lambda", "factory"])
+@pytest.mark.parametrize("kind", ["library", "torch"])
+def test_a_ramped_loss_weight_in_a_rebuilt_function_is_not_frozen(dev, kind, form):
+    """``train_step(..., extra_loss=lambda o, i, w=w: ...)`` with ``w`` ramped.  ``plan.loss_tag`` maps every such
+    function onto ONE PlannedTrainStep and the weight goes into the plan's key, so a new weight records a new plan - which must be
+    recorded from THIS call's function (and an eager fallback must run it), not from the one of the call that created the step.
+    Losses and final state equal the eager run's bit for bit; a run that keeps the first weight differs from step 3 on."""
+    loss, batches = _ramp_losses(dev, kind)
+    if kind not in _ramp_refs:          # the two eager references, once per kind (they do not depend on the function's form)
+        _ramp_refs[kind] = (_run_ramped(dev, False, loss, batches, "lambda", RAMP)[:2],
+                            _run_ramped(dev, False, loss, batches, "lambda", RAMP[:1] * 4)[0])
+    (l0, s0), l_stale = _ramp_refs[kind]
+    l1, s1, st = _run_ramped(dev, True, loss, batches, form, RAMP)
+    # the control: freezing the weight at its first value is visible from the third step on (and not before)
+    assert l_stale[:2] == l0[:2] and all(a != b for a, b in zip(l_stale[2:], l0[2:])), (l_stale, l0)
+    assert st is not None
+    if kind == "library":
+        # steps 1-2 warm up; 3 records (w2), 4 replays; 5 / 7 see a new key once (eager), 6 / 8 record it
+        assert st.disabled is None, st.disabled
+        assert st.records == len(RAMP) - 1 and st.replays >= 1, (st.records, st.replays)
+    else:
+        assert st.disabled is not None and "verification failed" in st.disabled and st.replays == 0, (st.disabled, st.replays)
+    assert l1 == l0, ("planned", l1, "eager", l0, "first weight kept", l_stale)
+    for a, b in zip(s0, s1):
+        assert torch.equal(a, b)
+
+
 def test_lovasz_step_poisons_the_recording(dev):
     batches = [_batch(2, 64, dev, 9)]
     m0, o0, l0, _ = _run(dev, False, 4, batches, loss_fn="lovasz_softmax")

@@ -550,6 +550,28 @@ def _publish_amax(t, slot):
     t._wsdl_amax_version = t._version
 
 
+def _publish_camax(t, camax, presplit=None):
+    """Attach producer-published per-channel maxima (and, for a BatchNorm input gradient, its pre-split fp16 rows) to the
+    tensor they describe, with the tensor's version - as ``_publish_amax``: after an in-place modification ``camax_of``
+    answers None and the weight gradient falls back to the per-tensor scale ``amax_of`` measures again."""
+    t._wsdl_camax = camax
+    if presplit is not None:
+        t._wsdl_presplit = presplit
+    t._wsdl_camax_version = t._version
+
+
+def camax_of(t, presplit=False):
+    """The per-channel maxima the tensor's producer published, or None if it carries none or was modified in place since
+    (``y.mul_()``, ``copy_()``: a channel that grew would overflow the fp16 pieces, pre-split rows would hold the old values).
+    ``presplit=True``: the pair (maxima, pre-split rows or None) - the rows are only valid together with the maxima."""
+    c = getattr(t, "_wsdl_camax", None)
+    if c is not None and getattr(t, "_wsdl_camax_version", None) != t._version:
+        c = None
+    if not presplit:
+        return c
+    return c, (getattr(t, "_wsdl_presplit", None) if c is not None else None)
+
+
 def reset_amax_pool(device):
     """Forget the current slot pools of ``device``: the next request allocates (and zeroes) a new one - graph.py brackets a
     capture with it so that the captured step's slots are re-zeroed by every replay."""
@@ -837,12 +859,16 @@ def conv2d_wgrad(x, dy, wshape, stride, pad, dil, out=None, accumulate=False, x_
     training step pass it instead of switching torch's current stream (a ``with torch.cuda.stream()`` costs the host ~20 us,
     61 times per step).  ``x_camax`` / ``dy_camax``: per-channel maxima of the operands (``_wsdl_camax`` of a
     BatchNorm output / input gradient), ``dy_presplit``: dY as the kernel's fp16 rows (``_wsdl_presplit``) - wsdl_conv2d_wgrad_ex."""
+    # maxima / rows that are the operand's OWN attributes are only as good as its version (camax_of): handed over after an
+    # in-place edit they are dropped here, and the operand keeps its (re-measured) per-tensor scale
+    if x_camax is not None and x_camax is getattr(x, "_wsdl_camax", None) and camax_of(x) is None:
+        x_camax = None
+    if dy_camax is not None and dy_camax is getattr(dy, "_wsdl_camax", None):
+        dy_camax, own_rows = camax_of(dy, presplit=True)
+        if dy_presplit is None or dy_presplit is getattr(dy, "_wsdl_presplit", None):
+            dy_presplit = own_rows
     if dy_camax is None:
         dy_presplit = None
-    elif dy_presplit is None:
-        dy_camax_p = getattr(dy, "_wsdl_camax", None)
-        if dy_camax_p is dy_camax:
-            dy_presplit = getattr(dy, "_wsdl_presplit", None)
     if stream is not None and stream != _stream():
         # everything this function would otherwise enqueue on the CURRENT stream (amax passes, densifying copies) must have
         # been resolved by the caller, in front of the wait that orders ``stream`` behind the current one (_wgrad_into)
@@ -955,7 +981,7 @@ def bn_train_fwd(x, gamma, beta, running_mean, running_var, momentum, eps, resid
     if y_amax is not None:
         _publish_amax(out, y_amax)
     if camax is not None:
-        out._wsdl_camax = camax
+        _publish_camax(out, camax)
     return (out, mean, invstd, mask) if want_mask else (out, mean, invstd)
 
 
@@ -1003,9 +1029,7 @@ def bn_train_bwd(x, dy, y, gamma, mean, invstd, relu, want_dres, dgamma_out=None
     if dx_amax is not None:
         _publish_amax(dx, dx_amax)
     if camax is not None:
-        dx._wsdl_camax = camax
-        if presplit is not None:
-            dx._wsdl_presplit = presplit
+        _publish_camax(dx, camax, presplit)
     dx._wsdl_fresh = True
     if dres is not None:
         dres._wsdl_fresh = True
@@ -1071,12 +1095,11 @@ def _wgrad_into(param, x, dconv, wshape, stride, pad, dil, sink, x_amax=None, la
     x_amax = x_amax if x_amax is not None else amax_of(x, split)       # resolved on the MAIN stream (may launch a pass)
     dy_amax = amax_of(dconv, split)
     # per-channel maxima / pre-split rows travel as attributes of the tensors their producers returned
-    dy_camax = getattr(dconv, "_wsdl_camax", None) if split else None
-    dy_presplit = getattr(dconv, "_wsdl_presplit", None) if dy_camax is not None else None
+    dy_camax, dy_presplit = camax_of(dconv, presplit=True) if split else (None, None)
     if not split:
         x_camax = None
     elif x_camax is None:
-        x_camax = getattr(x, "_wsdl_camax", None)
+        x_camax = camax_of(x)
     if x_camax is not None and x_camax.numel() != wshape[1]:
         x_camax = None                  # (a channel slice / concatenation of the tensor that carried it)
     if OVERLAP_WGRAD[0] and not (last and LAST_WGRAD_ON_MAIN[0]):
@@ -1164,7 +1187,7 @@ class _ConvBNAct(torch.autograd.Function):
         ctx.cfg = (stride, pad, dil, relu, tuple(weight.shape), tuple(x.shape), residual is not None)
         ctx.params = (weight, gamma, beta)
         ctx.x_amax = x_amax              # saved tensors come back as new Python objects: keep the scalar explicitly
-        ctx.x_camax = getattr(x, "_wsdl_camax", None)     # ... and the per-channel maxima its producer published
+        ctx.x_camax = camax_of(x)     # ... and the per-channel maxima its producer published
         # the ReLU mask is recomputed from the conv output in the backward unless a residual was added: then the forward
         # kernel wrote it as bits (or, where it cannot - H*W not a multiple of 8 - y is kept and read)
         ctx.save_for_backward(x, conv, y if (relu and residual is not None and rbits is None) else None, gamma, mean, invstd,
@@ -1174,7 +1197,7 @@ class _ConvBNAct(torch.autograd.Function):
             if x_amax is not None:
                 _publish_amax(xv, x_amax)
             if ctx.x_camax is not None:
-                xv._wsdl_camax = ctx.x_camax
+                _publish_camax(xv, ctx.x_camax)
             return y, xv
         return y
 
@@ -1303,13 +1326,13 @@ class _ConvBNBranches(torch.autograd.Function):
         ctx.cfg = ([(b[0], b[1]) for b in branches], wshapes, tuple(x.shape))
         ctx.params = [(w, g, b) for (w, g, b, _rm, _rv) in params]
         ctx.x_amax = x_amax
-        ctx.x_camax = getattr(x, "_wsdl_camax", None)
+        ctx.x_camax = camax_of(x)
         ctx.save_for_backward(*saved)
         xv = x.view_as(x)
         if x_amax is not None:
             _publish_amax(xv, x_amax)
         if ctx.x_camax is not None:
-            xv._wsdl_camax = ctx.x_camax
+            _publish_camax(xv, ctx.x_camax)
         return (*outs, xv)
 
     @staticmethod

@@ -439,4 +439,9 @@ def planned_step_for(model, optimizer, eager, tag):
         if len(table) >= 4:
             table.pop(next(iter(table)))
         st = table[key] = PlannedTrainStep(model, optimizer, eager)
+    else:
+        # ``loss_tag`` maps every inline function with the same code onto this step, so ``eager`` is a NEW closure on each call:
+        # the one that holds this call's loss function.  A recording (or an eager fallback) through the first call's closure
+        # would freeze a ramped loss weight at its first value - the plan's key changes with the weight, its content would not.
+        st.eager = eager
     return st
