@@ -875,6 +875,62 @@ int wsdl_mix_apply(const wsdl_mix_tensor* tensors, int n_tensors, const int32_t*
                    const int64_t* class_labels, const int64_t* sel, const uint8_t* mask, int invert, int B, int H, int W,
                    uint8_t* mask_out, int64_t* count_out, wsdl_stream_t stream);
 
+/* ---- score histograms: grouped histograms with exact counts, threshold sweeps, Otsu, calibration (csrc/score_hist.hip) ----
+ * The reference has no such step: its thresholds are constants.  A TABLE has G groups x (nb + 3) slots over nb + 1 edges (float32,
+ * strictly ascending, finite, in device memory; edges_host is the same nb + 1 values in host memory, which the entry point checks -
+ * nothing is read back from the device).  The slot of a value v is defined by comparisons against the edges alone:
+ *   slot 0: v < edges[0];  slot 1 + k: edges[k] <= v < edges[k + 1];  slot nb + 1: v >= edges[nb] (+inf included);  slot nb + 2: NaN;
+ *   -0.0 compares as 0.  For equally spaced edges the kernel guesses the slot arithmetically and then walks the guess to the slot the
+ *   comparisons define; other edges take a binary search over their copy in LDS.
+ * Limits: nb <= WSDL_HIST_MAX_BINS, G <= WSDL_HIST_MAX_GROUPS, G (nb + 3) <= WSDL_HIST_MAX_SLOTS, B <= 65535, a segment has fewer
+ * than 2^31 pixels.
+ *
+ * wsdl_score_hist: scores (B,HW) float32, groups (B,HW) int64 or NULL (all group 0); a pixel whose group is outside [0, G) is not
+ * counted.  counts (S,G,nb+3) int64 with S = B (per_image = 1) or 1: zeroed by a memset in front of the launch, then counts[s,g,slot]
+ * = the number of pixels.  sums (same shape, may be NULL): the sum of (long long)(v * 16777216.0f) - an exact product, a truncating
+ * conversion - over the pixels of the slots 1 .. nb, 0 elsewhere; with sums every edge must lie in [-128, 128].  One launch, grid
+ * (chunks, images) of about 1024 workgroups: the table is privatised in LDS (32-bit counters, 64-bit sums; one copy per wave up to
+ * 1040 slots, else one per workgroup), the per-pixel add is aggregated over the lanes of a wave that share a slot, and a workgroup
+ * flushes its non-zero slots with 64-bit integer atomics.  Four pixels per lane with 16-byte loads where HW % 4 == 0 and scores and
+ * groups are 16-byte aligned, else one.  An output that overlaps an input or the other output is refused.
+ *
+ * wsdl_confidence_hist: logits (B,C,H,W) float32, C <= WSDL_CONFIDENCE_MAX_CLASSES, labels (B,H,W) int64.  Per pixel pred = the
+ * first class of largest logit and conf = float(1 / sum_c exp(double(l_c) - double(l_pred))), NaN where a logit is not finite;
+ * a pixel with label != ignore_index is counted as wsdl_score_hist counts the value conf in group (pred == label) of a table with
+ * G = 2 (sums as there).  conf_out (B,H,W) float32 and pred_out (B,H,W) int64 may be NULL; they are written at every pixel.
+ *
+ * wsdl_hist_curves: counts (S,2,nb+3), group 1 the positives -> curves (S,nb+1,4) int64 = TP FP FN TN of the prediction
+ * v >= edges[k], k = 0 .. nb: the slots k + 1 .. nb + 1 are predicted positive, slot 0 and the NaN slot never.  One workgroup per
+ * segment, suffix sums.
+ *
+ * wsdl_otsu: per segment over h_i = the sum over the groups of group_mask of counts[s,g,1+i], i = 0 .. nb - 1; N = sum h_i,
+ * S = sum i h_i; for k = 0 .. nb - 2: w0 = sum_{i<=k} h_i, w1 = N - w0, s0 = sum_{i<=k} i h_i, s1 = S - s0, D = s0 w1 - s1 w0 (int64),
+ * q(k) = (double(D) * double(D)) / double(w0 w1) where w0 w1 > 0.  k_out = the first maximum of q, threshold_out = edges[k + 1],
+ * q_out = q(k); with fewer than two occupied bins k_out = -1, threshold_out = fallback, q_out = 0.  segment_pixels = the largest
+ * N the caller vouches for (0: no claim), refused above 2^21, which keeps D below 2^53; a segment that holds more all the same gets
+ * k_out = -2 and NaN.  One workgroup per segment.
+ *
+ * wsdl_threshold_images: mask[b,p] (uint8) = scores[b,p] >= thresh[b] && (!positive_only || scores[b,p] > 0); thresh (B) float32 in
+ * device memory (NaN: an empty mask).  count (B) int64, may be NULL: the number of set pixels, zeroed by a memset in front of the
+ * launch, one integer atomic per workgroup.
+ *
+ * All five: integer atomics only, so two calls give the same bits; no host read, every parameter by value or in device memory: a
+ * launch plan can hold the calls. */
+#define WSDL_HIST_MAX_BINS 1024
+#define WSDL_HIST_MAX_GROUPS 32
+#define WSDL_HIST_MAX_SLOTS 4096
+#define WSDL_CONFIDENCE_MAX_CLASSES 64
+int wsdl_score_hist(const float* scores, const int64_t* groups, const float* edges, const float* edges_host, int B, long long HW, int G,
+                    int nb, int per_image, int64_t* counts, int64_t* sums, wsdl_stream_t stream);
+int wsdl_confidence_hist(const float* logits, const int64_t* labels, const float* edges, const float* edges_host, int B, int C, int H, int W,
+                         long long ignore_index, int nb, int per_image, int64_t* counts, int64_t* sums, float* conf_out, int64_t* pred_out,
+                         wsdl_stream_t stream);
+int wsdl_hist_curves(const int64_t* counts, int S, int nb, int64_t* curves, wsdl_stream_t stream);
+int wsdl_otsu(const int64_t* counts, const float* edges, int S, int G, int nb, unsigned group_mask, float fallback, long long segment_pixels,
+              int32_t* k_out, float* threshold_out, double* q_out, wsdl_stream_t stream);
+int wsdl_threshold_images(const float* scores, const float* thresh, int B, long long HW, int positive_only, uint8_t* mask, int64_t* count,
+                          wsdl_stream_t stream);
+
 /* ---- pixel mining: selecting pixels by their loss without a host read (csrc/pixel_mining.hip) -
  * wsdl_kth_value: x holds `segments` runs of n_per_segment floats.  The candidates of segment s are the x[s*n + i] that are
  * not NaN and, when `valid` (one byte per element) is given, have valid[s*n + i] != 0; n_valid[s] receives their number n.

@@ -35,6 +35,20 @@ def compute_metrics(pred_mask, gt_mask):
     return iou, accuracy, pred_bin, gt_bin
 
 
+def saliency_curve_metrics(pred, trimaps, bins=256):
+    """The two numbers saliency papers report, for a batch of ``norm_pred`` maps ``pred`` (B,H,W) float32 in [0, 1] on the device
+    against ``(trimaps == 1)`` (B,H,W): the maximum F-measure over ``bins + 1`` thresholds (beta^2 = 0.3, from the pooled
+    precision and recall) and the mean absolute error, with the threshold that reaches the maximum.  One grouped histogram with
+    sums and one curve launch on the device (``ops.score_histogram``, ``ops.threshold_curves``), the rest on the host copies of the
+    counts.  Returns ``{"max_f", "mae", "best_threshold"}``; the MAE uses the maps' values truncated to 2^-24."""
+    pred = pred.reshape((-1,) + tuple(pred.shape[-2:]))
+    gt = (trimaps.reshape(pred.shape) == 1).long()
+    counts, sums = ops.score_histogram(pred, gt, bins=bins, range=(0.0, 1.0), num_groups=2, per_image=False, want_sums=True)
+    curves = ops.threshold_curves(counts).cpu().numpy()
+    f, k = ops.max_fbeta(curves, beta2=0.3)
+    return {"max_f": f, "mae": ops.mae_from_sums(counts, sums), "best_threshold": float(ops.uniform_edges(0.0, 1.0, bins)[k])}
+
+
 def run_inference(model_path='./Weights/basnet.pth', dataset_root='./OxfordIIITPetDataset/oxford-iiit-pet',
                   output_folder='./basnet_outputs', n_images=10, batch_size=10, device='cuda', net=None, verbose=True):
     """-> (per-image results [(name, iou, acc)], mean IoU, mean pixel accuracy); writes ``{name}_saliency.png``."""

@@ -379,6 +379,67 @@ def evaluate_layercam_on_test_set(layercam_gen, test_loader, alpha=1.0, cam_thre
     return out
 
 
+def sweep_cam_thresholds(layercam_gen, test_loader, alpha=1.0, thresholds=None, *, device="cuda", max_images=11, first_only=True,
+                         log=print):
+    """What ``evaluate_layercam_on_test_set`` reports, at EVERY threshold of ``thresholds`` from ONE LayerCAM pass (the reference
+    evaluates one constant, 0.3; PSA and IRN report CAM quality at the best threshold).  ``thresholds``: strictly ascending float32
+    values, at least two, positive (at a threshold <= 0 the epilogue's ``v > 0`` rule and ``v >= t`` part); the default is
+    ``ops.uniform_edges(0, 1, 256)[1:]``.  Per loader batch: ``generate_batch`` without ``thresh``, the CAM nearest-resized to the
+    trimap's size by the index rule of ``evaluate_layercam_on_test_set``, one ``ops.score_histogram`` against ``(trimap == 1)`` with
+    the thresholds as edges, one ``ops.threshold_curves`` and one ``ops.otsu_threshold`` over the same bins; the counts are copied to
+    the host once, after the loop.  ``first_only`` (the first image of each batch) and ``max_images=11`` visit exactly the images
+    ``evaluate_layercam_on_test_set`` visits, and at a threshold that equals its ``cam_thresh`` as float32 the two means below are
+    its numbers exactly.  Returns a dict: ``thresholds``; ``mean_iou`` / ``mean_acc`` - per threshold the mean over the images of
+    ``compute_iou_and_acc``'s two expressions; ``dataset_iou`` - per threshold the IoU of the pooled counts (an empty union gives
+    1); ``best_mean_iou`` / ``best_dataset_iou`` - ``(threshold, value)`` of the first maximum of each; ``otsu_thresholds`` - one
+    per image, over the same bins (the threshold nearest 0.3 where an image has fewer than two occupied bins); ``curves`` - the
+    int64 (images, thresholds, 4) TP FP FN TN."""
+    import numpy as np
+    th = ops.uniform_edges(0.0, 1.0, 256)[1:] if thresholds is None else np.ascontiguousarray(np.asarray(thresholds, dtype=np.float32))
+    if th.ndim != 1 or th.shape[0] < 2:
+        raise ValueError("sweep_cam_thresholds: thresholds must be at least two values")
+    edges = torch.from_numpy(th).to(device)
+    fallback = float(th[int(np.argmin(np.abs(th.astype(np.float64) - 0.3)))])
+    curve_rows, otsu_rows, seen = [], [], 0
+    for i, (img, (label, true_mask)) in enumerate(test_loader):
+        take = 1 if first_only else img.shape[0]
+        x = img[:take].to(device)
+        tm = true_mask[:take].to(device)
+        tm = (tm.reshape((take,) + tuple(tm.shape[-2:])) == 1).long()
+        cls = torch.as_tensor([int(v.item() if torch.is_tensor(v) else v) for v in label[:take]], device=device)
+        cam = layercam_gen.generate_batch(x, float(alpha), cls)
+        if cam.shape[-2:] != tm.shape[-2:]:
+            # F.interpolate(mode='nearest'): source index = floor(dst * in / out)
+            ih = torch.arange(tm.shape[-2], device=device) * cam.shape[-2] // tm.shape[-2]
+            iw = torch.arange(tm.shape[-1], device=device) * cam.shape[-1] // tm.shape[-1]
+            cam = cam[:, ih][:, :, iw]
+        counts = ops.score_histogram(cam, tm, edges=edges, num_groups=2)
+        curve_rows.append(ops.threshold_curves(counts))
+        otsu_rows.append(ops.otsu_threshold(counts, edges, fallback=fallback)[1])
+        seen += 1
+        if max_images is not None and seen >= max_images:
+            break
+    curves = torch.cat(curve_rows).cpu().numpy()                                # the one copy to the host
+    otsu = torch.cat(otsu_rows).cpu().numpy()
+    iou = ops.iou_curve_from_counts(curves, eps=1e-8)                           # compute_iou_and_acc: inter / (union + 1e-8)
+    acc = ops.accuracy_curve_from_counts(curves)
+    mean_iou, mean_acc = iou[0].copy(), acc[0].copy()
+    for r_iou, r_acc in zip(iou[1:], acc[1:]):                                  # sum(ious) / len(ious), image by image
+        mean_iou += r_iou
+        mean_acc += r_acc
+    mean_iou, mean_acc = mean_iou / len(iou), mean_acc / len(acc)
+    dataset_iou = ops.iou_curve_from_counts(curves.sum(axis=0))
+    k_mean, k_data = int(np.argmax(mean_iou)), int(np.argmax(dataset_iou))
+    out = {"thresholds": th, "mean_iou": mean_iou, "mean_acc": mean_acc, "dataset_iou": dataset_iou,
+           "best_mean_iou": (float(th[k_mean]), float(mean_iou[k_mean])), "best_dataset_iou": (float(th[k_data]), float(dataset_iou[k_data])),
+           "otsu_thresholds": otsu, "curves": curves}
+    if log:
+        log("\n Threshold sweep of CAMs on test set:")
+        log(f" - best mean-of-images IoU {out['best_mean_iou'][1]:.4f} at {out['best_mean_iou'][0]:.4f} | "
+            f"best pooled IoU {out['best_dataset_iou'][1]:.4f} at {out['best_dataset_iou'][0]:.4f}")
+    return out
+
+
 class CAMGenerator:
     """Classic fc-weight CAM (reference TraditionalModel/AlternatingDirectionCutLoss.py:320-403).
 

@@ -23,6 +23,8 @@ Mirrors reference TraditionalModel/PsuedoMasks.py: ``keep_largest`` (:15-21) and
     ``BoundaryNet`` (``ops.edge_random_walk``; off by default);
   * ``generate_prototype_pseudo_masks``: optional prototype CAM - the softmax similarity of every pixel's features to the image's own foreground and
     background prototypes, pooled over the CAM's sure regions (``prototype_cam``; off by default);
+  * ``generate_adaptive_pseudo_masks``: optional threshold per image - Otsu's, from a histogram of the map on the device - in place
+    of ``cam_thresh`` (``adaptive_masks``; off by default);
   * ``keep_largest(mask)`` is the reference's host function (skimage there; scipy.ndimage here - 8-connectivity, raster
     label order, first label wins area ties, empty mask returned unchanged).  ``generate_pseudo_masks`` itself labels
     the whole batch on the device (``keep_largest_batched`` -> ``ops.keep_largest_batched``, one workgroup per mask, the
@@ -212,11 +214,53 @@ def generate_prototype_pseudo_masks(loader, layercam_gen, prototype, **kwargs):
     return _generate_pseudo_masks(loader, layercam_gen, prototype=prototype, **kwargs)
 
 
+def _adaptive_options(adaptive):
+    """The ``adaptive`` dict of ``generate_adaptive_pseudo_masks`` with its defaults; ValueError / WsdlError for what it cannot be."""
+    if not isinstance(adaptive, dict) or set(adaptive) - {"method", "bins", "floor", "ceil"}:
+        raise ValueError("generate_adaptive_pseudo_masks: adaptive is a dict of method, bins, floor, ceil")
+    opts = dict(method="otsu", bins=256, floor=0.0, ceil=1.0)
+    opts.update(adaptive)
+    if opts["method"] != "otsu":
+        raise ValueError(f"generate_adaptive_pseudo_masks: method {opts['method']!r}: 'otsu' is the one there is")
+    if any(isinstance(opts[k], bool) or not isinstance(opts[k], (int, float)) for k in ("floor", "ceil")) or not opts["floor"] <= opts["ceil"]:
+        raise ValueError(f"generate_adaptive_pseudo_masks: floor {opts['floor']!r} and ceil {opts['ceil']!r} must be numbers, floor <= ceil")
+    ops.uniform_edges(0.0, 1.0, opts["bins"])                      # (refuses the bins it cannot have)
+    return opts
+
+
+def adaptive_masks(score_map, fallback, method="otsu", bins=256, floor=0.0, ceil=1.0):
+    """uint8 masks of a score map (B,H,W) in [0, 1] cut at a threshold of its own per image: Otsu's threshold over ``bins`` uniform
+    bins of [0, 1) (``ops.score_histogram`` + ``ops.otsu_threshold``; ``fallback`` for an image with fewer than two occupied bins),
+    clamped to ``[floor, ceil]``, applied by ``ops.threshold_per_image(positive_only=True)``: ``v >= t and v > 0``.  No host read."""
+    s = score_map.detach().float().contiguous()
+    counts = ops.score_histogram(s, bins=bins, range=(0.0, 1.0))
+    _k, t, _q = ops.otsu_threshold(counts, ops.uniform_edges(0.0, 1.0, bins, s.device), fallback=float(fallback))
+    return ops.threshold_per_image(s, t.clamp(float(floor), float(ceil)), positive_only=True)
+
+
+def generate_adaptive_pseudo_masks(loader, layercam_gen, adaptive, **kwargs):
+    """``generate_pseudo_masks(loader, layercam_gen, **kwargs)`` with a threshold per image.  (A function of its own: the positional
+    signature of ``generate_pseudo_masks`` is pinned.)  ``adaptive``: None (bit for bit ``generate_pseudo_masks``) or
+    ``dict(method="otsu", bins=256, floor=0.0, ceil=1.0)`` - every ``>= cam_thresh`` of the pipeline, on the raw CAM as on the
+    ``pamr`` / ``superpixels`` / ``affinity`` / ``boundary`` maps, becomes that map's own Otsu threshold per image
+    (``adaptive_masks``), clamped to ``[floor, ceil]``; ``cam_thresh`` is the fallback for an image with fewer than two occupied
+    bins; ``keep_largest`` follows as before.  The results are left where ``generate_pseudo_masks`` leaves them."""
+    return _generate_pseudo_masks(loader, layercam_gen, adaptive=adaptive, **kwargs)
+
+
+def generate_adaptive_prototype_pseudo_masks(loader, layercam_gen, prototype, adaptive, **kwargs):
+    """``generate_prototype_pseudo_masks`` with the per-image threshold of ``generate_adaptive_pseudo_masks`` on the prototype CAM."""
+    return _generate_pseudo_masks(loader, layercam_gen, prototype=prototype, adaptive=adaptive, **kwargs)
+
+
 def _generate_pseudo_masks(loader, layercam_gen, cam_thresh=0.3, alpha=1.0, keep_largest_masks=True, run_id="default",
                            out_root="/content", max_images=500, write_png=True, device="cuda", rank=0, world=1, keep_images=False,
                            streams=3, keep_on_device=False, device_batch=0, pamr=None, superpixels=None, affinity=None, boundary=None,
-                           multiscale=None, prototype=None):
-    """The body of ``generate_pseudo_masks`` / ``generate_prototype_pseudo_masks`` (their docstrings)."""
+                           multiscale=None, prototype=None, adaptive=None):
+    """The body of ``generate_pseudo_masks`` / ``generate_prototype_pseudo_masks`` / ``generate_adaptive_pseudo_masks`` (their
+    docstrings)."""
+    if adaptive is not None:
+        adaptive = _adaptive_options(adaptive)
     if prototype is not None:
         if pamr is not None or superpixels is not None or affinity is not None or boundary is not None:
             raise ValueError("generate_prototype_pseudo_masks: prototype cannot be combined with pamr=, superpixels=, affinity= or boundary=")
@@ -274,15 +318,27 @@ def _generate_pseudo_masks(loader, layercam_gen, cam_thresh=0.3, alpha=1.0, keep
         else:
             outs = [layercam_gen.generate_batch(g[1], alpha=alpha, class_idx=g[2], thresh=cam_thresh) for g in group]
         for (imgs, imgs_d, _l, first_id, take), (cam, m) in zip(group, outs):
-            if pamr is not None:
+            if adaptive is not None:                                 # the same maps, each cut at its own threshold per image
+                if pamr is not None:
+                    cam = ops.pamr(imgs_d, cam[:, None], **pamr)[:, 0]
+                elif superpixels is not None:
+                    cam = superpixel_cam(imgs_d, cam, **superpixels)
+                elif affinity is not None:
+                    cam = affinity_cam(imgs_d, cam, **affinity)
+                elif boundary is not None:
+                    cam = boundary_cam(imgs_d, cam, **boundary)
+                elif prototype is not None:
+                    cam = prototype_cam(imgs_d, cam, **prototype)
+                m = adaptive_masks(cam, cam_thresh, **adaptive)
+            elif pamr is not None:
                 m = ops.pamr_labels(ops.pamr(imgs_d, cam[:, None], **pamr), thresh=cam_thresh).to(torch.uint8)
-            if superpixels is not None:
+            elif superpixels is not None:
                 m = (superpixel_cam(imgs_d, cam, **superpixels) >= cam_thresh).to(torch.uint8)
-            if affinity is not None:
+            elif affinity is not None:
                 m = (affinity_cam(imgs_d, cam, **affinity) >= cam_thresh).to(torch.uint8)
-            if boundary is not None:
+            elif boundary is not None:
                 m = (boundary_cam(imgs_d, cam, **boundary) >= cam_thresh).to(torch.uint8)
-            if prototype is not None:
+            elif prototype is not None:
                 m = (prototype_cam(imgs_d, cam, **prototype) >= cam_thresh).to(torch.uint8)
             if keep_largest_masks:
                 m = keep_largest_batched(m)

@@ -637,6 +637,45 @@ def evaluate_model(model, loader, device="cuda", binarize="notebook", *, scales=
 
 
 @torch.no_grad()
+def evaluate_calibration(model, loader, device="cuda", binarize="notebook", bins=15):
+    """Whether the model's confidence means what it says, over the images ``evaluate_model`` scores - the first of each batch, the
+    same ground-truth rule (``binarize``), the logits nearest-resized to the ground truth's size by its index rule: the softmax
+    maximum of every pixel is binned over ``bins`` uniform bins of [0, 1] by whether the arg-max is right
+    (``ops.confidence_histogram``, one launch per image); the tables are added on the device and copied to the host once, after
+    the loop.  Returns a dict: ``ece`` - the expected calibration error; ``accuracy`` / ``confidence`` / ``count`` - the
+    reliability curve, one entry per bin (NaN where a bin is empty); ``tau_0.9`` / ``tau_0.95`` - the smallest confidence edge at
+    and above which 90 % / 95 % of the pixels are right (``ops.tau_for_precision``; None if there is none): what ``tau`` of
+    ``teacher_targets`` would have to be for that precision; ``counts`` / ``sums`` - the pooled tables."""
+    model.eval()
+    total = None
+    for img, (_label, true_mask) in loader:
+        x = img[0].to(device).unsqueeze(0)
+        tm = true_mask[0].to(device).clone()
+        if binarize == "notebook":
+            tm[tm == 2] = 1
+            tm = 1 - tm
+        elif binarize == "modular":
+            tm = (tm == 1).long()
+        else:
+            raise ValueError(binarize)
+        tm = tm.reshape(tm.shape[-2:]).long()
+        out = model(x)["out"]
+        if out.shape[-2:] != tm.shape:
+            idx_h = (torch.arange(tm.shape[-2], device=device) * out.shape[-2] // tm.shape[-2])
+            idx_w = (torch.arange(tm.shape[-1], device=device) * out.shape[-1] // tm.shape[-1])
+            out = out[:, :, idx_h][:, :, :, idx_w]
+        tables = torch.stack(ops.confidence_histogram(out.contiguous(), tm[None].contiguous(), bins=bins, per_image=False))
+        total = tables if total is None else total + tables
+    if total is None:
+        raise ValueError("evaluate_calibration: the loader is empty")
+    counts, sums = total.cpu().numpy()                                     # the one copy to the host
+    ece, acc, conf, cnt = ops.ece_from_counts(counts, sums)
+    edges = ops.uniform_edges(0.0, 1.0, bins)
+    return {"ece": ece, "accuracy": acc, "confidence": conf, "count": cnt, "tau_0.9": ops.tau_for_precision(counts, edges, 0.9),
+            "tau_0.95": ops.tau_for_precision(counts, edges, 0.95), "counts": counts, "sums": sums}
+
+
+@torch.no_grad()
 def evaluate_boundary_iou(model, loader, device="cuda", binarize="notebook", ratio=0.02):
     """Mean Boundary IoU (Cheng et al., CVPR 2021; ``ops.boundary_iou``) of the foreground over the images ``evaluate_model``
     scores - the first of each batch, the same ground-truth rule (``binarize``) and the same nearest resize of the argmax -

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libwsdl_hip.so")
 ARCH = "gfx950"
-SOURCES = ["common.hip", "plan.hip", "conv_igemm.hip", "norm_pool.hip", "resample_loss.hip", "layercam_optim.hip", "lovasz_seg.hip", "components.hip", "crf.hip", "basnet.hip", "seg_metrics.hip", "pil_resize.hip", "augment.hip", "flat_optim.hip", "pixel_mining.hip", "pamr.hip", "edt.hip", "boundary_loss.hip", "overlap_loss.hip", "components_grid.hip", "slic.hip", "affinity.hip", "boundary_affinity.hip", "group_norm.hip", "multiscale.hip", "prototype.hip", "ema.hip", "consistency.hip", "mix.hip"]
+SOURCES = ["common.hip", "plan.hip", "conv_igemm.hip", "norm_pool.hip", "resample_loss.hip", "layercam_optim.hip", "lovasz_seg.hip", "components.hip", "crf.hip", "basnet.hip", "seg_metrics.hip", "pil_resize.hip", "augment.hip", "flat_optim.hip", "pixel_mining.hip", "pamr.hip", "edt.hip", "boundary_loss.hip", "overlap_loss.hip", "components_grid.hip", "slic.hip", "affinity.hip", "boundary_affinity.hip", "group_norm.hip", "multiscale.hip", "prototype.hip", "ema.hip", "consistency.hip", "mix.hip", "score_hist.hip"]
 FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 
 

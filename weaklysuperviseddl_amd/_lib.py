@@ -122,6 +122,11 @@ SIGNATURES = {
     "wsdl_consistency_fwd_bwd": (_i, [_vp] * 5 + [_i] * 10 + [_vp] * 6 + [_sz, _vp]),
     "wsdl_mix_class_select": (_i, [_vp, _vp, _i, _i, _i, _i, _u64, _vp, _vp, _vp]),
     "wsdl_mix_apply": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "wsdl_score_hist": (_i, [_vp, _vp, _vp, _vp, _i, _ll, _i, _i, _i, _vp, _vp, _vp]),
+    "wsdl_confidence_hist": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "wsdl_hist_curves": (_i, [_vp, _i, _i, _vp, _vp]),
+    "wsdl_otsu": (_i, [_vp, _vp, _i, _i, _i, C.c_uint, _f, _ll, _vp, _vp, _vp, _vp]),
+    "wsdl_threshold_images": (_i, [_vp, _vp, _i, _ll, _i, _vp, _vp, _vp]),
     "wsdl_kth_workspace": (_sz, [_i]),
     "wsdl_kth_value": (_i, [_vp, _vp, _ll, _i, _i, _ll, C.c_double, _vp, _vp, _vp, _sz, _vp]),
     "wsdl_mining_valid": (_i, [_vp, _ll, _vp, _vp, _ll, _vp]),

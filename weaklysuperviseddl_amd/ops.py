@@ -5461,6 +5461,413 @@ def mix_batch(images, labels, partner, *, kind, boxes=None, class_labels=None, s
     return MixResult(**res)
 
 
+# ---- score histograms: grouped histograms with exact counts, threshold sweeps, Otsu, calibration (csrc/score_hist.hip) -----------
+HIST_MAX_BINS = 1024                                # WSDL_HIST_MAX_BINS
+HIST_MAX_GROUPS = 32                                # WSDL_HIST_MAX_GROUPS
+HIST_MAX_SLOTS = 4096                               # WSDL_HIST_MAX_SLOTS
+CONFIDENCE_MAX_CLASSES = 64                         # WSDL_CONFIDENCE_MAX_CLASSES
+OTSU_MAX_PIXELS = 1 << 21
+HIST_SUM_SCALE = 16777216.0                         # the fixed point of ``sums``: 2^24
+_EDGES_CACHE = {}
+
+
+def _int_in(v, name, what, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+        raise WsdlError(f"{name}: {what} {v!r} must be an int in [{lo}, {hi}]")
+    return int(v)
+
+
+def uniform_edges(lo, hi, bins, device=None):
+    """``bins + 1`` equally spaced float32 edges from ``lo`` to ``hi``: ``np.linspace`` in float64, rounded once to float32.  On
+    ``device`` (cached per (lo, hi, bins, device): a second call costs no copy) or, with ``device=None``, as a numpy array."""
+    bins = _int_in(bins, "uniform_edges", "bins", 1, HIST_MAX_BINS)
+    if not all(isinstance(v, (int, float)) and not isinstance(v, bool) and np.isfinite(v) for v in (lo, hi)) or not lo < hi:
+        raise WsdlError(f"uniform_edges: range ({lo!r}, {hi!r}) must be two finite numbers, lo < hi")
+    host = np.linspace(float(lo), float(hi), bins + 1, dtype=np.float64).astype(np.float32)
+    if device is None:
+        return host
+    key = (float(lo), float(hi), bins, str(torch.device(device)))
+    t = _EDGES_CACHE.get(key)
+    if t is None:
+        t = torch.from_numpy(host).to(device)
+        t._wsdl_edges_host = (t._version, host)
+        _EDGES_CACHE[key] = t
+    return t
+
+
+def _edges_host(edges):
+    """The float32 host copy of an edges tensor; read from the device once per tensor and version."""
+    tag = getattr(edges, "_wsdl_edges_host", None)
+    if tag is not None and tag[0] == edges._version:
+        return tag[1]
+    host = np.ascontiguousarray(edges.detach().cpu().numpy())
+    edges._wsdl_edges_host = (edges._version, host)
+    return host
+
+
+def check_score_hist_options(scores=None, groups=None, *, edges=None, bins=256, range=(0.0, 1.0), num_groups=1, per_image=True,
+                             want_sums=False, out=None, counts=None, sums=None, curves=False, otsu_groups=None, fallback=0.5,
+                             segment_pixels=0, thresh=None, logits=None, labels=None, ignore_index=-100, extra_outs=(),
+                             name="score_histogram"):
+    """Host-side validation shared by ``score_histogram``, ``threshold_curves``, ``otsu_threshold``, ``threshold_per_image`` and
+    ``confidence_histogram``, before any device call; returns ``(G, nb, host copy of the edges or None)``.  WsdlError for:
+    ``scores`` not a float32 tensor of rank >= 2 / with an empty dimension, ``groups`` not an int64 tensor of its shape; ``edges``
+    not a one-dimensional float32 tensor of 2..1025 values, not finite or not strictly ascending, outside [-128, 128] with
+    ``want_sums``; ``bins`` / ``range`` / ``num_groups`` outside the table limits (1024 bins, 32 groups, 4096 slots); a segment of
+    2^31 pixels or more; ``counts`` / ``sums`` not dense int64 (S, G, nb + 3) tensors, ``G != 2`` where curves are asked for, an
+    Otsu group outside [0, G), a non-finite ``fallback`` or an Otsu segment of more than 2^21 pixels; ``thresh`` neither a number nor a float32 (B,) tensor; ``logits`` /
+    ``labels`` of the wrong rank, type, size or more than 64 classes; an output (``out`` entries, ``extra_outs``) that shares memory
+    with an input or another output.  The place comes last: everything above is refused without a device."""
+    tensors, inputs = [], []
+    B = None
+
+    def tensor(t, what, dtype, rank=None, min_rank=None, shape=None):
+        if not torch.is_tensor(t):
+            raise WsdlError(f"{name}: {what} must be a tensor")
+        if rank is not None and t.dim() != rank or min_rank is not None and t.dim() < min_rank:
+            raise WsdlError(f"{name}: {what} {tuple(t.shape)} must have rank {rank if rank is not None else '>= %d' % min_rank}")
+        if t.dtype != dtype:
+            raise WsdlError(f"{name}: {what} must be {dtype}, got {t.dtype}")
+        if t.numel() == 0:
+            raise WsdlError(f"{name}: {what} {tuple(t.shape)} has an empty dimension")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise WsdlError(f"{name}: {what} {tuple(t.shape)} must be {tuple(shape)}")
+        tensors.append((t, what))
+
+    if not isinstance(per_image, (bool, np.bool_)) or not isinstance(want_sums, (bool, np.bool_)):
+        raise WsdlError(f"{name}: per_image and want_sums must be bools")
+    seg = None
+    if scores is not None:
+        tensor(scores, "scores", torch.float32, min_rank=2)
+        inputs.append((scores, "scores"))
+        B = scores.shape[0]
+        if groups is not None:
+            tensor(groups, "groups", torch.int64, shape=scores.shape)
+            inputs.append((groups, "groups"))
+        seg = scores.numel() // B if per_image else scores.numel()
+    if logits is not None:
+        tensor(logits, "logits", torch.float32, rank=4)
+        B = logits.shape[0]
+        if logits.shape[1] > CONFIDENCE_MAX_CLASSES:
+            raise WsdlError(f"{name}: logits {tuple(logits.shape)}: at most {CONFIDENCE_MAX_CLASSES} classes")
+        tensor(labels, "labels", torch.int64, shape=(B,) + tuple(logits.shape[2:]))
+        if isinstance(ignore_index, bool) or not isinstance(ignore_index, int):
+            raise WsdlError(f"{name}: ignore_index {ignore_index!r} must be an int")
+        inputs += [(logits, "logits"), (labels, "labels")]
+        seg = labels.numel() // B if per_image else labels.numel()
+    if B is not None and B > 65535:
+        raise WsdlError(f"{name}: {B} images, at most 65535")
+    if seg is not None and seg >= 1 << 31:
+        raise WsdlError(f"{name}: a segment of {seg} pixels, fewer than 2^31 are supported")
+    host = None
+    if edges is not None:
+        tensor(edges, "edges", torch.float32, rank=1)
+        inputs.append((edges, "edges"))
+        nb = edges.numel() - 1
+        if not 1 <= nb <= HIST_MAX_BINS:
+            raise WsdlError(f"{name}: {edges.numel()} edges, 2..{HIST_MAX_BINS + 1} are supported")
+        host = _edges_host(edges)
+        if not np.isfinite(host).all():
+            raise WsdlError(f"{name}: edges must be finite")
+        if not (np.diff(host.astype(np.float64)) > 0).all():
+            raise WsdlError(f"{name}: edges must be strictly ascending")
+    elif counts is None and thresh is None:
+        nb = _int_in(bins, name, "bins", 1, HIST_MAX_BINS)
+        if (not isinstance(range, (tuple, list)) or len(range) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, float)) or
+                                                                          not np.isfinite(v) for v in range) or not range[0] < range[1]):
+            raise WsdlError(f"{name}: range {range!r} must be two finite numbers (lo, hi), lo < hi")
+        host = uniform_edges(range[0], range[1], nb)
+        if not (np.diff(host.astype(np.float64)) > 0).all():
+            raise WsdlError(f"{name}: range {range!r} has no {nb} distinct float32 bins")
+    else:
+        nb = None
+    G = _int_in(num_groups, name, "num_groups", 1, HIST_MAX_GROUPS)
+    if counts is not None:
+        tensor(counts, "counts", torch.int64, rank=3)
+        S, G, row = counts.shape
+        if nb is None:
+            nb = row - 3
+        if row != nb + 3 or not 1 <= nb <= HIST_MAX_BINS:
+            raise WsdlError(f"{name}: counts {tuple(counts.shape)} must be (S, G, bins + 3) with 1..{HIST_MAX_BINS} bins"
+                            + ("" if edges is None else f" ({edges.numel()} edges given)"))
+        if not counts.is_contiguous():
+            raise WsdlError(f"{name}: counts must be dense")
+        inputs.append((counts, "counts"))
+        if sums is not None:
+            tensor(sums, "sums", torch.int64, shape=counts.shape)
+        if curves and G != 2:
+            raise WsdlError(f"{name}: curves need counts of G = 2 groups (group 1 the positives), got G = {G}")
+        if otsu_groups is not None:
+            for g in otsu_groups:
+                _int_in(g, name, "group", 0, G - 1)
+            if len(list(otsu_groups)) == 0:
+                raise WsdlError(f"{name}: groups selects nothing")
+        if isinstance(fallback, bool) or not isinstance(fallback, (int, float)) or not np.isfinite(fallback):
+            raise WsdlError(f"{name}: fallback {fallback!r} must be a finite number")
+        if isinstance(segment_pixels, bool) or not isinstance(segment_pixels, int) or segment_pixels < 0:
+            raise WsdlError(f"{name}: segment_pixels {segment_pixels!r} must be an int >= 0")
+        if segment_pixels > OTSU_MAX_PIXELS:
+            raise WsdlError(f"{name}: segments of {segment_pixels} pixels, at most 2^21 = {OTSU_MAX_PIXELS} are supported")
+    if G > HIST_MAX_GROUPS or (nb is not None and G * (nb + 3) > HIST_MAX_SLOTS):
+        raise WsdlError(f"{name}: {G} groups x ({nb} + 3) slots, at most {HIST_MAX_GROUPS} groups and {HIST_MAX_SLOTS} slots")
+    if want_sums and host is not None and np.abs(host).max() > 128.0:
+        raise WsdlError(f"{name}: want_sums needs every edge in [-128, 128]")
+    if thresh is not None:
+        if torch.is_tensor(thresh):
+            tensor(thresh, "thresh", torch.float32, shape=(B,))
+            inputs.append((thresh, "thresh"))
+        elif isinstance(thresh, bool) or not isinstance(thresh, (int, float)):
+            raise WsdlError(f"{name}: thresh {thresh!r} must be a number or a float32 (B,) tensor")
+    outs = []
+    if out is not None and not isinstance(out, dict):
+        raise WsdlError(f"{name}: out must be a dict of tensors to fill")
+    for what, t in list((out or {}).items()) + list(extra_outs):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or t.requires_grad:
+            raise WsdlError(f"{name}: {what} must be a tensor that needs no gradient")
+        for other, oname in inputs + outs:
+            if _shares_memory(t, other):
+                raise WsdlError(f"{name}: {what} shares memory with {oname}")
+        outs.append((t, what))
+        tensors.append((t, what))
+    device = None                                   # the place last: everything above can be refused without a device
+    for t, what in tensors:
+        if not t.is_cuda:
+            raise WsdlError(f"{name}: {what}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
+        if device is None:
+            device = t.device
+        elif t.device != device:
+            raise WsdlError(f"{name}: {what} is on {t.device}, the other tensors on {device}")
+    return G, nb, host
+
+
+def score_histogram(scores, groups=None, *, edges=None, bins=256, range=(0.0, 1.0), num_groups=1, per_image=True, want_sums=False,
+                    out=None):
+    """Grouped histogram of the float32 device planes ``scores`` (B, ...) with exact integer counts kept on the device
+    (wsdl_score_hist).  ``groups``: int64 of the shape of ``scores`` or None (all group 0); a pixel whose group is outside
+    ``[0, num_groups)`` is not counted (a trimap's 2, the void label 255).  ``edges``: ``nb + 1`` strictly ascending float32 values on
+    the device, or None for ``uniform_edges(*range, bins)``.  Returns int64 ``counts`` (S, G, nb + 3), S = B with ``per_image`` else 1;
+    the slots, defined by comparisons alone: 0: ``v < edges[0]``; ``1 + k``: ``edges[k] <= v < edges[k + 1]``; ``nb + 1``:
+    ``v >= edges[nb]``; ``nb + 2``: NaN.  With ``want_sums`` also ``sums`` of the same shape: the sum of
+    ``int64(v * 2^24)`` (exact product, truncated) over the pixels of the slots 1 .. nb - every edge must then lie in [-128, 128].
+    ``out``: a dict whose dense ``"counts"`` / ``"sums"`` tensors are refilled (no stale counts: the call zeroes them).  Inputs are
+    not modified; non-dense inputs are made dense first; no host read, bitwise reproducible, a launch plan can hold the call."""
+    G, nb, host = check_score_hist_options(scores, groups, edges=edges, bins=bins, range=range, num_groups=num_groups,
+                                           per_image=per_image, want_sums=want_sums, out=out)
+    scores = scores.detach()
+    scores = scores if scores.is_contiguous() else scores.contiguous()
+    if groups is not None:
+        groups = groups if groups.is_contiguous() else groups.contiguous()
+    if edges is None:
+        edges = uniform_edges(range[0], range[1], nb, scores.device)
+    B = scores.shape[0]
+    HW = scores.numel() // B
+    S = B if per_image else 1
+    counts = _out_tensor(out, "counts", (S, G, nb + 3), torch.int64, scores.device)
+    sums = _out_tensor(out, "sums", (S, G, nb + 3), torch.int64, scores.device) if want_sums else None
+    check(lib().wsdl_score_hist(_p(scores), _p(groups), _p(edges), host.ctypes.data, B, HW, G, nb, int(bool(per_image)), _p(counts),
+                                _p(sums), _stream()))
+    counts._wsdl_segment_pixels = HW if per_image else B * HW
+    return (counts, sums) if want_sums else counts
+
+
+def threshold_curves(counts, out=None):
+    """From the ``counts`` (S, 2, nb + 3) of ``score_histogram`` with two groups - group 1 the positives - int64 ``curves``
+    (S, nb + 1, 4) on the device: TP, FP, FN, TN of the prediction ``v >= edges[k]`` for k = 0 .. nb (wsdl_hist_curves).  NaN
+    pixels and pixels below the first edge are never predicted positive.  ``out``: a dense int64 tensor to fill."""
+    _G, nb, _ = check_score_hist_options(counts=counts, curves=True, extra_outs=[("out", out)], name="threshold_curves")
+    S = counts.shape[0]
+    if out is None or tuple(out.shape) != (S, nb + 1, 4) or out.dtype != torch.int64 or not out.is_contiguous():
+        out = torch.empty(S, nb + 1, 4, device=counts.device, dtype=torch.int64)
+    check(lib().wsdl_hist_curves(_p(counts), S, nb, _p(out), _stream()))
+    return out
+
+
+def otsu_threshold(counts, edges, groups=None, fallback=0.5, *, segment_pixels=None):
+    """Otsu's threshold per segment from ``counts`` (S, G, nb + 3) over the bins 1 .. nb of the groups ``groups`` (ints; None: all),
+    on the device (wsdl_otsu).  With h_i the bin counts, for k = 0 .. nb - 2: ``w0 = sum_{i<=k} h_i``, ``w1 = N - w0``,
+    ``s0 = sum_{i<=k} i h_i``, ``s1 = S - s0``, ``D = s0 w1 - s1 w0`` (int64), ``q(k) = (float64(D) * float64(D)) / float64(w0 w1)``
+    where ``w0 w1 > 0``.  Returns ``(k, threshold, q)``: int32 ``k*`` = the first maximum of q, float32 ``edges[k* + 1]`` (pixels
+    with ``v >= threshold`` are foreground) and float64 ``q(k*)``; with fewer than two occupied bins ``k* = -1``, the threshold is
+    ``fallback`` and q is 0.  Segments of more than 2^21 pixels are refused (D must stay below 2^53): the size is what
+    ``score_histogram`` recorded for ``counts``, or ``segment_pixels``; a segment that holds more all the same gets ``k* = -2`` and
+    NaN.  Equal to the same formula in numpy float64 bit for bit."""
+    npix = segment_pixels if segment_pixels is not None else getattr(counts, "_wsdl_segment_pixels", 0)
+    G, nb, _ = check_score_hist_options(counts=counts, edges=edges, otsu_groups=groups, fallback=fallback, segment_pixels=npix,
+                                        name="otsu_threshold")
+    mask = (1 << G) - 1 if groups is None else sum(1 << g for g in set(int(g) for g in groups))
+    S = counts.shape[0]
+    dev = counts.device
+    k = torch.empty(S, device=dev, dtype=torch.int32)
+    thr = torch.empty(S, device=dev, dtype=torch.float32)
+    q = torch.empty(S, device=dev, dtype=torch.float64)
+    check(lib().wsdl_otsu(_p(counts), _p(edges), S, G, nb, mask, float(fallback), npix, _p(k), _p(thr), _p(q), _stream()))
+    return k, thr, q
+
+
+def threshold_per_image(scores, thresh, positive_only=True, want_count=False, out=None):
+    """uint8 ``mask[b, ...] = scores[b, ...] >= thresh[b]``, with ``positive_only`` (the LayerCAM epilogue's rule) also
+    ``scores > 0`` (wsdl_threshold_images).  ``scores``: float32 device planes (B, ...); ``thresh``: a float32 (B,) device tensor -
+    what ``otsu_threshold`` returns - or a number; a NaN threshold gives an empty mask.  ``want_count``: also the int64 (B,) number
+    of set pixels, from the same launch.  ``out``: a dict whose ``"mask"`` / ``"count"`` tensors are filled.  No host read."""
+    check_score_hist_options(scores, thresh=thresh, out=out, name="threshold_per_image")
+    scores = scores.detach()
+    scores = scores if scores.is_contiguous() else scores.contiguous()
+    B = scores.shape[0]
+    if not torch.is_tensor(thresh):
+        thresh = torch.full((B,), float(thresh), device=scores.device, dtype=torch.float32)
+    thresh = thresh if thresh.is_contiguous() else thresh.contiguous()
+    mask = _out_tensor(out, "mask", tuple(scores.shape), torch.uint8, scores.device)
+    count = _out_tensor(out, "count", (B,), torch.int64, scores.device) if want_count else None
+    check(lib().wsdl_threshold_images(_p(scores), _p(thresh), B, scores.numel() // B, int(bool(positive_only)), _p(mask), _p(count),
+                                      _stream()))
+    return (mask, count) if want_count else mask
+
+
+def confidence_histogram(logits, labels, bins=15, ignore_index=-100, per_image=False, conf_out=None, pred_out=None):
+    """The reliability table of a classifier's float32 device logits (B,C,H,W), C <= 64, against int64 labels (B,H,W)
+    (wsdl_confidence_hist).  Per pixel ``pred`` = the first class of largest logit and ``conf`` = the softmax maximum, taken in
+    double and rounded once to float32 (NaN where a logit is not finite: the NaN slot); a pixel with ``label != ignore_index`` is
+    counted in group ``(pred == label)`` of a two-group histogram over ``bins`` uniform edges on [0, 1].  Returns ``(counts, sums)``
+    as ``score_histogram(..., want_sums=True)`` does, (S, 2, bins + 3) with S = B for ``per_image`` else 1.  ``conf_out`` /
+    ``pred_out``: dense float32 / int64 (B,H,W) tensors that receive the two planes (every pixel).  No host read."""
+    check_score_hist_options(logits=logits, labels=labels, ignore_index=ignore_index, bins=bins, range=(0.0, 1.0), num_groups=2,
+                             per_image=per_image, want_sums=True, extra_outs=[("conf_out", conf_out), ("pred_out", pred_out)],
+                             name="confidence_histogram")
+    logits = logits.detach()
+    logits = logits if logits.is_contiguous() else logits.contiguous()
+    labels = labels if labels.is_contiguous() else labels.contiguous()
+    B, Cc, H, W = logits.shape
+    for t, what, dtype in ((conf_out, "conf_out", torch.float32), (pred_out, "pred_out", torch.int64)):
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != (B, H, W) or not t.is_contiguous()):
+            raise WsdlError(f"confidence_histogram: {what} must be a dense {dtype} {(B, H, W)} tensor")
+    edges = uniform_edges(0.0, 1.0, bins, logits.device)
+    S = B if per_image else 1
+    counts = torch.empty(S, 2, bins + 3, device=logits.device, dtype=torch.int64)
+    sums = torch.empty_like(counts)
+    check(lib().wsdl_confidence_hist(_p(logits), _p(labels), _p(edges), _edges_host(edges).ctypes.data, B, Cc, H, W, int(ignore_index),
+                                     bins, int(bool(per_image)), _p(counts), _p(sums), _p(conf_out), _p(pred_out), _stream()))
+    counts._wsdl_segment_pixels = H * W if per_image else B * H * W
+    return counts, sums
+
+
+# host-side float64 reductions of the (tiny) count tensors: numpy, no kernels
+def _np64(x):
+    return (x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)).astype(np.float64)
+
+
+def _ratio(num, den, empty):
+    num, den = np.broadcast_arrays(np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64))
+    return np.where(den > 0, num / np.where(den > 0, den, 1.0), empty)
+
+
+def iou_curve_from_counts(curves, empty=1.0, eps=0.0):
+    """IoU of the foreground per threshold from ``curves`` (..., 4) = TP FP FN TN: ``TP / (TP + FP + FN)`` in float64, ``empty``
+    where the union is 0.  ``eps > 0``: ``TP / (union + eps)`` at every entry instead - ``compute_iou_and_acc``'s expression, which
+    gives 0 for an empty union."""
+    c = _np64(curves)
+    union = c[..., 0] + c[..., 1] + c[..., 2]
+    return c[..., 0] / (union + eps) if eps > 0 else _ratio(c[..., 0], union, empty)
+
+
+def accuracy_curve_from_counts(curves):
+    """Pixel accuracy per threshold: ``(TP + TN) / (TP + FP + FN + TN)``, 0 for an empty segment."""
+    c = _np64(curves)
+    return _ratio(c[..., 0] + c[..., 3], c.sum(axis=-1), 0.0)
+
+
+def _fbeta_curve(c, beta2):
+    return _ratio((1.0 + beta2) * c[..., 0], (1.0 + beta2) * c[..., 0] + beta2 * c[..., 2] + c[..., 1], 0.0)
+
+
+def best_threshold(curves, edges, metric="iou", reduce="dataset", beta2=0.3):
+    """The threshold of best ``metric`` ('iou' | 'f', the F-measure with ``beta2``) from ``curves`` (S, nb + 1, 4):
+    ``reduce='dataset'`` pools the counts of the segments first, 'mean_image' averages the per-segment metric.  Returns
+    ``(threshold, value, k)``: the first maximum."""
+    if metric not in ("iou", "f") or reduce not in ("dataset", "mean_image"):
+        raise WsdlError(f"best_threshold: metric {metric!r} ('iou' | 'f'), reduce {reduce!r} ('dataset' | 'mean_image')")
+    c, e = _np64(curves), _np64(edges)
+    c = c.reshape((-1,) + c.shape[-2:])
+    if c.shape[1] != e.shape[0]:
+        raise WsdlError(f"best_threshold: curves {c.shape} do not belong to {e.shape[0]} edges")
+    if reduce == "dataset":
+        c = c.sum(axis=0, keepdims=True)
+    m = (iou_curve_from_counts(c) if metric == "iou" else _fbeta_curve(c, beta2)).mean(axis=0)
+    k = int(np.argmax(m))
+    return float(e[k]), float(m[k]), k
+
+
+def pr_curve(curves):
+    """``(precision, recall)`` per threshold from pooled ``curves`` (..., nb + 1, 4): TP / (TP + FP), 1 where nothing is predicted,
+    and TP / (TP + FN), 0 where there is no positive."""
+    c = _np64(curves)
+    c = c.reshape((-1,) + c.shape[-2:]).sum(axis=0)
+    return _ratio(c[:, 0], c[:, 0] + c[:, 1], 1.0), _ratio(c[:, 0], c[:, 0] + c[:, 2], 0.0)
+
+
+def average_precision(curves):
+    """Area under the precision-recall steps of ``pr_curve``: ``sum_k (R_k - R_{k+1}) P_k`` with the thresholds ascending and
+    ``R_{nb+1} = 0``.  Positives below the first edge are never recalled."""
+    p, r = pr_curve(curves)
+    return float(np.sum((r - np.append(r[1:], 0.0)) * p))
+
+
+def max_fbeta(curves, beta2=0.3):
+    """``(F_max, k)``: the maximum over the thresholds of ``(1 + beta2) P R / (beta2 P + R)`` from the pooled ``curves``, and the
+    first threshold index that reaches it (beta2 = 0.3: the saliency literature's F-measure)."""
+    c = _np64(curves)
+    f = _fbeta_curve(c.reshape((-1,) + c.shape[-2:]).sum(axis=0), beta2)
+    k = int(np.argmax(f))
+    return float(f[k]), k
+
+
+def _pooled_bins(counts, sums, hi):
+    """Per group (2, nb): pixel counts and value sums of the bins; the slot above the last edge joins the last bin at value ``hi``."""
+    c, s = _np64(counts), _np64(sums) / HIST_SUM_SCALE
+    c, s = c.reshape((-1,) + c.shape[-2:]).sum(axis=0), s.reshape((-1,) + s.shape[-2:]).sum(axis=0)
+    n, v = c[:, 1:-2].copy(), s[:, 1:-2].copy()
+    n[:, -1] += c[:, -2]
+    v[:, -1] += c[:, -2] * hi
+    return c, n, v
+
+
+def mae_from_sums(counts, sums, lo=0.0, hi=1.0):
+    """Mean absolute error of a score map against the binary ground truth its two groups encode (group 1: target 1), from the
+    ``(counts, sums)`` of ``score_histogram(..., num_groups=2, want_sums=True)`` over [lo, hi]: values outside the range count as
+    clamped to it, NaN pixels are left out."""
+    c, n, v = _pooled_bins(counts, sums, hi)
+    v[:, 0] += c[:, 0] * lo
+    n[:, 0] += c[:, 0]
+    total = n.sum()
+    return float((v[0].sum() + (n[1].sum() - v[1].sum())) / total) if total else 0.0
+
+
+def ece_from_counts(counts, sums):
+    """Expected calibration error from the ``(counts, sums)`` of ``confidence_histogram`` (pooled over the segments):
+    ``(ece, accuracy, mean confidence, count)`` with one entry per bin; a confidence of exactly 1 belongs to the last bin; empty
+    bins have NaN accuracy and confidence and weigh nothing."""
+    _c, n, v = _pooled_bins(counts, sums, 1.0)
+    cnt = n[0] + n[1]
+    acc, conf = _ratio(n[1], cnt, np.nan), _ratio(v[0] + v[1], cnt, np.nan)
+    total = cnt.sum()
+    ece = float(np.sum(np.where(cnt > 0, cnt * np.abs(np.where(cnt > 0, acc - conf, 0.0)), 0.0)) / total) if total else 0.0
+    return ece, acc, conf, cnt.astype(np.int64)
+
+
+def tau_for_precision(counts, edges, target):
+    """The smallest edge at and above which the pooled accuracy of ``confidence_histogram``'s counts is at least ``target``; None
+    where no edge with a pixel at or above it qualifies."""
+    c, e = _np64(counts), _np64(edges)
+    c = c.reshape((-1,) + c.shape[-2:]).sum(axis=0)
+    right = np.cumsum(c[1, 1:-1][::-1])[::-1]
+    both = np.cumsum((c[0, 1:-1] + c[1, 1:-1])[::-1])[::-1]
+    for k in np.arange(e.shape[0]):
+        if both[k] > 0 and right[k] / both[k] >= target:
+            return float(e[k])
+    return None
+
+
 def softmax_channels(x):
     return _SoftmaxChannels.apply(x)
 
